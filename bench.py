@@ -17,14 +17,25 @@ Input form.  `value` is timed on the form the reference consumes: ASCII bases + 
 (vg_reads_process_device).  The reduced form -- one gate word per read, what the device-side FASTQ framing hands the read loop
 (vg_reads_process_device_gated) -- is timed in the same run and reported as `other_input_form` (`--gate-words` swaps the two).
 
-Secondary configurations (N = 1, default workload only; `--secondary none` switches them off).  After the main line's legs the
-same run measures, each with its own roofline and a parity check against the oracle: the 50 % low-quality stress profile on the
-index that is already open; then, as child processes of this one (each prints its own JSON line, which becomes an entry of
+Secondary configurations (`--full`, N = 1, default workload only; `--secondary none` switches them off).  After the main line's
+legs the same run measures, each with its own roofline and a parity check against the oracle: the 50 % low-quality stress profile
+on the index that is already open; then, as child processes of this one (each prints its own JSON line, which becomes an entry of
 `secondary`): chr22-scale (configs[1]), the repeat-rich hg38-size genome (--repeats 0.3), and the index of configs[4] (hg38 +
 100 M SNPs) on one replica.  A leg is skipped, with the reason stated, when the run's time budget ($VG_BENCH_BUDGET_S, default
-1500 s) would not hold it; a failing leg never fails the main line.
+540 s) would not hold it; a failing leg never fails the main line.
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload hg38|chr22|hg38f]
+Plain run and `--full`.  A plain run does only what the headline figure needs: it sets up (data set, index files, index open,
+resident batches), warms up, times the K steps, writes the outputs when `--dump-outputs DIR` is given and prints the line.
+Everything else -- the counted pass and the roofline, the gather-ceiling probe, the device pre-touch, the CPU baselines (oracle
+and reference binary) and the parity checks, the other input form, `sustained`, ingest, `job`, `job_stream`, the multi-GPU
+verification and per-rank figures, the secondary legs -- runs under `--full` only.  A `--full` run keeps to a time budget
+($VG_BENCH_BUDGET_S, default 540 s): a leg that would not fit is skipped with the reason stated.
+
+`--dump-outputs DIR`: after the timed steps, what the timed path handed its caller -- the clamped per-site counters fetched after
+the K-th step -- goes to DIR as float32 .npy files (a fixed, seeded sample of the sites when the whole arrays would pass 48 MB,
+plus histograms of the whole arrays); the same arguments give the same inputs, so two builds can be compared output for output.
+
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload hg38|chr22|hg38f] [--full] [--dump-outputs DIR]
 `--gpus N` with N > 1 starts the N ranks itself (one per GPU, `python -m torch.distributed.run`, before anything in this
 process touches a GPU); under an external torchrun (WORLD_SIZE set) it runs as one rank of that job.
 """
@@ -90,12 +101,19 @@ def parse_args():
     ap.add_argument("--device-budget", type=int, default=None, help="device-memory budget of the index in bytes (vg_index_open_ex): the plan takes the widest tables and the views it holds")
     ap.add_argument("--detail-out", default=None, help="where the run's full record goes (every leg's phases, plans, notes: what used to be on the line before it outgrew the driver's parser); "
                     "default: bench_detail.json beside the index files, and gpurun_out/bench_detail_<workload>.json when that directory exists.  The LAST stdout line stays a compact object (< 8000 bytes)")
+    ap.add_argument("--full", action="store_true", help="besides the headline figure, everything else this bench measures and checks: roofline and gather ceiling, CPU baselines and "
+                    "parity against the oracle, the other input form, sustained, ingest, job, job_stream, multi-GPU verification, secondary legs (within $VG_BENCH_BUDGET_S)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write the counters the timed path fetched after its last step to DIR as .npy (float32)")
     args = ap.parse_args()
     for k, v in PRESETS[args.workload].items():
         if getattr(args, k) is None:
             setattr(args, k, v)
     args.cpu_sample = min(args.cpu_sample, args.reads)
     args.ascii_quals = not args.gate_words
+    if not args.full:
+        # a plain run: set up, warm up, time the K steps, (dump), print the line -- nothing else
+        args.secondary, args.cpu_sample, args.sustain_seconds, args.job_reads, args.stream_reads = "none", 0, 0.0, 0, 0
+        args.no_gather_probe = args.no_pretouch = args.no_ingest = args.no_check = True
     return args
 
 
@@ -867,7 +885,7 @@ def job_stream(src, d, job_dir, prefix, dev_index, n_reads, batch_reads, lowq, r
 
 IDLE_BEFORE_CHILD_S = 20.0        # seconds between this process's release of the device and a child's start (see job_run)
 T_START = time.time()
-BUDGET_S = float(os.environ.get("VG_BENCH_BUDGET_S", "1500"))
+BUDGET_S = float(os.environ.get("VG_BENCH_BUDGET_S", "540"))         # (a --full run ends within ten minutes)
 # (estimated wall seconds, bench.py arguments) of the secondary legs that run as child processes, in this order
 # (measured on the pool's boxes: 15 s, 145 s, 315 s)
 CHILD_LEGS = [("chr22", 60, ["--workload", "chr22", "--steps", "40", "--warmup", "5"]),
@@ -942,6 +960,29 @@ def timed_block(gx, run, batches, steps, first=0):
     dt = time.perf_counter() - t0
     del fetched
     return dt
+
+
+DUMP_WHOLE_BYTES = 48 << 20      # float32 bytes of the two counter arrays below which they are written whole
+DUMP_SAMPLE_SITES = 3 << 20      # sites of the fixed sample above that (2 x 12 MiB of counters + 24 MiB of site indices)
+
+
+def dump_outputs(out_dir, ref_cnt, alt_cnt):
+    """What the timed path handed its caller after its last step -- the clamped per-site counters (ref, alt) -- as float32 .npy files
+    in `out_dir`: whole when they fit DUMP_WHOLE_BYTES, else at a fixed, seeded sample of the sites (`sample_sites.npy`, float64
+    site indices, the same for every run with the same arguments), plus the histogram of each whole array over 0..63 (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    ref_cnt, alt_cnt = np.asarray(ref_cnt), np.asarray(alt_cnt)
+    n = len(ref_cnt)
+    for name, a in (("ref_cnt", ref_cnt), ("alt_cnt", alt_cnt)):
+        np.save(os.path.join(out_dir, name + "_hist.npy"), np.bincount(a, minlength=64).astype(np.float64))
+    if 2 * 4 * n <= DUMP_WHOLE_BYTES:
+        sel = None
+    else:
+        sel = np.sort(np.random.default_rng(20261002).choice(n, size=DUMP_SAMPLE_SITES, replace=False))
+        np.save(os.path.join(out_dir, "sample_sites.npy"), sel.astype(np.float64))
+    for name, a in (("ref_cnt", ref_cnt), ("alt_cnt", alt_cnt)):
+        np.save(os.path.join(out_dir, name + ".npy"), (a if sel is None else a[sel]).astype(np.float32))
+    log("[bench] outputs written to %s: %s of %d sites" % (out_dir, "all" if sel is None else "a fixed sample of %d" % len(sel), n))
 
 
 def check_against_oracle(gx, ox, run, batch, n_check, st_full, ref):
@@ -1027,7 +1068,7 @@ def compact_line(out, detail_path):
                       "index_bytes_hbm": c["index_bytes_hbm"], "index_views": _short(",".join(c.get("index_views") or []) if isinstance(c.get("index_views"), (list, tuple)) else c.get("index_views"), 80), "index_open_s": _r(c["index_open_s"], 4), "lib_build_id": c["lib_build_id"],
                       "parallelism": _short(c["parallelism"], 120)}
     gcl = rf.get("gather_ceiling") or {}
-    line["roofline"] = {"bound": rf.get("bound"), "achieved": _r(rf.get("achieved")), "peak": rf.get("peak"), "unit": rf.get("unit"), "frac": _r(rf.get("frac")), "kernel": rf.get("kernel"),
+    line["roofline"] = None if not rf else {"bound": rf.get("bound"), "achieved": _r(rf.get("achieved")), "peak": rf.get("peak"), "unit": rf.get("unit"), "frac": _r(rf.get("frac")), "kernel": rf.get("kernel"),
                         "kernel_ms": _r(rf.get("kernel_ms")), "algorithmic_bytes_per_launch": rf.get("algorithmic_bytes_per_launch"), "algorithmic_bytes_per_read": _r(rf.get("algorithmic_bytes_per_read"), 6),
                         "traffic": rf.get("traffic"), "traffic_source": _short(rf.get("traffic_source"), 90),
                         "random_line_ceiling_GB_per_s": _r(gcl.get("peak_GB_per_s"), 4), "frac_of_random_line_ceiling": _r(gcl.get("frac"), 4)}
@@ -1166,7 +1207,7 @@ def run_child_leg(name, est, extra, args, ref):
     if room is not None and room < CHILD_LEG_ROOM_GB.get(name, 100) * 1e9:
         return {"skipped": "container memory: %.0f GB left (cgroup memory.max), this leg needs %d GB" % (room / 1e9, CHILD_LEG_ROOM_GB.get(name, 100))}
     ref.wait_quiet("secondary leg %s" % name)
-    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--secondary", "none", "--no-gather-probe", "--no-ingest", "--cpu-reference", "no", "--sustain-seconds", "0",
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--gpus", "1", "--secondary", "none", "--no-gather-probe", "--no-ingest", "--cpu-reference", "no", "--sustain-seconds", "0",
            "--cleanup", "--cpu-sample", "200000", "--job-reads", "0", "--no-pretouch"] + extra
     detail = os.path.join(args.workdir, "bench_detail_child_%s.json" % name)
     cmd += ["--detail-out", detail]
@@ -1174,7 +1215,7 @@ def run_child_leg(name, est, extra, args, ref):
         cmd += ["--workdir", args.workdir]
     time.sleep(IDLE_BEFORE_CHILD_S)                        # (the device's memory, just freed by the process before, scrubbed: see job_run)
     t0 = time.time()
-    log("[bench] secondary leg %s: %s" % (name, " ".join(cmd[2:])))
+    log("[bench] secondary leg %s: %s" % (name, " ".join(cmd[3:])))
     try:
         ref.heavy_begin()
         limit = max(60.0, min(left - 20.0, 2.5 * est))
@@ -1285,7 +1326,7 @@ def main():
         while not os.path.exists(prefix + ".done"):
             time.sleep(1.0)
     files_warm = None
-    if rank == 0 and args.genome >= 10 ** 9:
+    if rank == 0 and args.genome >= 10 ** 9 and args.full:
         files_warm = warm_index_files(prefix)
         log("[bench] index files read once before the open: %.1f GB in %.1f s (%.1f GB/s)" % (files_warm["GB"], files_warm["seconds"], files_warm["GB_per_s"]))
     pretouched = pretouch_finish(pretouch, log)
@@ -1349,7 +1390,7 @@ def main():
     src = synth.DeviceReadSource(g, s, dev)
     del g, s
     batches = [src.batch(rank * 1000 + b, args.reads, length=args.read_len, lowq=args.lowq) for b in range(args.batches)]
-    common = src.batch(999_999, min(args.reads, 1_000_000), length=args.read_len, lowq=args.lowq) if world > 1 else None
+    common = src.batch(999_999, min(args.reads, 1_000_000), length=args.read_len, lowq=args.lowq) if (world > 1 and args.full) else None
     # the stress profile's batches (50 % low-quality characters) wait on the host until their leg
     # (likewise the batches of the read-length legs: 101 bp -- the reference's own experiment, 3 chunks -- and 250 bp, 7 chunks)
     lowq_host = None
@@ -1415,12 +1456,14 @@ def main():
         else:
             gx.process_device_gated(b[0], b[3], b[2], len(b[2]) - 1)
 
-    # ---- one counted pass over batch 0: event counts -> algorithmic bytes; parity against the oracle ------------------------
-    gx.set_stats(True)
-    gx.reset()
-    run(batches[0])
-    st = gx.stats()
-    alg_bytes_per_launch = st["alg_bytes"]
+    # ---- one counted pass over batch 0 (--full): event counts -> algorithmic bytes; parity against the oracle ----------------
+    st, alg_bytes_per_launch = None, None
+    if args.full:
+        gx.set_stats(True)
+        gx.reset()
+        run(batches[0])
+        st = gx.stats()
+        alg_bytes_per_launch = st["alg_bytes"]
     cpu, parity, ox = None, None, None
     if rank == 0 and world == 1 and args.cpu_sample > 0:        # the CPU legs (and the parity check they feed) run at N = 1 only
         from oracle import oracle as O
@@ -1504,7 +1547,7 @@ def main():
     # ---- N > 1: the sharded path must reproduce one rank.  Every rank takes its shard of one common stream; the all-reduced
     #      counters must equal what rank 0 gets from the whole stream alone. ---------------------------------------------------
     verification = None
-    if world > 1:
+    if world > 1 and args.full:
         gx.set_stats(False)
         cb, cq, co = common
         n_c = len(co) - 1
@@ -1557,6 +1600,8 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *fetched)
     del fetched
     tm = gx.timing()                                    # HIP events on the library's own streams, averaged over the K batches
     per_rank = None
@@ -1568,6 +1613,7 @@ def main():
         dist.all_reduce(local_sum)
         total_after = int(gx.counts_tensor().sum(dtype=torch.int64).item())
         assert total_after == int(local_sum.item()), "reduced counters hold %d increments, the ranks made %d" % (total_after, int(local_sum.item()))
+    if world > 1 and args.full:
         # what every rank saw, so that a scaling run explains itself: main-tier kernel ms, steps' wall ms, the exchange's ms
         mine = torch.tensor([tm["ms_main"], 1e3 * (t_steps_done - t0) / args.steps, 1e3 * t_reduce, t_open, cpu_open, gx.device_bytes / 1e9], dtype=torch.float64, device=coll_dev)
         allr = [torch.zeros_like(mine) for _ in range(world)]
@@ -1583,7 +1629,7 @@ def main():
 
     # ---- the other input form, for the record (N = 1): the same K steps with the gate words handed over (or, under --gate-words, the strings)
     other_form, sustained = None, None
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         gx.reset()
         for i in range(min(args.warmup, 2)):
             run(batches[i % args.batches], strings=not args.ascii_quals)
@@ -1674,6 +1720,11 @@ def main():
         if hb is None or ox is None:
             secondary[name] = {"skipped": "needs the oracle (--cpu-sample > 0) at N = 1"}
             continue
+        left = BUDGET_S - (time.time() - T_START)
+        if left < 120:
+            secondary[name] = {"skipped": "time budget: %.0f s of $VG_BENCH_BUDGET_S = %.0f s left" % (left, BUDGET_S)}
+            log("[bench] secondary %s: %s" % (name, secondary[name]["skipped"]))
+            continue
         try:
             secondary[name] = open_index_leg(name, hb, lq, L_, what)
         except Exception as e:                                 # a secondary leg never fails the main line
@@ -1687,7 +1738,7 @@ def main():
     if rank == 0 and ref_timer is not None:
         # the reference's own binary is the baseline of record; the port (oracle) stays beside it
         t0 = time.time()
-        refres = ref_timer.result()
+        refres = ref_timer.result(timeout=BUDGET_S - (time.time() - T_START) - 60)     # (past the budget: the port is the baseline)
         log("[bench] waited %.0fs more for the reference binary: %s" % (time.time() - t0, refres and "%.4g reads/s" % refres["value"]))
         if refres is not None:
             port = cpu or {}
@@ -1742,7 +1793,7 @@ def main():
         left = BUDGET_S - (time.time() - T_START)
         if job_out is not None and "skipped" in job_out and job_dir is None:
             job_dir = "/tmp/vg_bench_job"
-        if left < 820:                                                # (the child legs behind this one need ~660 s, this leg ~110)
+        if left < 150:                                                # (this leg ~110 s; the child legs behind it are gated on the budget themselves)
             stream_out = {"skipped": "time budget: %.0f s left" % left}
         else:
             try:
@@ -1777,8 +1828,8 @@ def main():
     if rank == 0:
         ms_step = 1e3 * elapsed / args.steps
         k_ms = tm["ms_main"]
-        traffic, misses, traffic_note = traffic_for(args, build_id)
-        gc = None
+        traffic, misses, traffic_note = traffic_for(args, build_id) if args.full else (None, None, None)
+        gc, roof = None, None
         if ceiling:
             # An L2 miss of a random gather moves one 128-byte line (profiles/line_probe_r03_counters.txt), so the chip's measured
             # random-gather rate IS the HBM roofline for this access shape: lines/s x 128 B
@@ -1786,9 +1837,10 @@ def main():
                   "peak_GB_per_s": ceiling["gathers_per_s"] * 128 / 1e9,
                   "l2_misses_per_launch": misses, "achieved": (misses / (k_ms * 1e-3)) if misses else None}
             gc["frac"] = (gc["achieved"] / gc["peak"]) if misses else None
-        roof = roofline_of(alg_bytes_per_launch, k_ms, args.reads, kernel)
-        roof.update({"traffic": traffic, "traffic_source": traffic_note, "traffic_GB_per_s": (traffic / (k_ms * 1e-3) / 1e9) if traffic else None,
-                     "traffic_frac_of_peak": (traffic / (k_ms * 1e-3) / 1e9 / 8000.0) if traffic else None, "gather_ceiling": gc})
+        if alg_bytes_per_launch is not None:
+            roof = roofline_of(alg_bytes_per_launch, k_ms, args.reads, kernel)
+            roof.update({"traffic": traffic, "traffic_source": traffic_note, "traffic_GB_per_s": (traffic / (k_ms * 1e-3) / 1e9) if traffic else None,
+                         "traffic_frac_of_peak": (traffic / (k_ms * 1e-3) / 1e9 / 8000.0) if traffic else None, "gather_ceiling": gc})
         out = {
             "metric": "reads/sec genotyped (whole node), hg38+dbSNP 30×; achieved HBM GB/s vs peak",
             "value": world * args.reads * args.steps / elapsed,
@@ -1816,8 +1868,8 @@ def main():
             "device_ms_per_step": {"pack": tm["ms_pack"], "wave": k_ms, "spill_tiers_overlapped": tm["ms_tail"], "of_which_deep_list_wave_tier": tm["ms_deep_lists"], "batches": tm["batches"],
                                    "note": "spill tiers: elapsed time from the end of a batch's main-tier kernel to the end of its last tier, on the tail stream, under the NEXT batches' "
                                            "kernels -- mostly waiting (a tier's workgroups are placed when main-tier workgroups of the following batch retire), not work: see reads_per_step_redone_by_deep_list_tier"},
-            "reads_per_step_redone_by_deep_list_tier": st["overflow_reads"], "reads_per_step_sent_on_to_lane_tier": st["overflow_deep"],
-            "events_per_read": {k: st[k] / args.reads for k in ("passes", "chunks", "gate_open", "ref_query", "snp_query", "ctx", "walks", "incr")},
+            "reads_per_step_redone_by_deep_list_tier": st and st["overflow_reads"], "reads_per_step_sent_on_to_lane_tier": st and st["overflow_deep"],
+            "events_per_read": st and {k: st[k] / args.reads for k in ("passes", "chunks", "gate_open", "ref_query", "snp_query", "ctx", "walks", "incr")},
             "input_form": "ASCII bases + offsets + " + ("quality strings (what the reference reads; vg_reads_process_device)" if args.ascii_quals else "one gate word per read (bit c = quality character c < '8'; vg_reads_process_device_gated)") + ", resident in HBM",
             "fetch": "pinned (fold + clamp on the device, two bytes per site into a reused page-locked buffer, GenoIndex.counts(copy=False); rounds 1-3 fetched into pageable memory)",
             "other_input_form": other_form,

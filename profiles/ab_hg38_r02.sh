@@ -6,7 +6,7 @@ TAG=${1:-ab}
 OUT=$R/gpurun_out/ab_$TAG
 mkdir -p $OUT
 cd $R
-ARGS="--cpu-sample 0 --no-gather-probe --no-ingest --steps 20 --warmup 5"
+ARGS="--full --cpu-sample 0 --no-gather-probe --no-ingest --steps 20 --warmup 5"
 run() {   # name, env assignments...
 	local name=$1; shift
 	env "$@" VARGENO_VERBOSE=1 python3 bench.py $ARGS > $OUT/$name.json 2> $OUT/$name.err

@@ -6,7 +6,7 @@ TAG=${1:-ab}
 OUT=$R/gpurun_out/ab_$TAG
 mkdir -p $OUT
 cd $R
-ARGS="--cpu-sample 0 --no-gather-probe --no-ingest --steps 20 --warmup 5"
+ARGS="--full --cpu-sample 0 --no-gather-probe --no-ingest --steps 20 --warmup 5"
 run() {   # name, env assignments...
 	local name=$1; shift
 	env "$@" VARGENO_VERBOSE=1 python3 bench.py $ARGS > $OUT/$name.json 2> $OUT/$name.err
@@ -21,7 +21,7 @@ except Exception as e:
 PY
 }
 # the shipped build first, with the parity check of the whole 8 M-read batch against the oracle (both builds of the kernel)
-ARGS_KEEP=$ARGS; ARGS="--cpu-sample 1000 --cpu-reference no --no-gather-probe --no-ingest --steps 20 --warmup 5"
+ARGS_KEEP=$ARGS; ARGS="--full --cpu-sample 1000 --cpu-reference no --no-gather-probe --no-ingest --steps 20 --warmup 5"
 run base
 grep -E "parity" $OUT/base.err | tee -a $OUT/summary.txt
 ARGS=$ARGS_KEEP

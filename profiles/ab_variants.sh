@@ -5,6 +5,7 @@
 set -u
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
+set -- --full "$@"                                           # (the roofline read below is measured under --full)
 cp vargeno_amd/csrc/libvargeno_hip.so /tmp/shipped.so
 for v in variants/*.so; do
 	name=$(basename "$v" .so)

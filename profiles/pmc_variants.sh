@@ -1,7 +1,7 @@
 # one --pmc pass per prebuilt variant (variants/*.so): bash profiles/pmc_variants.sh "CTR1 CTR2 ..." [bench args]
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 CTRS="$1"; shift
-ARGS="${@:---steps 3 --warmup 1 --cpu-sample 0 --no-check --reads 8000000}"
+ARGS="${@:---full --steps 3 --warmup 1 --cpu-sample 0 --no-check --reads 8000000}"
 cp $R/vargeno_amd/csrc/libvargeno_hip.so /tmp/shipped.so
 cd /tmp && export TMPDIR=/tmp
 for v in $R/variants/*.so; do

@@ -5,13 +5,14 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/r06_s
 mkdir -p $OUT
+KEEP=$(mktemp -u --suffix=.fq)                               # (one batch of FASTQ text kept for pipe_ab.py)
 rm -rf /tmp/vg_bench /tmp/vg_bench_job /dev/shm/vg_bench* /dev/shm/vg_keep.fq /tmp/pytest-of-* 2>/dev/null
 cd $R
 ( while true; do echo "$(date +%s) mem $(cat /sys/fs/cgroup/memory.current 2>/dev/null) max $(cat /sys/fs/cgroup/memory.max 2>/dev/null) root $(df --output=used -B1 / | tail -1) shm $(df --output=used -B1 /dev/shm | tail -1)"; sleep 5; done ) > $OUT/watch.txt 2>&1 &
 W=$!
 bash profiles/device_code_sha.sh > $OUT/device_code.txt 2>&1; cat $OUT/device_code.txt
 timeout 400 python3 -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.txt 2>&1; tail -2 $OUT/smoke.txt
-( time VG_BENCH_KEEP_FASTQ=/dev/shm/vg_keep.fq timeout 1000 python3 bench.py --gpus 1 --steps 5 --warmup 2 --secondary none --no-gather-probe --no-ingest --cpu-reference no --sustain-seconds 0 --cpu-sample 0 --job-reads 8000000 --stream-reads 620000000 ) > $OUT/bench.json 2> $OUT/bench.err
+( time VG_BENCH_KEEP_FASTQ=$KEEP timeout 1000 python3 bench.py --full --gpus 1 --steps 5 --warmup 2 --secondary none --no-gather-probe --no-ingest --cpu-reference no --sustain-seconds 0 --cpu-sample 0 --job-reads 8000000 --stream-reads 620000000 ) > $OUT/bench.json 2> $OUT/bench.err
 grep -E "^\[bench\]" $OUT/bench.err | tail -12 | cut -c1-400
 python3 - $OUT/bench.json <<'PY'
 import json, sys
@@ -24,12 +25,12 @@ except Exception as e:
 PY
 cp /tmp/vg_bench/bench_detail_g3100000000_s10000000_c24.json $OUT/bench_detail.json 2>/dev/null
 D=/tmp/vg_bench/g3100000000_s10000000_c24
-if [ -s /dev/shm/vg_keep.fq ] && [ -e $D/idx.done ]; then
-	timeout 900 python3 profiles/pipe_ab.py $D /dev/shm/vg_keep.fq 24 \
+if [ -s $KEEP ] && [ -e $D/idx.done ]; then
+	timeout 900 python3 profiles/pipe_ab.py $D $KEEP 24 \
 		write64:LEND=0 lend64:LEND=1 lend16:LEND=1,VARGENO_CHUNK_MB=16 lend8:LEND=1,VARGENO_CHUNK_MB=8 lend4:LEND=1,VARGENO_CHUNK_MB=4 lend2:LEND=1,VARGENO_CHUNK_MB=2 write8:LEND=0,VARGENO_CHUNK_MB=8 lend64again:LEND=1 > $OUT/pipe_ab.jsonl 2> $OUT/pipe_ab.err
 	cat $OUT/pipe_ab.jsonl | cut -c1-700
 	tail -3 $OUT/pipe_ab.err
 fi
-rm -f /dev/shm/vg_keep.fq
+rm -f $KEEP
 kill $W
 awk '{ if ($3 > m) m = $3; if ($7 > r) r = $7; if ($9 > s) s = $9; mx = $5 } END { printf "peak cgroup memory %.1f GB of %.1f, root fs used %.1f GB, shm used %.1f GB\n", m / 1e9, mx / 1e9, r / 1e9, s / 1e9 }' $OUT/watch.txt

@@ -11,7 +11,7 @@ cat /sys/fs/cgroup/memory.stat 2>/dev/null | grep -E "^(anon|file|shmem|kernel|s
 cd $R
 ( while true; do echo "$(date +%s) mem $(cat /sys/fs/cgroup/memory.current) root $(df --output=used -B1 / | tail -1) shm $(df --output=used -B1 /dev/shm | tail -1)"; sleep 5; done ) > $OUT/watch.txt 2>&1 &
 W=$!
-( time timeout 2400 python3 bench.py --gpus 1 --steps 20 --warmup 5 "$@" ) > $OUT/bench.json 2> $OUT/bench.err
+( time timeout 2400 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 "$@" ) > $OUT/bench.json 2> $OUT/bench.err
 kill $W
 grep -E "^\[bench\]" $OUT/bench.err | tail -60 | cut -c1-250
 wc -c $OUT/bench.json

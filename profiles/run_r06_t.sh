@@ -10,7 +10,7 @@ cd $R
 W=$!
 ( time timeout 700 python -m pytest tests/test_gpu_fastq.py tests/test_gpu_multi.py tests/test_gpu_cli.py -x -q -m gpu --durations=8 -k "not hg38_scale" ) > $OUT/tests.txt 2>&1
 tail -14 $OUT/tests.txt
-( time timeout 1100 python3 bench.py --gpus 1 --steps 20 --warmup 5 --secondary lowq50,len101,len250 --cpu-reference no ) > $OUT/bench.json 2> $OUT/bench.err
+( time timeout 1100 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --secondary lowq50,len101,len250 --cpu-reference no ) > $OUT/bench.json 2> $OUT/bench.err
 grep -E "^\[bench\]" $OUT/bench.err | tail -30 | cut -c1-300
 wc -c $OUT/bench.json
 cp /tmp/vg_bench/bench_detail_g3100000000_s10000000_c24.json $OUT/bench_detail.json 2>/dev/null

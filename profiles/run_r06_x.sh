@@ -8,7 +8,7 @@ rm -rf /tmp/vg_bench /tmp/vg_bench_job /dev/shm/vg_bench* /tmp/pytest-of-* 2>/de
 cd $R
 bash profiles/device_code_sha.sh > $OUT/device_code.txt 2>&1; cat $OUT/device_code.txt
 timeout 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.txt 2>&1; tail -1 $OUT/smoke.txt
-( time timeout 600 python3 bench.py --gpus 1 --steps 5 --warmup 2 --secondary none --no-gather-probe --no-ingest --cpu-reference no --sustain-seconds 0 --cpu-sample 200000 --job-reads 0 ) > $OUT/bench.json 2> $OUT/bench.err
+( time timeout 600 python3 bench.py --full --gpus 1 --steps 5 --warmup 2 --secondary none --no-gather-probe --no-ingest --cpu-reference no --sustain-seconds 0 --cpu-sample 200000 --job-reads 0 ) > $OUT/bench.json 2> $OUT/bench.err
 grep -E "^\[bench\] (parity|index resident|vg_index_open)" $OUT/bench.err | cut -c1-330
 tail -c 300 $OUT/bench.json; echo
 P=/tmp/vg_bench/g3100000000_s10000000_c24/idx

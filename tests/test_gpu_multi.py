@@ -137,7 +137,7 @@ def test_two_ranks_shard_and_all_reduce_equal_one_rank(backend, ftiny_dir, ftiny
     matters; after GenoIndex.counts_tensor() / all_reduce_counts() every rank holds the counters of one rank on all
     reads.  gloo: both ranks share GPU 0 (any box); nccl = RCCL: needs two GPUs."""
     if backend == "nccl" and torch.cuda.device_count() < 2:
-        pytest.skip("RCCL refuses two ranks on one device; this box has %d GPU(s)" % torch.cuda.device_count())
+        pytest.skip("needs 2 GPUs, found %d (RCCL refuses two ranks on one device)" % torch.cuda.device_count())
     prefix = os.path.join(ftiny_dir, "idx")
     so = _oracle(prefix, ftiny_reads, times=7)
     got = _run_ranks(tmp_path, prefix, backend, 7)
@@ -154,7 +154,7 @@ def test_bench_starts_its_own_ranks(tmp_path):
     env = dict(os.environ, VG_BENCH_BACKEND=backend, VG_BENCH_DIR=str(tmp_path), HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "chr22", "--genome", "3000000", "--snps", "30000",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--workload", "chr22", "--genome", "3000000", "--snps", "30000",
                         "--reads", "20000", "--batches", "2", "--steps", "3", "--warmup", "1", "--cpu-sample", "0", "--no-gather-probe"],
                        env=env, capture_output=True, text=True, timeout=1200)
     assert p.returncode == 0, p.stderr[-4000:]
@@ -216,7 +216,7 @@ def test_bench_with_eight_ranks(tmp_path):
     env = dict(os.environ, VG_BENCH_BACKEND=backend, VG_BENCH_DIR=str(tmp_path), HSA_ENABLE_IPC_MODE_LEGACY="0", **LEAN)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--workload", "chr22", "--genome", "3000000", "--snps", "30000",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "8", "--workload", "chr22", "--genome", "3000000", "--snps", "30000",
                         "--reads", "20000", "--batches", "2", "--steps", "3", "--warmup", "1", "--cpu-sample", "0", "--no-gather-probe"],
                        env=env, capture_output=True, text=True, timeout=1200)
     assert p.returncode == 0, p.stderr[-4000:]
