@@ -4,6 +4,8 @@ from /root/reference).  Runs only in the build container; the GPU box and the te
 committed outputs.  Usage:  python tests/golden/make_golden.py [workdir]
 
 Produces
+  <name>.sha256  for every fixture below: its inputs, the six index files the reference wrote for it (the lite bit vector
+               idx.ref.bf.lite.bf among them) and its output VCF.
   ftiny.*      60 kbp / 2 951 SNPs / 4 000 reads -- committed whole: inputs, the reference-written
                dict files, the set bits of its bit-vector files, its output VCF.
   ftiny.info_<kind>.sha256  the reference's index files when the SNP list's INFO column is one of vcf_variants.INFO_KINDS
@@ -84,7 +86,7 @@ def run(name, gen, work, commit_all):
     subprocess.check_call([REF_BIN, "index", "ref.fa", "snps.vcf", "idx"], cwd=d, stdout=subprocess.DEVNULL)
     subprocess.check_call([REF_BIN, "geno", "idx", "reads.fq", "snps.vcf", "out.vcf"], cwd=d, stdout=subprocess.DEVNULL)
     files = ["ref.fa", "snps.vcf", "reads.fq", "idx.chrlens", "idx.ref.dict", "idx.snp.dict", "idx.ref.bf",
-             "idx.snp.bf", "out.vcf"]
+             "idx.ref.bf.lite.bf", "idx.snp.bf", "out.vcf"]
     with open(os.path.join(OUT, name + ".sha256"), "w") as f:
         for fn in files:
             f.write("%s  %s\n" % (sha(os.path.join(d, fn)), fn))

@@ -41,6 +41,17 @@ static const int AUX_COLS = 10;
 
 [[noreturn]] static void die(const std::string &m) { throw Error{m}; }
 
+// Where the build cuts its work (FASTA pieces, window and record chunks, the sort's counting pass, ...).  Every such number is
+// read once from the environment, clamped to [1, hi], so that tests can make the pieces tiny and put their boundaries inside
+// sequences, N runs and repeat copies; unset (or empty), the default holds.  The knobs are listed in main.cpp's header.
+static size_t env_knob(const char *name, size_t dflt, size_t hi = SIZE_MAX)
+{
+	const char *e = getenv(name);
+	if (!e || !*e) return dflt;
+	const long long v = atoll(e);
+	return std::min(hi, v < 1 ? (size_t)1 : (size_t)v);
+}
+
 // VARGENO_VERBOSE=1: wall time of the phases on stderr
 struct PhaseTimer {
 	const bool on = getenv("VARGENO_VERBOSE") != nullptr && atoi(getenv("VARGENO_VERBOSE")) != 0;
@@ -75,8 +86,8 @@ struct Seq { std::string name, seq; };
 // src/fasta_parser.c:35-133: a record starts at a '>' (wherever it stands); its name ends at '|', white space or 64 characters and
 // the rest of that line is skipped; its sequence is every character up to the next '>' except newlines, ACGT folded to upper
 // case, anything else mapped to N.  The bodies (3.1 GB for a human genome) are converted by all threads: newlines are counted
-// per 16 MiB piece first, so that every piece knows where its bases land.
-static std::vector<Seq> parse_fasta_dict(const std::string &buf)
+// per 16 MiB piece (VARGENO_FASTA_PIECE) first, so that every piece knows where its bases land.
+static std::vector<Seq> parse_fasta_dict(const std::string &buf, size_t piece_bytes, size_t &n_pieces)
 {
 	std::vector<Seq> out;
 	std::vector<std::pair<size_t, size_t>> body;                  // [begin, end) of every record's sequence text
@@ -103,10 +114,11 @@ static std::vector<Seq> parse_fasta_dict(const std::string &buf)
 	struct Piece { size_t rec, lo, hi, bases, at; };
 	std::vector<Piece> pieces;
 	for (size_t r = 0; r < body.size(); r++)
-		for (size_t lo = body[r].first; lo < body[r].second || lo == body[r].first; lo += (size_t)16 << 20) {
-			pieces.push_back(Piece{r, lo, std::min(body[r].second, lo + ((size_t)16 << 20)), 0, 0});
+		for (size_t lo = body[r].first; lo < body[r].second || lo == body[r].first; lo += piece_bytes) {
+			pieces.push_back(Piece{r, lo, std::min(body[r].second, lo + piece_bytes), 0, 0});
 			if (lo >= body[r].second) break;
 		}
+	n_pieces = pieces.size();
 	#pragma omp parallel for schedule(dynamic, 1)
 	for (long p = 0; p < (long)pieces.size(); p++) {
 		Piece &pc = pieces[(size_t)p];
@@ -288,15 +300,18 @@ static void partition_records(size_t n_chunks, Produce &&produce, Partitioned<T>
 // Sort one bucket of a partitioned dictionary by k-mer, equal k-mers keeping their order (the bucket is in input order).  The
 // records of a bucket share the top PART_BITS bits of the k-mer: one stable counting pass on the next SUB_BITS bits into a
 // scratch buffer leaves groups of a few hundred records, which are finished by a stable comparison sort in cache -- about
-// three sweeps over the bucket where a comparison sort of the whole 12 MB bucket makes twenty.
+// three sweeps over the bucket where a comparison sort of the whole 12 MB bucket makes twenty.  A bucket of fewer than
+// `counting_min` records (default 4 x 2^12, VARGENO_COUNTING_SORT_MIN) is sorted by the comparison sort alone.  Returns whether
+// the counting pass ran.
+static const size_t COUNTING_SORT_MIN = (size_t)4 << 12;
 template <class T>
-static void sort_bucket(T *lo, T *hi, std::vector<T> &tmp, std::vector<uint32_t> &cnt)
+static bool sort_bucket(T *lo, T *hi, std::vector<T> &tmp, std::vector<uint32_t> &cnt, size_t counting_min)
 {
 	const size_t n = (size_t)(hi - lo);
 	constexpr int SUB_BITS = 12;
 	constexpr size_t NS = (size_t)1 << SUB_BITS;
 	const auto less = [](const T &a, const T &b) { return a.kmer < b.kmer; };
-	if (n < 4 * NS) { std::stable_sort(lo, hi, less); return; }
+	if (n < counting_min) { std::stable_sort(lo, hi, less); return false; }
 	const auto digit = [](const T &r) { return (size_t)((r.kmer >> (64 - PART_BITS - SUB_BITS)) & (NS - 1)); };
 	cnt.assign(NS + 1, 0);
 	for (const T *p = lo; p < hi; p++) cnt[digit(*p) + 1]++;
@@ -311,6 +326,7 @@ static void sort_bucket(T *lo, T *hi, std::vector<T> &tmp, std::vector<uint32_t>
 		if (b - a > 1) std::stable_sort(a, b, less);
 	}
 	memcpy((void *)lo, (const void *)tmp.data(), n * sizeof(T));
+	return true;
 }
 
 // A dictionary file under construction: fixed-size records region + auxiliary rows region, produced bucket by bucket by many
@@ -327,7 +343,8 @@ struct DictFile {
 	struct Piece { std::vector<uint8_t> data; uint64_t off; };
 	std::deque<Piece> queue; size_t queued = 0; bool closing = false; std::string error;
 	std::mutex mu; std::condition_variable cv_push, cv_pop; std::thread writer;
-	static constexpr size_t QUEUE_BYTES = (size_t)2 << 30;
+	// stream: producers wait while this many bytes are queued for the writer (VARGENO_STREAM_QUEUE, default 2 GiB)
+	const size_t queue_bytes = env_knob("VARGENO_STREAM_QUEUE", (size_t)2 << 30);
 
 	DictFile(const std::string &p, size_t bytes) : path(p), size(bytes)
 	{
@@ -373,7 +390,7 @@ struct DictFile {
 		if (mode == MMAP) { memcpy(map + off, buf.data(), buf.size()); return; }
 		if (mode == PWRITE) { pwrite_all(buf.data(), buf.size(), off); return; }
 		std::unique_lock<std::mutex> g(mu);
-		cv_push.wait(g, [&] { return queued < QUEUE_BYTES; });
+		cv_push.wait(g, [&] { return queued < queue_bytes; });
 		queued += buf.size();
 		queue.push_back(Piece{std::move(buf), off});
 		g.unlock();
@@ -388,6 +405,7 @@ struct DictFile {
 		}
 	}
 	void finish() { finish_nothrow(); if (!error.empty()) die(error); }
+	const char *mode_name() const { return mode == STREAM ? "stream" : mode == MMAP ? "mmap" : "pwrite"; }
 };
 
 struct KP { uint64_t kmer; uint32_t pos; uint32_t pad; };
@@ -421,7 +439,15 @@ void build_index(const std::string &fasta, const std::string &vcf, const std::st
 	omp_set_num_threads(nthreads);
 	PhaseTimer pt;
 	// the SNP list is parsed in pieces of this many bytes (cut at line ends), in parallel; VARGENO_PARSE_PIECE: tests make it tiny
-	const size_t parse_piece_bytes = getenv("VARGENO_PARSE_PIECE") ? (size_t)std::max(1, atoi(getenv("VARGENO_PARSE_PIECE"))) : (size_t)4 << 20;
+	const size_t parse_piece_bytes = env_knob("VARGENO_PARSE_PIECE", (size_t)4 << 20, (size_t)1 << 40);
+	// the other places where the work is cut (a chunk holds < 2^32 records: partition_records counts them in 32 bits)
+	const size_t fasta_piece_bytes = env_knob("VARGENO_FASTA_PIECE", (size_t)16 << 20, (size_t)1 << 40);
+	const size_t bf_chunk = env_knob("VARGENO_BF_CHUNK", (size_t)1 << 22, (size_t)1 << 31);
+	const size_t kmer_chunk = env_knob("VARGENO_KMER_CHUNK", (size_t)1 << 22, (size_t)1 << 31);
+	const size_t snp_chunk = env_knob("VARGENO_SNP_CHUNK", (size_t)1 << 15, (size_t)1 << 26);
+	const size_t counting_min = env_knob("VARGENO_COUNTING_SORT_MIN", COUNTING_SORT_MIN);
+	// what the build did, for VARGENO_VERBOSE=1 (the tests read it: a knob that changes nothing shows here)
+	struct Cuts { size_t vcf_pieces = 0, fasta_pieces = 0, bf_chunks = 0, kmer_chunks = 0, snp_chunks = 0, snp_buckets = 0, snp_counting = 0, ref_buckets = 0, ref_counting = 0; bool dense = false; std::string write_mode; } cuts;
 	const std::string fa = slurp(fasta);
 	const std::string vcf_text = slurp(vcf);
 	pt.lap("inputs read");
@@ -430,7 +456,10 @@ void build_index(const std::string &fasta, const std::string &vcf, const std::st
 	{
 		std::vector<Seq> g = parse_fasta_bf(fa);
 		pt.lap("FASTA parsed (bit-vector side)");
-		const bool dense = fa.size() > ((size_t)256 << 20);
+		// VARGENO_DENSE_BF=1 / 0: dense / lazily-zeroed vectors whatever the FASTA's size
+		const char *dense_env = getenv("VARGENO_DENSE_BF");
+		const bool dense = dense_env && *dense_env ? atoi(dense_env) != 0 : fa.size() > ((size_t)256 << 20);
+		cuts.dense = dense;
 		BitVec bf(REF_BF_BITS, dense);
 		BitVec lite(opt.write_lite ? REF_LITE_BF_BITS : 64, dense && opt.write_lite);
 		// Bits to set: hash32(first 16 bases) of every N-free 32-mer -- 3.1 G scattered bits at hg38 scale.  Setting them with
@@ -442,8 +471,9 @@ void build_index(const std::string &fasta, const std::string &vcf, const std::st
 		for (size_t si = 0; si < g.size(); si++) {
 			if (g[si].seq.size() < 32) die("reference sequence shorter than 32 bases: " + g[si].name);      // assert, generate_bf.cc:104
 			const size_t nwin = g[si].seq.size() - 31;
-			for (size_t lo = 0; lo < nwin; lo += (size_t)1 << 22) chunks.push_back(Chunk{si, lo, std::min(nwin, lo + ((size_t)1 << 22))});
+			for (size_t lo = 0; lo < nwin; lo += bf_chunk) chunks.push_back(Chunk{si, lo, std::min(nwin, lo + bf_chunk)});
 		}
+		cuts.bf_chunks = chunks.size();
 		std::string err;
 		struct Bit { uint32_t at; };
 		Partitioned<Bit> part;
@@ -555,6 +585,7 @@ void build_index(const std::string &fasta, const std::string &vcf, const std::st
 			pieces.push_back(std::move(pc));
 			lo = hi;
 		}
+		cuts.vcf_pieces = pieces.size();
 		#pragma omp parallel for schedule(dynamic, 1)
 		for (long pi = 0; pi < (long)pieces.size(); pi++) {
 			Piece &pc = pieces[(size_t)pi];
@@ -583,7 +614,7 @@ void build_index(const std::string &fasta, const std::string &vcf, const std::st
 	}
 
 	// =============================== dictionaries (dictgen.c) ===============================
-	std::vector<Seq> ref = parse_fasta_dict(fa);
+	std::vector<Seq> ref = parse_fasta_dict(fa, fasta_piece_bytes, cuts.fasta_pieces);
 	pt.lap("FASTA parsed (dictionary side)");
 	{
 		FILE *f = fopen((prefix + ".chrlens").c_str(), "w");
@@ -766,12 +797,12 @@ void build_index(const std::string &fasta, const std::string &vcf, const std::st
 		}
 		pt.lap("SNP list parsed");
 		// k-mer t of a SNP covers bases [index - 31 + t, index + t], the SNP's alt base at offset 31 - t
-		const size_t SNP_CHUNK = 1 << 15;
-		const size_t n_chunks = (snps.size() + SNP_CHUNK - 1) / SNP_CHUNK;
+		const size_t n_chunks = (snps.size() + snp_chunk - 1) / snp_chunk;
+		cuts.snp_chunks = n_chunks;
 		Partitioned<SK> part;
 		partition_records<SK>(n_chunks, [&](size_t c, auto &&sink) {
-			const size_t hi = std::min(snps.size(), (c + 1) * SNP_CHUNK);
-			for (size_t i = c * SNP_CHUNK; i < hi; i++) {
+			const size_t hi = std::min(snps.size(), (c + 1) * snp_chunk);
+			for (size_t i = c * snp_chunk; i < hi; i++) {
 				const SnpRec &r = snps[i];
 				const std::string &seq = r.chrom->seq;
 				uint64_t k = 0;
@@ -786,18 +817,21 @@ void build_index(const std::string &fasta, const std::string &vcf, const std::st
 		pt.lap("SNP k-mers made and partitioned");
 		// per bucket: stable sort by k-mer (qsort is glibc's stable merge sort: ties keep VCF order), then count its records and rows
 		std::vector<uint64_t> n_rec(N_PART + 1, 0), n_aux(N_PART + 1, 0);
-		#pragma omp parallel
+		size_t buckets = 0, counting = 0;
+		#pragma omp parallel reduction(+ : buckets, counting)
 		{
 		std::vector<SK> tmp; std::vector<uint32_t> cnt;
 		#pragma omp for schedule(dynamic, 1)
 		for (long b = 0; b < (long)N_PART; b++) {
 			SK *lo = part.data + part.begin[(size_t)b], *hi = part.data + part.begin[(size_t)b + 1];
-			sort_bucket(lo, hi, tmp, cnt);
+			buckets += lo != hi;
+			counting += sort_bucket(lo, hi, tmp, cnt, counting_min) && lo != hi;
 			uint64_t rec = 0, aux = 0;
 			for (SK *p = lo; p < hi;) { SK *q = p + 1; while (q < hi && q->kmer == p->kmer) q++; rec++; aux += (q - p >= 2 && q - p <= AUX_COLS); p = q; }
 			n_rec[(size_t)b + 1] = rec; n_aux[(size_t)b + 1] = aux;
 		}
 		}
+		cuts.snp_buckets = buckets; cuts.snp_counting = counting;
 		for (size_t b = 0; b < N_PART; b++) { n_rec[b + 1] += n_rec[b]; n_aux[b + 1] += n_aux[b]; }
 		const uint64_t written = n_rec[N_PART], aux_count = n_aux[N_PART];
 		pt.lap("SNP k-mers sorted");
@@ -837,6 +871,7 @@ void build_index(const std::string &fasta, const std::string &vcf, const std::st
 			out.write_at(rows, 16 + 16 * written + 78 * n_aux[(size_t)b]);
 		}
 		out.finish();
+		cuts.write_mode = out.mode_name();
 		pt.lap("SNP dictionary written");
 		if (!opt.quiet) {
 			printf("SNP Dictionary\nTotal k-mers:        %lu\nUnambig k-mers:      %lu\nAmbig unique k-mers: %lu\nAmbig total k-mers:  %lu\n",
@@ -852,10 +887,10 @@ void build_index(const std::string &fasta, const std::string &vcf, const std::st
 		uint32_t base = 1;
 		for (size_t si = 0; si < ref.size(); si++) {
 			const size_t nwin = ref[si].seq.size() - 31;
-			const size_t step = 1 << 22;
-			for (size_t lo = 0; lo < nwin; lo += step) chunks.push_back(Chunk{si, lo, std::min(nwin, lo + step), base});
+			for (size_t lo = 0; lo < nwin; lo += kmer_chunk) chunks.push_back(Chunk{si, lo, std::min(nwin, lo + kmer_chunk), base});
 			base += (uint32_t)ref[si].seq.size();
 		}
+		cuts.kmer_chunks = chunks.size();
 		Partitioned<KP> part;
 		partition_records<KP>(chunks.size(), [&](size_t c, auto &&sink) {
 			const Chunk &ch = chunks[c];
@@ -865,18 +900,21 @@ void build_index(const std::string &fasta, const std::string &vcf, const std::st
 		pt.lap("reference k-mers made and partitioned");
 		// per bucket: stable sort by k-mer = order by (k-mer, position), a bucket being in position order already
 		std::vector<uint64_t> n_rec(N_PART + 1, 0), n_aux(N_PART + 1, 0);
-		#pragma omp parallel
+		size_t buckets = 0, counting = 0;
+		#pragma omp parallel reduction(+ : buckets, counting)
 		{
 		std::vector<KP> tmp; std::vector<uint32_t> cnt;
 		#pragma omp for schedule(dynamic, 1)
 		for (long b = 0; b < (long)N_PART; b++) {
 			KP *lo = part.data + part.begin[(size_t)b], *hi = part.data + part.begin[(size_t)b + 1];
-			sort_bucket(lo, hi, tmp, cnt);
+			buckets += lo != hi;
+			counting += sort_bucket(lo, hi, tmp, cnt, counting_min) && lo != hi;
 			uint64_t rec = 0, aux = 0;
 			for (KP *p = lo; p < hi;) { KP *q = p + 1; while (q < hi && q->kmer == p->kmer) q++; rec++; aux += (q - p >= 2 && q - p <= AUX_COLS); p = q; }
 			n_rec[(size_t)b + 1] = rec; n_aux[(size_t)b + 1] = aux;
 		}
 		}
+		cuts.ref_buckets = buckets; cuts.ref_counting = counting;
 		for (size_t b = 0; b < N_PART; b++) { n_rec[b + 1] += n_rec[b]; n_aux[b + 1] += n_aux[b]; }
 		const uint64_t written = n_rec[N_PART], aux_count = n_aux[N_PART];
 		pt.lap("reference k-mers sorted");
@@ -914,12 +952,18 @@ void build_index(const std::string &fasta, const std::string &vcf, const std::st
 			out.write_at(rows, 16 + 13 * written + 40 * n_aux[(size_t)b]);
 		}
 		out.finish();
+		if (cuts.write_mode != out.mode_name()) cuts.write_mode += std::string("/") + out.mode_name();
 		pt.lap("reference dictionary written");
 		if (!opt.quiet) {
 			printf("Ref Dictionary\nTotal k-mers:        %lu\nUnambig k-mers:      %lu\nAmbig unique k-mers: %lu\nAmbig total k-mers:  %lu\n",
 			       (unsigned long)part.n, (unsigned long)unamb, (unsigned long)amb_unique, (unsigned long)amb_total);
 		}
 	}
+	// one line: how the work was cut (x/y: of the y non-empty buckets, x were sorted with the counting pass)
+	if (pt.on)
+		fprintf(stderr, "[vargeno index] cuts: vcf_pieces=%zu fasta_pieces=%zu bf_chunks=%zu kmer_chunks=%zu snp_chunks=%zu snp_counting=%zu/%zu ref_counting=%zu/%zu dense=%d write_mode=%s threads=%d\n",
+		        cuts.vcf_pieces, cuts.fasta_pieces, cuts.bf_chunks, cuts.kmer_chunks, cuts.snp_chunks, cuts.snp_counting, cuts.snp_buckets,
+		        cuts.ref_counting, cuts.ref_buckets, (int)cuts.dense, cuts.write_mode.c_str(), nthreads);
 }
 
 }  // namespace vgh

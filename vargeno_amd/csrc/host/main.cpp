@@ -26,6 +26,19 @@
 //   VARGENO_DUMP_COUNTS=path  also write the per-site counters the caller is given (ref counts then alt counts, one byte per site, site order of the index)
 //   VARGENO_HOST_FASTQ=1  frame the FASTQ on the host (the reference's four fgets per record) instead of on the device
 //   VARGENO_NO_LITE=1     index: skip <prefix>.ref.bf.lite.bf (2.3 GB, read by nothing in geno)
+//   VARGENO_THREADS=n     index: threads (default: all)
+// Where `index` cuts its work (host/index_build.cpp; numbers clamped to >= 1, defaults unchanged when unset -- tests make them
+// tiny so that every boundary falls inside sequences, N runs and repeat copies; VARGENO_VERBOSE=1 prints one "cuts:" line
+// with what the build actually did; every chunk costs 48 KiB of bucket counters, so tiny chunks are for small inputs):
+//   VARGENO_PARSE_PIECE=n   bytes per piece of the SNP list, cut at line ends (default 4 MiB)
+//   VARGENO_FASTA_PIECE=n   bytes per piece of a FASTA record's text, dictionary side (default 16 MiB)
+//   VARGENO_BF_CHUNK=n      k-mer windows per chunk of the reference bit-vector pass (default 2^22)
+//   VARGENO_KMER_CHUNK=n    k-mer windows per chunk of the reference-dictionary pass (default 2^22)
+//   VARGENO_SNP_CHUNK=n     SNP records per chunk of the SNP-dictionary pass (default 2^15)
+//   VARGENO_COUNTING_SORT_MIN=n  records from which a dictionary bucket is sorted with the counting pass first (default 4 x 2^12)
+//   VARGENO_DENSE_BF=0|1    reference bit vectors populated up front (1) or lazily zeroed (0) (default: 1 for a FASTA > 256 MB)
+//   VARGENO_WRITE_MODE=pwrite|stream|mmap  how the dictionary files are written (default pwrite)
+//   VARGENO_STREAM_QUEUE=n  stream mode: bytes queued for the writer thread before producers wait (default 2 GiB)
 #include <errno.h>
 #include <fcntl.h>
 #include <stdio.h>
