@@ -321,18 +321,20 @@ def test_cli_read_store_that_fills_up_in_the_middle_of_the_file(ftiny_dir, tmp_p
     want, ahead, _ = run({"VARGENO_PREPACK": "0"})
     assert ahead == [] and want.count(b"\n") > 100
     # (reads.fq is just under 1 MiB: `one_chunk` is what ~4 000 reads take, a 1 MiB chunk holds a few more; a replica's range is
-    # five such chunks, or two and a half with two replicas)
+    # five such chunks, or two and a half with two replicas).  Each size twice: the pre-packer maps the file (the default), and it
+    # has the file read into chunk buffers of its own (VARGENO_PREPACK_MMAP=0: the same reader ring as the rest of a range)
     for size, expect in ((4096, "none"), (one_chunk * 13 // 10, "some"), (one_chunk * 23 // 10, "some"), (64 << 20, "all")):
-        got, ahead, err = run({"VARGENO_PREPACK_BYTES": str(size)})
-        assert got == want, (size, err)
-        assert len(ahead) == int(replicas), err
-        if expect == "none":
-            assert sum(ahead) == 0, err
-        elif expect == "all":
-            assert sum(ahead) == n_total, err
-        else:
-            assert 0 < sum(ahead) < n_total, (size, ahead, err)
-            assert "when the store was full" in err and "rest of the range" in err, err
+        for how in ({}, {"VARGENO_PREPACK_MMAP": "0"}):
+            got, ahead, err = run(dict(how, VARGENO_PREPACK_BYTES=str(size)))
+            assert got == want, (size, how, err)
+            assert len(ahead) == int(replicas), (how, err)
+            if expect == "none":
+                assert sum(ahead) == 0, (how, err)
+            elif expect == "all":
+                assert sum(ahead) == n_total, (how, err)
+            else:
+                assert 0 < sum(ahead) < n_total, (size, how, ahead, err)
+                assert "when the store was full" in err and "rest of the range" in err, (how, err)
 
 
 @pytest.mark.parametrize("replicas", ["1", "2"])

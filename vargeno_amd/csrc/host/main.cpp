@@ -25,6 +25,13 @@
 //                         from the index and this number alone (default: the whole device); VARGENO_VERBOSE=1 prints the plan
 //   VARGENO_DUMP_COUNTS=path  also write the per-site counters the caller is given (ref counts then alt counts, one byte per site, site order of the index)
 //   VARGENO_HOST_FASTQ=1  frame the FASTQ on the host (the reference's four fgets per record) instead of on the device
+//   VARGENO_PIPE_COPIERS=n  a FASTQ that is not a regular file: copier threads the one reader deals the pipe's pages to (default 4, at most 16;
+//                         0: the plain read() loop; see PipeIngest)
+//   VARGENO_VERBOSE=1     stderr: the index plan and start-up report, one "ingest, replica g:" line per route taken, the "reads:" line with
+//                         the wall time phase by phase; index: the "cuts:" line
+//   VARGENO_STATS=1       the kernel's counting build: events per read (vg_set_stats; off by default here, it carries ~50 more registers per lane)
+//   VARGENO_FORCE_RCCL=1  send the counters of a single replica through the RCCL all-reduce too (the identity)
+//   VARGENO_FQPIPE_QUIET=1  the hidden `fqpipe` command counts the reads and prints a rate instead of one line per record
 //   VARGENO_NO_LITE=1     index: skip <prefix>.ref.bf.lite.bf (2.3 GB, read by nothing in geno)
 //   VARGENO_THREADS=n     index: threads (default: all)
 // Where `index` cuts its work (host/index_build.cpp; numbers clamped to >= 1, defaults unchanged when unset -- tests make them
@@ -41,6 +48,7 @@
 //   VARGENO_STREAM_QUEUE=n  stream mode: bytes queued for the writer thread before producers wait (default 2 GiB)
 #include <errno.h>
 #include <fcntl.h>
+#include <limits.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -75,6 +83,7 @@ static void arg_check(int argc, int expected)
 	if (argc - 2 != expected) { print_help(); exit(EXIT_FAILURE); }
 }
 static int env_int(const char *name, int dflt) { const char *e = getenv(name); return e && *e ? atoi(e) : dflt; }
+static const char *env_str(const char *name) { const char *e = getenv(name); return e ? e : ""; }
 // CPUs this process may use: the hardware threads, capped by a cgroup CPU quota (cpu.max: "<quota> <period>"; this pool's GPU boxes
 // give a container 16 CPUs' worth of time on a 256-thread host)
 static int usable_cpus()
@@ -89,15 +98,107 @@ static int usable_cpus()
 	return h;
 }
 
+// Every VARGENO_* value `geno` and the hidden `fqpipe` use, read ONCE, here, before any thread exists, and handed down by const
+// reference.  The constructor clamps, and resolves the defaults that depend on the machine (`have` devices, the usable CPUs).
+struct GenoOptions {
+	const int have;                                                  // devices of this node: replica g sits on device g % have
+	int ngpu = env_int("VARGENO_GPUS", 1);                           // replicas
+	const bool share = env_int("VARGENO_SHARE_DEVICES", 0) != 0;     // more replicas than devices
+	const uint64_t batch = (uint64_t)env_int("VARGENO_BATCH", 1 << 22);
+	const bool verbose = env_int("VARGENO_VERBOSE", 0) != 0;
+	const bool host_framing = env_int("VARGENO_HOST_FASTQ", 0) != 0;
+	const int hw = usable_cpus();
+	// host threads that frame + pack (per replica); 0: the text is framed on the device, nothing is packed ahead
+	int pack_threads = env_int("VARGENO_PACK_THREADS", -1);
+	const bool pack_threads_given = pack_threads >= 0;
+	const int n_readers = std::max(1, std::min(env_int("VARGENO_READERS", std::max(8, std::min(32, hw / 8))), 64));
+	const bool prepack = env_int("VARGENO_PREPACK", 1) != 0, prepack_mmap = env_int("VARGENO_PREPACK_MMAP", 1) != 0;
+	const uint64_t prepack_want = (uint64_t)std::max(1, env_int("VARGENO_PREPACK_GB", 16)) << 30;
+	const uint64_t prepack_bytes = (uint64_t)std::max(0ll, atoll(env_str("VARGENO_PREPACK_BYTES")));    // 0: not given
+	const int chunk_mb = env_int("VARGENO_CHUNK_MB", INT_MIN);       // INT_MIN: not given -- each of its three users has a default of its own
+	const int pipe_copiers = std::min(16, std::max(0, env_int("VARGENO_PIPE_COPIERS", 4)));
+	const uint64_t budget = (uint64_t)(atof(env_str("VARGENO_MAX_DEVICE_GB")) * 1e9);                   // 0: not given
+	const int stats = env_int("VARGENO_STATS", 0);
+	const bool force_rccl = env_int("VARGENO_FORCE_RCCL", 0) != 0, orderly_exit = env_int("VARGENO_ORDERLY_EXIT", 0) != 0, fqpipe_quiet = env_int("VARGENO_FQPIPE_QUIET", 0) != 0;
+	const char *const dump_counts = getenv("VARGENO_DUMP_COUNTS");
+	explicit GenoOptions(int devices) : have(devices)
+	{
+		if (ngpu > have && !share) ngpu = have;
+		if (ngpu < 1) ngpu = 1;
+		if (pack_threads < 0) pack_threads = std::max(2, std::min(hw - 2, 96) / ngpu);
+	}
+	uint64_t chunk(int dflt_mb) const { return (uint64_t)std::max(1, chunk_mb == INT_MIN ? dflt_mb : chunk_mb) << 20; }
+	uint64_t pipe_chunk() const { return chunk(64); }                // the once-only route's ring
+	uint64_t prepack_chunk() const { return chunk(256); }            // what a pre-packer frames + packs at a time
+	uint64_t rest_chunk(bool host_packs) const { return chunk(host_packs ? 256 : 64); }      // the rest of a range
+	int range_readers() const { return std::max(2, n_readers / ngpu); }
+	int replicas_on_device(int g) const { int on = 0; for (int k = 0; k < ngpu; k++) on += k % have == g % have; return on; }
+};
+
 #define VG_CHECK(call)                                                                           \
 	do {                                                                                         \
 		int rc_ = (call);                                                                        \
 		if (rc_ != VG_OK) { fprintf(stderr, "vargeno: %s failed (%d): %s\n", #call, rc_, vg_last_error()); exit(EXIT_FAILURE); } \
 	} while (0)
 
-// Bytes [lo, hi) of the FASTQ file as a stream to one replica: reader threads pread() the range piecewise into a ring of pinned
-// chunk buffers; this thread pushes the chunks in order (vg_fastq_stream_push returns as soon as a chunk is on the device) and
-// learns what was framed only at the end.  Offsets in the result are relative to lo.
+// Bytes [lo, hi) of a descriptor, read ahead of ONE consumer that takes them chunk by chunk, in order: n_readers threads pread()
+// the range piecewise (pieces of at most 8 MiB, claimed in file order) into the caller's ring of chunk buffers.  Chunk i lives in
+// buf(i) from wait(i) to release(i); the readers run at most the ring's length ahead of the last release.
+class RangeReader {
+public:
+	RangeReader(int fd, uint64_t lo, uint64_t hi, uint64_t chunk, int n_readers, std::vector<uint8_t *> ring)
+		: fd_(fd), lo_(lo), fsize_(hi - lo), chunk_(chunk), piece_(std::min<uint64_t>(chunk, 8ull << 20)), ppc_((chunk + piece_ - 1) / piece_),
+		  n_chunks_((fsize_ + chunk - 1) / chunk), ring_(std::move(ring)), left_((size_t)n_chunks_)
+	{
+		for (uint64_t i = 0; i < n_chunks_; i++) left_[(size_t)i] = (uint32_t)((chunk_len(i) + piece_ - 1) / piece_);
+		for (int t = 0; t < n_readers; t++) readers_.emplace_back([this] { read_pieces(); });
+	}
+	~RangeReader() { stop(); }
+	uint64_t n_chunks() const { return n_chunks_; }
+	uint64_t chunk_len(uint64_t i) const { return std::min(chunk_, fsize_ - i * chunk_); }
+	uint8_t *buf(uint64_t i) const { return ring_[(size_t)(i % ring_.size())]; }
+	// chunk i is complete in buf(i) (true), or a pread failed somewhere (false)
+	bool wait(uint64_t i) { std::unique_lock<std::mutex> g(mu_); cv_.wait(g, [&] { return left_[(size_t)i] == 0 || io_error_; }); return !io_error_; }
+	// the consumer is done with chunk i: its buffer may be refilled
+	void release(uint64_t i) { { std::lock_guard<std::mutex> g(mu_); released_ = i + 1; } cv_.notify_all(); }
+	// no more chunks are wanted: the readers finish the pread they are in and are joined
+	void stop() { { std::lock_guard<std::mutex> g(mu_); quit_ = true; } cv_.notify_all(); for (auto &t : readers_) if (t.joinable()) t.join(); }
+	bool failed() { std::lock_guard<std::mutex> g(mu_); return io_error_; }
+private:
+	void read_pieces()
+	{
+		for (;;) {
+			const uint64_t p = next_piece_.fetch_add(1);
+			const uint64_t ci = p / ppc_, off = ci * chunk_ + (p % ppc_) * piece_;
+			if (ci >= n_chunks_) return;
+			if (off >= std::min(fsize_, (ci + 1) * chunk_)) continue;
+			{ std::unique_lock<std::mutex> g(mu_); cv_.wait(g, [&] { return ci < released_ + (uint64_t)ring_.size() || io_error_ || quit_; }); if (io_error_ || quit_) return; }
+			uint64_t n = std::min(piece_, std::min(fsize_, (ci + 1) * chunk_) - off), done = 0;
+			uint8_t *dst = buf(ci) + (off - ci * chunk_);
+			while (done < n) {
+				const ssize_t g = pread(fd_, dst + done, (size_t)(n - done), (off_t)(lo_ + off + done));
+				if (g <= 0) break;
+				done += (uint64_t)g;
+			}
+			std::lock_guard<std::mutex> g(mu_);
+			if (done < n) io_error_ = true;
+			left_[(size_t)ci]--;
+			cv_.notify_all();
+		}
+	}
+	const int fd_; const uint64_t lo_, fsize_, chunk_, piece_, ppc_, n_chunks_;     // ppc_: pieces per (full) chunk
+	const std::vector<uint8_t *> ring_;
+	std::mutex mu_; std::condition_variable cv_;
+	std::vector<uint32_t> left_;                                     // pieces of chunk i still to be read
+	uint64_t released_ = 0;                                          // chunks the consumer is done with (their buffers are free again)
+	std::atomic<uint64_t> next_piece_{0};
+	bool io_error_ = false, quit_ = false;
+	std::vector<std::thread> readers_;
+};
+
+// Bytes [lo, hi) of the FASTQ file as a stream to one replica: a RangeReader fills a ring of pinned chunk buffers; this thread
+// pushes the chunks in order (vg_fastq_stream_push returns as soon as a chunk is on the device) and learns what was framed only
+// at the end.  Offsets in the result are relative to lo.
 struct StreamResult {
 	uint64_t nrec = 0, used = 0, last = 0;
 	int refused = 0;
@@ -106,9 +207,6 @@ struct StreamResult {
 static StreamResult stream_range(vg_index *ix, int fd, uint64_t lo, uint64_t hi, uint64_t chunk, int n_readers, int pack_threads)
 {
 	StreamResult res;
-	const uint64_t fsize = hi - lo;                                  // the stream's length
-	const uint64_t piece = std::min<uint64_t>(chunk, 8ull << 20);
-	const uint64_t n_chunks = (fsize + chunk - 1) / chunk;
 	const int NBUF = 4;
 	std::vector<uint8_t *> ring((size_t)NBUF, nullptr);
 	std::vector<std::vector<uint8_t>> pageable((size_t)NBUF);
@@ -116,46 +214,16 @@ static StreamResult stream_range(vg_index *ix, int fd, uint64_t lo, uint64_t hi,
 		ring[(size_t)i] = (uint8_t *)vg_host_alloc_pinned((size_t)chunk);
 		if (!ring[(size_t)i]) { pageable[(size_t)i].resize((size_t)chunk); ring[(size_t)i] = pageable[(size_t)i].data(); }
 	}
-	std::mutex mu; std::condition_variable cv;
-	std::vector<uint32_t> left((size_t)n_chunks);                   // pieces of chunk i still to be read
-	for (uint64_t i = 0; i < n_chunks; i++) { const uint64_t len = std::min(chunk, fsize - i * chunk); left[(size_t)i] = (uint32_t)((len + piece - 1) / piece); }
-	uint64_t pushed = 0;                                            // chunks handed to the device (their buffers are free again)
-	std::atomic<uint64_t> next_piece{0};
-	const uint64_t ppc = (chunk + piece - 1) / piece;               // pieces per (full) chunk
-	bool io_error = false;
-	std::vector<std::thread> readers;
-	for (int t = 0; t < n_readers; t++) readers.emplace_back([&] {
-		for (;;) {
-			const uint64_t p = next_piece.fetch_add(1);
-			const uint64_t ci = p / ppc, off = ci * chunk + (p % ppc) * piece;
-			if (ci >= n_chunks) return;
-			if (off >= std::min(fsize, (ci + 1) * chunk)) continue;
-			{ std::unique_lock<std::mutex> g(mu); cv.wait(g, [&] { return ci < pushed + (uint64_t)NBUF || io_error; }); if (io_error) return; }
-			uint64_t n = std::min(piece, std::min(fsize, (ci + 1) * chunk) - off), done = 0;
-			uint8_t *dst = ring[(size_t)(ci % NBUF)] + (off - ci * chunk);
-			while (done < n) {
-				const ssize_t g = pread(fd, dst + done, (size_t)(n - done), (off_t)(lo + off + done));
-				if (g <= 0) break;
-				done += (uint64_t)g;
-			}
-			std::lock_guard<std::mutex> g(mu);
-			if (done < n) io_error = true;
-			left[(size_t)ci]--;
-			cv.notify_all();
-		}
-	});
+	RangeReader rr(fd, lo, hi, chunk, n_readers, ring);
 	int rc = pack_threads > 0 ? vg_fastq_stream_begin_packed(ix, pack_threads) : vg_fastq_stream_begin(ix);
-	for (uint64_t i = 0; i < n_chunks && rc == VG_OK; i++) {
-		{ std::unique_lock<std::mutex> g(mu); cv.wait(g, [&] { return left[(size_t)i] == 0 || io_error; }); if (io_error) break; }
-		rc = vg_fastq_stream_push(ix, ring[(size_t)(i % NBUF)], std::min(chunk, fsize - i * chunk));
-		{ std::lock_guard<std::mutex> g(mu); pushed = i + 1; }
-		cv.notify_all();
+	for (uint64_t i = 0; i < rr.n_chunks() && rc == VG_OK; i++) {
+		if (!rr.wait(i)) break;
+		rc = vg_fastq_stream_push(ix, rr.buf(i), rr.chunk_len(i));
+		rr.release(i);
 	}
-	{ std::lock_guard<std::mutex> g(mu); if (rc != VG_OK) io_error = true; pushed = n_chunks; }
-	cv.notify_all();
-	for (auto &t : readers) t.join();
+	rr.stop();                                                       // (the readers are joined: the ring is ours again)
 	if (rc != VG_OK) res.error = std::string("FASTQ stream failed: ") + vg_last_error();
-	else if (io_error) res.error = "error reading the FASTQ file";
+	else if (rr.failed()) res.error = "error reading the FASTQ file";
 	else {
 		rc = vg_fastq_stream_end(ix, &res.nrec, &res.used, &res.last, &res.refused);
 		if (rc != VG_OK) res.error = std::string("vg_fastq_stream_end failed: ") + vg_last_error();
@@ -178,8 +246,8 @@ static StreamResult stream_range(vg_index *ix, int fd, uint64_t lo, uint64_t hi,
 // would run at -- and lets the faster one finish.
 class PrePacker {
 public:
-	PrePacker(int fd, uint64_t lo, uint64_t hi, uint64_t chunk, int n_readers, int pack_threads, vg_read_store *store)
-		: fd_(fd), lo_(lo), hi_(hi), chunk_(std::min(chunk, std::max<uint64_t>(hi - lo, 1))), n_readers_(n_readers), pack_threads_(pack_threads), store_(store)
+	PrePacker(int fd, uint64_t lo, uint64_t hi, uint64_t chunk, int n_readers, int pack_threads, bool use_mmap, vg_read_store *store)
+		: fd_(fd), lo_(lo), hi_(hi), chunk_(std::min(chunk, std::max<uint64_t>(hi - lo, 1))), n_readers_(n_readers), pack_threads_(pack_threads), use_mmap_(use_mmap), store_(store)
 	{
 		clock_gettime(CLOCK_MONOTONIC, &born_);
 		th_ = std::thread([this] { run(); });
@@ -219,62 +287,34 @@ private:
 		// The text: the file mapped (the packer's threads read the page cache / tmpfs pages themselves: no copy into buffers of
 		// ours, which cost as many CPU seconds as the packing itself -- and the job shares a CPU quota with the index's start-up),
 		// the chunks after the current one asked for ahead (MADV_WILLNEED); VARGENO_PREPACK_MMAP=0 or a file that cannot be
-		// mapped: reader threads fill three chunk buffers with pread, a chunk ahead of the packer
+		// mapped: a RangeReader fills three chunk buffers with pread, a chunk ahead of the packer
 		const uint64_t page = (uint64_t)sysconf(_SC_PAGESIZE), map_lo = lo_ / page * page;
 		const uint8_t *map = nullptr;
-		if (env_int("VARGENO_PREPACK_MMAP", 1)) {
+		if (use_mmap_) {
 			void *m = mmap(nullptr, (size_t)(hi_ - map_lo), PROT_READ, MAP_SHARED, fd_, (off_t)map_lo);
 			if (m != MAP_FAILED) { map = (const uint8_t *)m; (void)madvise(m, (size_t)(hi_ - map_lo), MADV_SEQUENTIAL); }
 		}
-		const int NBUF = 3;
-		std::vector<std::vector<uint8_t>> text((size_t)NBUF);
-		if (!map) for (auto &t : text) t.resize((size_t)std::min(chunk_, fsize));
-		const uint64_t piece = std::min<uint64_t>(chunk_, 8ull << 20), ppc = (chunk_ + piece - 1) / piece;
-		std::vector<uint32_t> left((size_t)n_chunks);
-		for (uint64_t i = 0; i < n_chunks; i++) { const uint64_t len = std::min(chunk_, fsize - i * chunk_); left[(size_t)i] = map ? 0u : (uint32_t)((len + piece - 1) / piece); }
-		std::mutex rmu; std::condition_variable rcv;
-		uint64_t packed = 0;                                                     // chunks the packer is done with (their buffers are free)
+		std::vector<std::vector<uint8_t>> text(map ? 0u : 3u);
+		std::vector<uint8_t *> ring;
+		for (auto &t : text) { t.resize((size_t)std::min(chunk_, fsize)); ring.push_back(t.data()); }
+		std::unique_ptr<RangeReader> rr(map ? nullptr : new RangeReader(fd_, lo_, hi_, chunk_, n_readers_, ring));
 		uint64_t n_pushes = 0;                                                   // batches handed to the store
-		std::atomic<uint64_t> next_piece{0};
-		bool io_error = false, quit = false;
-		std::vector<std::thread> readers;
-		for (int t = 0; t < (map ? 0 : n_readers_); t++) readers.emplace_back([&] {
-			for (;;) {
-				const uint64_t p = next_piece.fetch_add(1);
-				const uint64_t ci = p / ppc, off = ci * chunk_ + (p % ppc) * piece;
-				if (ci >= n_chunks) return;
-				if (off >= std::min(fsize, (ci + 1) * chunk_)) continue;
-				{ std::unique_lock<std::mutex> g(rmu); rcv.wait(g, [&] { return ci < packed + (uint64_t)NBUF || io_error || quit; }); if (io_error || quit) return; }
-				uint64_t n = std::min(piece, std::min(fsize, (ci + 1) * chunk_) - off), done = 0;
-				uint8_t *dst = text[(size_t)(ci % NBUF)].data() + (off - ci * chunk_);
-				while (done < n) {
-					const ssize_t g = pread(fd_, dst + done, (size_t)(n - done), (off_t)(lo_ + off + done));
-					if (g <= 0) break;
-					done += (uint64_t)g;
-				}
-				std::lock_guard<std::mutex> g(rmu);
-				if (done < n) io_error = true;
-				left[(size_t)ci]--;
-				rcv.notify_all();
-			}
-		});
 		for (uint64_t i = 0; i < n_chunks && !stop_.load(); i++) {
-			{ std::unique_lock<std::mutex> g(rmu); rcv.wait(g, [&] { return left[(size_t)i] == 0 || io_error; }); if (io_error) break; }
+			if (rr && !rr->wait(i)) break;
 			const uint64_t len = std::min(chunk_, fsize - i * chunk_);
 			// (the sets alternate on the number of PUSHES: the store waits for the copies of the push before at its next push, so a
 			// chunk that framed nothing -- no push -- must not hand the set of a push still in flight to the chunk after it)
 			uint64_t *sk = stage[n_pushes & 1], *sm = sk + kcap, *so = sm + rcap;
 			uint64_t nr = 0, nc = 0, ninv = 0;
 			struct timespec a, b; clock_gettime(CLOCK_MONOTONIC, &a);
-			const uint8_t *src = map ? map + (lo_ - map_lo) + i * chunk_ : text[(size_t)(i % NBUF)].data();
+			const uint8_t *src = map ? map + (lo_ - map_lo) + i * chunk_ : rr->buf(i);
 			if (map && i + 1 < n_chunks) (void)madvise((void *)(map + ((lo_ - map_lo) + (i + 1) * chunk_) / page * page), (size_t)std::min(2 * chunk_, hi_ - lo_ - (i + 1) * chunk_), MADV_WILLNEED);
 			const int rc = vg_packer_push(pk, src, len, sk, kcap, sm, so, rcap, &nr, &nc, &ninv);
 			if (map && i > 0) (void)madvise((void *)(map + ((lo_ - map_lo) + (i - 1) * chunk_ + page - 1) / page * page), (size_t)(chunk_ / page * page - page), MADV_DONTNEED);      // (the mapping of the chunk before: its pages stay in the page cache, the page tables go)
 			clock_gettime(CLOCK_MONOTONIC, &b);
 			if (rc != VG_OK) { error = vg_last_error(); break; }
 			pack_s_.store(pack_s_.load() + (double)(b.tv_sec - a.tv_sec) + 1e-9 * (double)(b.tv_nsec - a.tv_nsec));
-			{ std::lock_guard<std::mutex> g(rmu); packed = i + 1; }
-			rcv.notify_all();
+			if (rr) rr->release(i);
 			if (nr) {
 				// (the push waits for the copies of the chunk before -- the other staging set -- and enqueues this chunk's)
 				const int prc = vg_read_store_push(store_, sk, sm, so, nr);
@@ -290,10 +330,8 @@ private:
 			(void)vg_packer_end(pk, nullptr, nullptr, nullptr, &ref);
 			if (ref) { refused_ = true; break; }
 		}
-		{ std::lock_guard<std::mutex> g(rmu); quit = true; }
-		rcv.notify_all();
-		for (auto &t : readers) t.join();
-		if (io_error && error.empty()) error = "error reading the FASTQ file";
+		if (rr) rr->stop();
+		if (rr && rr->failed() && error.empty()) error = "error reading the FASTQ file";
 		if (vg_read_store_flush(store_) != VG_OK && error.empty()) error = vg_last_error();      // the staging sets are free
 		if (map) (void)munmap((void *)map, (size_t)(hi_ - map_lo));
 		for (int k = 0; k < 2; k++) vg_host_free_pinned(stage[k]);
@@ -306,7 +344,7 @@ private:
 		finished_s_.store((double)(now.tv_sec - born_.tv_sec) + 1e-9 * (double)(now.tv_nsec - born_.tv_nsec));
 		done_.store(true);
 	}
-	const int fd_; const uint64_t lo_, hi_, chunk_; const int n_readers_, pack_threads_;
+	const int fd_; const uint64_t lo_, hi_, chunk_; const int n_readers_, pack_threads_; const bool use_mmap_;
 	vg_read_store *const store_;
 	std::thread th_;
 	std::atomic<bool> stop_{false}, done_{false};
@@ -332,8 +370,8 @@ public:
 	// sink(replica, kmers, meta, chunk_offsets, n_reads): a packed batch for a replica's read loop, once attach() has been called;
 	// blocking (the arrays are free when it returns); returns an error text or ""
 	typedef std::function<std::string(size_t, const uint64_t *, const uint64_t *, const uint64_t *, uint64_t)> Sink;
-	PipeIngest(int fd, uint64_t chunk, int pack_threads, const std::vector<vg_read_store *> &stores, Sink sink)
-		: fd_(fd), chunk_(chunk), pack_threads_(pack_threads < 1 ? 1 : pack_threads), stores_(stores), sink_(std::move(sink))
+	PipeIngest(int fd, uint64_t chunk, int pack_threads, int copiers, const std::vector<vg_read_store *> &stores, Sink sink)
+		: fd_(fd), chunk_(chunk), pack_threads_(pack_threads < 1 ? 1 : pack_threads), want_copiers_(copiers), stores_(stores), sink_(std::move(sink))
 	{
 		clock_gettime(CLOCK_MONOTONIC, &born_);
 		for (auto &b : ring_) b.data.resize((size_t)chunk_);
@@ -392,9 +430,8 @@ private:
 	};
 	void read_loop()
 	{
-		const int want = std::min(16, std::max(0, env_int("VARGENO_PIPE_COPIERS", 4)));
 		std::vector<std::unique_ptr<Copier>> cop;
-		for (int k = 0; k < want; k++) {
+		for (int k = 0; k < want_copiers_; k++) {
 			int p[2];
 			if (pipe(p) != 0) break;
 			(void)fcntl(p[1], F_SETPIPE_SZ, 1 << 20);               // (fails harmlessly when the user's pipe pages are used up: 64 KiB then)
@@ -517,7 +554,7 @@ private:
 		struct timespec now; clock_gettime(CLOCK_MONOTONIC, &now);
 		seconds = (double)(now.tv_sec - born_.tv_sec) + 1e-9 * (double)(now.tv_nsec - born_.tv_nsec);
 	}
-	const int fd_; const uint64_t chunk_; const int pack_threads_;
+	const int fd_; const uint64_t chunk_; const int pack_threads_, want_copiers_;
 	std::vector<vg_read_store *> stores_;
 	Sink sink_;
 	Buf ring_[NB];
@@ -565,294 +602,332 @@ static bool range_cuts(int fd, uint64_t fsize, int n, std::vector<uint64_t> &cut
 	return true;
 }
 
-[[maybe_unused]] static uint64_t mem_available_bytes()
+static double secs(const struct timespec &a, const struct timespec &b) { return (double)(b.tv_sec - a.tv_sec) + 1e-9 * (double)(b.tv_nsec - a.tv_nsec); }
+
+// ---- `vargeno geno`, step by step (run_geno at the end puts the steps together) ------------------------------------------------
+// The FASTQ as the command line was given it; what it is decides the ingest route
+struct FastqInput {
+	int fd = -1;                               // (-1 under VARGENO_HOST_FASTQ=1: the host reader opens the path itself)
+	uint64_t fsize = 0;
+	bool once_only = false;                    // a FIFO, /dev/stdin, <(...): one descriptor, read once, no ranges (PipeIngest)
+	bool cuts_ok = false;                      // a regular file, and cut[] holds a record-aligned range per replica
+	std::vector<uint64_t> cut;
+};
+// What an ingest route hands to the host reader that runs behind it
+struct HostHandover {
+	uint64_t total = 0;                        // reads the route framed
+	uint64_t host_from = 0;                    // file offset the host reader takes over from
+	uint64_t prime_from = UINT64_MAX;          // start of the last record the route framed (to prime the stale buffers)
+	int next_gpu = 0;                          // the replica the host reader's first batch goes to
+};
+
+// The size of replica g's read store: VARGENO_PREPACK_GB per device, never more than an eighth of the device, shared among the
+// replicas on it, at most `bound`; or VARGENO_PREPACK_BYTES exactly (tests: a store that fills up after a chunk or two)
+static uint64_t read_store_bytes(const GenoOptions &o, int g, uint64_t bound)
 {
-	uint64_t kb = 0;
-	if (FILE *f = fopen("/proc/meminfo", "r")) {
-		char line[256];
-		while (fgets(line, sizeof line, f)) if (sscanf(line, "MemAvailable: %lu kB", &kb) == 1) break;
-		fclose(f);
-	}
-	return kb * 1024;
+	const uint64_t bytes = std::min<uint64_t>(std::min<uint64_t>(o.prepack_want, vg_device_memory(g % o.have) / 8) / (uint64_t)o.replicas_on_device(g), bound);
+	return o.prepack_bytes ? o.prepack_bytes : bytes;
 }
 
-static int run_geno(const std::string &prefix, const std::string &fastq, const std::string &vcf_in, const std::string &vcf_out)
+// false: the path cannot be opened (said on stderr)
+static bool open_fastq(const std::string &fastq, const GenoOptions &o, FastqInput &in)
 {
-	const clock_t begin = clock();
-	struct timespec t0; clock_gettime(CLOCK_MONOTONIC, &t0);
-	auto secs = [](const struct timespec &a, const struct timespec &b) { return (double)(b.tv_sec - a.tv_sec) + 1e-9 * (double)(b.tv_nsec - a.tv_nsec); };
-	std::vector<vgh::ChrLen> chrlens = vgh::read_chrlens(prefix + ".chrlens");
-	int ngpu = env_int("VARGENO_GPUS", 1);
-	const int have = vg_device_count();
-	if (have <= 0) { fprintf(stderr, "vargeno: no HIP device found (this build has no CPU path)\n"); return EXIT_FAILURE; }
-	const bool share = env_int("VARGENO_SHARE_DEVICES", 0) != 0;     // more replicas than devices: replica g sits on device g % have
-	if (ngpu > have && !share) ngpu = have;
-	if (ngpu < 1) ngpu = 1;
-	const uint64_t batch = (uint64_t)env_int("VARGENO_BATCH", 1 << 22);
-	const bool verbose = env_int("VARGENO_VERBOSE", 0) != 0;
+	if (o.host_framing) return true;
+	in.fd = open(fastq.c_str(), O_RDONLY);
+	if (in.fd < 0) { fprintf(stderr, "vargeno: cannot open %s\n", fastq.c_str()); return false; }
+	struct stat sb;
+	if (fstat(in.fd, &sb) != 0) { close(in.fd); fprintf(stderr, "vargeno: cannot stat %s\n", fastq.c_str()); return false; }
+	in.fsize = (uint64_t)sb.st_size;
+	in.once_only = !S_ISREG(sb.st_mode);
+	if (in.once_only) (void)fcntl(in.fd, F_SETPIPE_SZ, 1 << 20);        // (a pipe: the largest buffer an unprivileged process may ask for; fails harmlessly on anything else)
+	else in.cuts_ok = range_cuts(in.fd, in.fsize, o.ngpu, in.cut);
+	return true;
+}
 
-	fprintf(stderr, "Initializing...\n");
-	// ---- the FASTQ file first: where the replicas' ranges are cut, and -- what needs no device -- framing + packing of their text on
-	//      host threads, started BEFORE the index is opened and running beside it
-	const bool host_framing = env_int("VARGENO_HOST_FASTQ", 0) != 0;
-	int fd = -1;
-	uint64_t fsize = 0;
-	std::vector<uint64_t> cut;
-	bool cuts_ok = false;
-	const int hw = usable_cpus();
-	// host threads that frame + pack (per replica); 0: the text is framed on the device, nothing is packed ahead
-	int pack_threads = env_int("VARGENO_PACK_THREADS", -1);
-	const bool pack_threads_given = pack_threads >= 0;
-	if (pack_threads < 0) pack_threads = std::max(2, std::min(hw - 2, 96) / ngpu);
-	const int n_readers = std::max(1, std::min(env_int("VARGENO_READERS", std::max(8, std::min(32, hw / 8))), 64));
-	std::vector<std::unique_ptr<PrePacker>> pre((size_t)ngpu);
-	std::vector<vg_read_store *> store((size_t)ngpu, nullptr);
-	std::vector<vg_index *> ix((size_t)ngpu, nullptr);
-	std::unique_ptr<PipeIngest> pipe_in;
-	bool once_only = false;
-	if (!host_framing) {
-		fd = open(fastq.c_str(), O_RDONLY);
-		if (fd < 0) { fprintf(stderr, "vargeno: cannot open %s\n", fastq.c_str()); return EXIT_FAILURE; }
-		struct stat sb;
-		if (fstat(fd, &sb) != 0) { close(fd); fprintf(stderr, "vargeno: cannot stat %s\n", fastq.c_str()); return EXIT_FAILURE; }
-		fsize = (uint64_t)sb.st_size;
-		once_only = !S_ISREG(sb.st_mode);                               // a FIFO, /dev/stdin, <(...): one descriptor, read once, no ranges (PipeIngest)
-		if (once_only) {
-			(void)fcntl(fd, F_SETPIPE_SZ, 1 << 20);                     // (a pipe: the largest buffer an unprivileged process may ask for; fails harmlessly on anything else)
-			const uint64_t want = (uint64_t)std::max(1, env_int("VARGENO_PREPACK_GB", 16)) << 30;
-			if (env_int("VARGENO_PREPACK", 1)) for (int g = 0; g < ngpu; g++) {
-				int on = 0;
-				for (int k = 0; k < ngpu; k++) on += k % have == g % have;
-				uint64_t bytes = std::min<uint64_t>(want, vg_device_memory(g % have) / 8) / (uint64_t)on;
-				if (const char *e = getenv("VARGENO_PREPACK_BYTES")) if (atoll(e) > 0) bytes = (uint64_t)atoll(e);
-				if (vg_read_store_create(g % have, bytes, &store[(size_t)g]) != VG_OK) store[(size_t)g] = nullptr;      // (no store: its batches wait for the handle)
-			}
-			pipe_in.reset(new PipeIngest(fd, (uint64_t)std::max(1, env_int("VARGENO_CHUNK_MB", 64)) << 20, std::max(1, pack_threads * ngpu), store,
-			                             [&ix](size_t g, const uint64_t *k, const uint64_t *m, const uint64_t *o, uint64_t n) -> std::string {
-				                             return vg_reads_submit_packed(ix[g], k, m, o, n) == VG_OK ? std::string() : std::string("vg_reads_submit_packed failed: ") + vg_last_error();
-			                             }));
-		}
-		cuts_ok = !once_only && range_cuts(fd, fsize, ngpu, cut);
-		if (cuts_ok && pack_threads > 0 && env_int("VARGENO_PREPACK", 1)) {
-			// a read store per replica, on its device, taken NOW (the index is planned with what is left): as large as the range's
-			// packed form (~1/5.5 of its text, and room for a chunk's worst case is not needed: a push that does not fit ends the
-			// pre-packing), at most VARGENO_PREPACK_GB per device and never more than an eighth of the device
-			const uint64_t want = (uint64_t)std::max(1, env_int("VARGENO_PREPACK_GB", 16)) << 30;
-			const uint64_t pchunk = (uint64_t)std::max(1, env_int("VARGENO_CHUNK_MB", 256)) << 20;
-			for (int g = 0; g < ngpu; g++) {
-				if (cut[(size_t)g] >= cut[(size_t)g + 1]) continue;
-				int on = 0;
-				for (int k = 0; k < ngpu; k++) on += k % have == g % have;
-				const uint64_t range = cut[(size_t)g + 1] - cut[(size_t)g];
-				uint64_t bytes = std::min<uint64_t>(std::min<uint64_t>(want, vg_device_memory(g % have) / 8) / (uint64_t)on, range / 5 + (8ull << 20));
-				if (const char *e = getenv("VARGENO_PREPACK_BYTES")) if (atoll(e) > 0) bytes = (uint64_t)atoll(e);          // (tests: a store that fills up after a chunk or two)
-				if (vg_read_store_create(g % have, bytes, &store[(size_t)g]) != VG_OK) { fprintf(stderr, "vargeno: no read store on device %d (%s): its range is framed after the index is open\n", g % have, vg_last_error()); continue; }
-				pre[(size_t)g].reset(new PrePacker(fd, cut[(size_t)g], cut[(size_t)g + 1], pchunk, std::max(2, n_readers / ngpu), pack_threads, store[(size_t)g]));
-			}
-		}
-	}
-	// the SNP list is read now, beside the index open (the VCF pass at the end of the job starts from its bytes)
-	std::string vcf_text;
-	bool vcf_ok = false;
-	std::thread vcf_reader([&] { vcf_ok = vgh::read_whole_file(vcf_in, vcf_text); });
-	struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } vcf_joiner{vcf_reader};
-	{
-		std::vector<std::thread> th;
-		std::vector<int> rcs((size_t)ngpu, 0);
-		std::vector<std::string> errs((size_t)ngpu);
-		const char *bgt = getenv("VARGENO_MAX_DEVICE_GB");
-		const uint64_t budget = bgt && *bgt ? (uint64_t)(atof(bgt) * 1e9) : 0ull;
-		// replicas that share a device (VARGENO_SHARE_DEVICES) share its memory too: without a budget of its own each of them gets
-		// an equal part -- planned for the whole device, the third or fourth one would fail where it could have run on fewer views
-		std::vector<uint64_t> budgets((size_t)ngpu, budget);
-		if (!budget && ngpu > have) for (int g = 0; g < ngpu; g++) { int on = 0; for (int k = 0; k < ngpu; k++) on += k % have == g % have; if (on > 1) budgets[(size_t)g] = vg_share_budget(g % have, on); }
-		// a read store was taken on the device before the index is planned: the plan must be told, or it plans for the device's TOTAL
-		// less 12 GiB while the store (up to 16 GiB) already holds part of that -- an index whose views fill the budget would then
-		// fail in its allocations where it could have run on fewer views.  vg_share_budget looks at what is free NOW (all budgets are
-		// computed here, before any replica opens)
-		if (!budget) for (int g = 0; g < ngpu; g++) if (!budgets[(size_t)g] && store[(size_t)g]) { int on = 0; for (int k = 0; k < ngpu; k++) on += k % have == g % have; budgets[(size_t)g] = vg_share_budget(g % have, on); }
-		for (int g = 0; g < ngpu; g++) th.emplace_back([&, g] { rcs[(size_t)g] = vg_index_open_ex(prefix.c_str(), g % have, budgets[(size_t)g], &ix[(size_t)g]); if (rcs[(size_t)g]) errs[(size_t)g] = vg_last_error(); });
-		for (auto &t : th) t.join();
-		for (int g = 0; g < ngpu; g++) if (rcs[(size_t)g]) {
-			fprintf(stderr, "vargeno: cannot load index %s on GPU %d (%d): %s\n", prefix.c_str(), g, rcs[(size_t)g], errs[(size_t)g].c_str());
-			if (pipe_in) exit(EXIT_FAILURE);                            // (its threads hold the pipe: no unwinding)
-			return EXIT_FAILURE;
-		}
-	}
-	for (auto *h : ix) VG_CHECK(vg_set_stats(h, env_int("VARGENO_STATS", 0)));
-	if (verbose) { fprintf(stderr, "index replica: %s\n", vg_index_plan(ix[0])); fprintf(stderr, "index start-up: %s\n", vg_index_open_report(ix[0])); }
+// The once-only route starts NOW, beside the index open: a read store per replica (none: its batches wait for the handle), and
+// the ingest whose sink submits to the handles in `ix` once they exist (PipeIngest::attach)
+static std::unique_ptr<PipeIngest> start_pipe_ingest(const GenoOptions &o, int fd, std::vector<vg_read_store *> &store, const std::vector<vg_index *> &ix)
+{
+	if (o.prepack) for (int g = 0; g < o.ngpu; g++)
+		if (vg_read_store_create(g % o.have, read_store_bytes(o, g, UINT64_MAX), &store[(size_t)g]) != VG_OK) store[(size_t)g] = nullptr;
+	return std::unique_ptr<PipeIngest>(new PipeIngest(fd, o.pipe_chunk(), std::max(1, o.pack_threads * o.ngpu), o.pipe_copiers, store,
+	                                                  [&ix](size_t g, const uint64_t *k, const uint64_t *m, const uint64_t *off, uint64_t n) -> std::string {
+		                                                  return vg_reads_submit_packed(ix[g], k, m, off, n) == VG_OK ? std::string() : std::string("vg_reads_submit_packed failed: ") + vg_last_error();
+	                                                  }));
+}
 
-	fprintf(stderr, "Processing...\n");
-	struct timespec t_loaded; clock_gettime(CLOCK_MONOTONIC, &t_loaded);
-	uint64_t total = 0; int next_gpu = 0;
-	// Default ingest: the file is a byte stream to the device(s).  One replica takes all of it; several take one contiguous range
-	// each, cut at record starts, all at once.  A range's text is framed + packed by host threads (what was packed while the index
-	// was being opened is submitted first) or copied up as it is and framed on the device -- whichever runs faster HERE: the
-	// pre-packer has measured its rate, vg_link_rate() the link's.  Whatever the stream refuses (from the first chunk with a line
-	// beyond fgets' 1023 characters on) and the (possibly truncated) tail of the file go through the host reader below, which
-	// reproduces the reference's four-fgets framing exactly, stale buffers included; with several replicas a refusal anywhere but
-	// in the last range means the ranges after it were framed out of step with the reference, so everything is reset and framed
-	// on the host.
-	uint64_t host_from = 0;                    // file offset the host reader takes over from
-	uint64_t prime_from = UINT64_MAX;          // start of the last record the device framed (to prime the stale buffers)
-	if (pipe_in) {
-		// a stream that is read once: what went into the read stores while the index opened first, then the packer's batches
-		// straight into the read loops until the stream ends (or is refused)
-		for (int g = 0; g < ngpu; g++) if (store[(size_t)g]) { VG_CHECK(vg_read_store_flush(store[(size_t)g])); }
-		pipe_in->attach();
-		pipe_in->finish();
-		for (int g = 0; g < ngpu; g++) if (store[(size_t)g] && vg_read_store_reads(store[(size_t)g])) VG_CHECK(vg_reads_submit_store(ix[(size_t)g], store[(size_t)g]));
-		if (!pipe_in->error.empty()) { fprintf(stderr, "vargeno: %s\n", pipe_in->error.c_str()); exit(EXIT_FAILURE); }
-		total += pipe_in->records;
-		if (verbose) fprintf(stderr, "ingest, replica 0: the FASTQ is not a regular file: one descriptor read once, %lu reads framed + packed by %d host threads (%lu into the read stores while the index opened, %lu straight into the read loop), "
-		                             "%.2f GB of text in %.2f s (%.2f GB/s), dealt to %d copier threads%s\n", (unsigned long)pipe_in->records, std::max(1, pack_threads * ngpu), (unsigned long)pipe_in->to_store, (unsigned long)pipe_in->direct,
-		                     (double)pipe_in->bytes_read / 1e9, pipe_in->seconds, pipe_in->seconds > 0 ? (double)pipe_in->bytes_read / 1e9 / pipe_in->seconds : 0.0, pipe_in->copiers, pipe_in->refused ? "; the stream framing refused a chunk: the host reader takes the rest" : "");
-	} else if (!host_framing) {
-		if (!cuts_ok) {
-			host_from = 0;                                              // no record start found where one should be: the host reader takes the file
-			fprintf(stderr, "vargeno: no FASTQ record start within 1 MiB of a range boundary: the whole file is framed on the host (slower)\n");
-		} else {
-			const double link = pack_threads > 0 ? vg_link_rate(0) : 0.0;          // bytes/s of text the device-side framing can be fed at
-			std::vector<StreamResult> res((size_t)ngpu);
-			std::vector<std::string> route((size_t)ngpu);
-			std::vector<std::thread> th;
-			for (int g = 0; g < ngpu; g++)
-				if (cut[(size_t)g] < cut[(size_t)g + 1] || g == 0)
-					th.emplace_back([&, g] {
-						StreamResult &r = res[(size_t)g];
-						uint64_t done_to = 0;                                  // bytes of the range framed so far
-						// the rest of a range (what the pre-packer did not take -- it was stopped, its store filled up, or it never ran): host
-						// packing or device framing, whichever is faster HERE.  With a pre-packer its measured rate decides, whether it is
-						// still running or done (a 30x file overruns a 16 GB store: the larger part of the file is "the rest"); without one
-						// (VARGENO_PREPACK=0, no store) the number of CPUs does, as in r04, unless VARGENO_PACK_THREADS says what is wanted
-						bool pack_rest = pack_threads > 0 && (pack_threads_given || hw >= 32);
-						if (pre[(size_t)g]) {
-							PrePacker &pp = *pre[(size_t)g];
-							pack_rest = pack_threads > 0;
-							// it keeps the rest of the range unless the device-side framing would finish it at least a second earlier
-							// (changing horses costs about that much: a new stream, its readers starting cold)
-							{
-								const double rp = pp.text_bytes_per_s();
-								const double left = (double)(cut[(size_t)g + 1] - cut[(size_t)g]) - (double)pp.text_bytes_done();
-								if (rp > 0 && link > 0 && left > 0) pack_rest = rp >= link || left * (1.0 / rp - 1.0 / link) < 1.0;
-								if (!pp.done() && !pack_rest) pp.stop();
-							}
-							pp.join();
-							if (!pp.error.empty()) r.error = pp.error;
-							const uint64_t submitted = vg_read_store_reads(store[(size_t)g]);
-							if (r.error.empty() && vg_reads_submit_store(ix[(size_t)g], store[(size_t)g]) != VG_OK) r.error = std::string("vg_reads_submit_store failed: ") + vg_last_error();
-							r.nrec = pp.records(); r.used = pp.consumed(); r.last = pp.last_record_start(); r.refused = pp.refused() ? 1 : 0;
-							done_to = pp.consumed();
-							char line[320];
-							snprintf(line, sizeof line, "%lu reads packed ahead of / beside the index into %.1f GB of device memory (%.1f GB/s of text on %d threads, done %.2f s after the command line started them%s; link %.1f GB/s)",
-							         (unsigned long)submitted, (double)vg_read_store_bytes_used(store[(size_t)g]) / 1e9, pp.text_bytes_per_s() / 1e9, pack_threads, pp.finished_after_s(), pp.store_full() ? ", when the store was full" : "", link / 1e9);
-							route[(size_t)g] = line;
-						}
-						const uint64_t lo = cut[(size_t)g] + done_to, hi = cut[(size_t)g + 1];
-						if (r.error.empty() && !r.refused && lo < hi) {
-							const uint64_t chunk = (uint64_t)std::max(1, env_int("VARGENO_CHUNK_MB", pack_rest ? 256 : 64)) << 20;
-							const StreamResult r2 = stream_range(ix[(size_t)g], fd, lo, hi, chunk, std::max(2, n_readers / ngpu), pack_rest ? pack_threads : 0);
-							route[(size_t)g] += pack_rest ? "; rest of the range: framed + packed by host threads" : "; rest of the range: framed on the device";
-							if (!r2.error.empty()) r.error = r2.error;
-							if (r2.nrec) r.last = done_to + r2.last;
-							r.nrec += r2.nrec; r.used = done_to + r2.used; r.refused = r2.refused;
-						}
-					});
-			for (auto &t : th) t.join();
-			for (int g = 0; g < ngpu; g++) if (!res[(size_t)g].error.empty()) { fprintf(stderr, "vargeno: %s\n", res[(size_t)g].error.c_str()); exit(EXIT_FAILURE); }
-			if (verbose) for (int g = 0; g < ngpu; g++) if (!route[(size_t)g].empty()) fprintf(stderr, "ingest, replica %d: %s\n", g, route[(size_t)g].c_str());
-			int last_range = 0;                                         // the last range that holds bytes
-			for (int g = 0; g < ngpu; g++) if (cut[(size_t)g] < cut[(size_t)g + 1]) last_range = g;
-			bool in_step = true;
-			for (int g = 0; g < last_range; g++) if (res[(size_t)g].used != cut[(size_t)g + 1] - cut[(size_t)g]) in_step = false;
-			if (in_step) {
-				for (int g = 0; g <= last_range; g++) total += res[(size_t)g].nrec;
-				for (int g = last_range; g >= 0; g--) if (res[(size_t)g].nrec) { prime_from = cut[(size_t)g] + res[(size_t)g].last; break; }
-				host_from = cut[(size_t)last_range] + res[(size_t)last_range].used;    // the incomplete tail, or everything from a refused chunk on
-				next_gpu = last_range;
-			} else {
-				// (the file has been streamed once already: a 2x or larger slowdown that must not pass silently)
-				fprintf(stderr, "vargeno: a FASTQ range before the last one was refused by the stream framing (a line beyond 1023 characters?): "
-				                "counters reset, the whole file is framed on the host\n");
-				for (auto *h : ix) VG_CHECK(vg_counts_reset(h));
-				host_from = 0;
-			}
-		}
-		pre.clear();
-		close(fd);
+// The ranged route packs ahead of the index: a read store per replica, on its device, taken NOW (the index is planned with what
+// is left): as large as the range's packed form (~1/5.5 of its text, and room for a chunk's worst case is not needed: a push that
+// does not fit ends the pre-packing), at most VARGENO_PREPACK_GB per device and never more than an eighth of the device
+static std::vector<std::unique_ptr<PrePacker>> start_prepackers(const GenoOptions &o, const FastqInput &in, std::vector<vg_read_store *> &store)
+{
+	std::vector<std::unique_ptr<PrePacker>> pre((size_t)o.ngpu);
+	if (!in.cuts_ok || o.pack_threads <= 0 || !o.prepack) return pre;
+	for (int g = 0; g < o.ngpu; g++) {
+		const uint64_t lo = in.cut[(size_t)g], hi = in.cut[(size_t)g + 1];
+		if (lo >= hi) continue;
+		if (vg_read_store_create(g % o.have, read_store_bytes(o, g, (hi - lo) / 5 + (8ull << 20)), &store[(size_t)g]) != VG_OK) { fprintf(stderr, "vargeno: no read store on device %d (%s): its range is framed after the index is open\n", g % o.have, vg_last_error()); continue; }
+		pre[(size_t)g].reset(new PrePacker(in.fd, lo, hi, o.prepack_chunk(), o.range_readers(), o.pack_threads, o.prepack_mmap, store[(size_t)g]));
 	}
-	{
-		// the host reader: the file from host_from on -- or, for a stream that is read once, the bytes still in memory and then the
-		// descriptor (never a second open: a FIFO has lost its writer by then)
-		if (pipe_in) { host_from = pipe_in->consumed; if (pipe_in->records) prime_from = pipe_in->last; }
-		std::unique_ptr<vgh::FastqReader> rdp(pipe_in ? new vgh::FastqReader(fd, pipe_in->span_base, pipe_in->spans) : new vgh::FastqReader(fastq));
-		vgh::FastqReader &rd = *rdp;
-		vgh::ReadBatch rb;
-		if (!host_framing && prime_from != UINT64_MAX) {   // re-read the last framed record: it only fills the line buffers
-			rd.seek(prime_from);
-			rb.clear();
-			(void)rd.next(rb, 1);
-		}
-		if (!host_framing) rd.seek(host_from);
-		for (;;) {
-			rb.clear();
-			const uint64_t n = rd.next(rb, batch);
-			if (!n) break;
-			total += n;
-			VG_CHECK(vg_reads_submit(ix[(size_t)next_gpu], rb.bases.data(), rb.quals.data(), rb.offsets.data(), n));
-			next_gpu = (next_gpu + 1) % ngpu;
-		}
+	return pre;
+}
+
+// All replicas open their index at once, each under a budget computed HERE, before the first open.  false: said on stderr
+static bool open_indexes(const std::string &prefix, const GenoOptions &o, const std::vector<vg_read_store *> &store, std::vector<vg_index *> &ix, bool pipe_running)
+{
+	const int ngpu = o.ngpu, have = o.have;
+	std::vector<std::thread> th;
+	std::vector<int> rcs((size_t)ngpu, 0);
+	std::vector<std::string> errs((size_t)ngpu);
+	// replicas that share a device (VARGENO_SHARE_DEVICES) share its memory too: without a budget of its own each of them gets
+	// an equal part -- planned for the whole device, the third or fourth one would fail where it could have run on fewer views
+	std::vector<uint64_t> budgets((size_t)ngpu, o.budget);
+	if (!o.budget && ngpu > have) for (int g = 0; g < ngpu; g++) { const int on = o.replicas_on_device(g); if (on > 1) budgets[(size_t)g] = vg_share_budget(g % have, on); }
+	// a read store was taken on the device before the index is planned: the plan must be told, or it plans for the device's TOTAL
+	// less 12 GiB while the store (up to 16 GiB) already holds part of that -- an index whose views fill the budget would then
+	// fail in its allocations where it could have run on fewer views.  vg_share_budget looks at what is free NOW (all budgets are
+	// computed here, before any replica opens)
+	if (!o.budget) for (int g = 0; g < ngpu; g++) if (!budgets[(size_t)g] && store[(size_t)g]) budgets[(size_t)g] = vg_share_budget(g % have, o.replicas_on_device(g));
+	for (int g = 0; g < ngpu; g++) th.emplace_back([&, g] { rcs[(size_t)g] = vg_index_open_ex(prefix.c_str(), g % have, budgets[(size_t)g], &ix[(size_t)g]); if (rcs[(size_t)g]) errs[(size_t)g] = vg_last_error(); });
+	for (auto &t : th) t.join();
+	for (int g = 0; g < ngpu; g++) if (rcs[(size_t)g]) {
+		fprintf(stderr, "vargeno: cannot load index %s on GPU %d (%d): %s\n", prefix.c_str(), g, rcs[(size_t)g], errs[(size_t)g].c_str());
+		if (pipe_running) exit(EXIT_FAILURE);                           // (its threads hold the pipe: no unwinding)
+		return false;
 	}
-	for (auto *h : ix) VG_CHECK(vg_sync(h));
-	struct timespec t_reads; clock_gettime(CLOCK_MONOTONIC, &t_reads);
+	return true;
+}
+
+// Replica g's range [cut[g], cut[g + 1]) on the ranged route: what its pre-packer (if it has one) put into the read store is
+// submitted first, then the rest of the range is streamed.  `route` says in words what was done (the verbose "ingest" line).
+static StreamResult ingest_range(const GenoOptions &o, const FastqInput &in, int g, double link, vg_index *ix, vg_read_store *store, PrePacker *pre, std::string &route)
+{
+	StreamResult r;
+	const uint64_t range_lo = in.cut[(size_t)g], range_hi = in.cut[(size_t)g + 1];
+	uint64_t done_to = 0;                                  // bytes of the range framed so far
+	// the rest of a range (what the pre-packer did not take -- it was stopped, its store filled up, or it never ran): host
+	// packing or device framing, whichever is faster HERE.  With a pre-packer its measured rate decides, whether it is
+	// still running or done (a 30x file overruns a 16 GB store: the larger part of the file is "the rest"); without one
+	// (VARGENO_PREPACK=0, no store) the number of CPUs does, as in r04, unless VARGENO_PACK_THREADS says what is wanted
+	bool pack_rest = o.pack_threads > 0 && (o.pack_threads_given || o.hw >= 32);
+	if (pre) {
+		PrePacker &pp = *pre;
+		pack_rest = o.pack_threads > 0;
+		// it keeps the rest of the range unless the device-side framing would finish it at least a second earlier
+		// (changing horses costs about that much: a new stream, its readers starting cold)
+		const double rp = pp.text_bytes_per_s();
+		const double left = (double)(range_hi - range_lo) - (double)pp.text_bytes_done();
+		if (rp > 0 && link > 0 && left > 0) pack_rest = rp >= link || left * (1.0 / rp - 1.0 / link) < 1.0;
+		if (!pp.done() && !pack_rest) pp.stop();
+		pp.join();
+		if (!pp.error.empty()) r.error = pp.error;
+		const uint64_t submitted = vg_read_store_reads(store);
+		if (r.error.empty() && vg_reads_submit_store(ix, store) != VG_OK) r.error = std::string("vg_reads_submit_store failed: ") + vg_last_error();
+		r.nrec = pp.records(); r.used = pp.consumed(); r.last = pp.last_record_start(); r.refused = pp.refused() ? 1 : 0;
+		done_to = pp.consumed();
+		char line[320];
+		snprintf(line, sizeof line, "%lu reads packed ahead of / beside the index into %.1f GB of device memory (%.1f GB/s of text on %d threads, done %.2f s after the command line started them%s; link %.1f GB/s)",
+		         (unsigned long)submitted, (double)vg_read_store_bytes_used(store) / 1e9, pp.text_bytes_per_s() / 1e9, o.pack_threads, pp.finished_after_s(), pp.store_full() ? ", when the store was full" : "", link / 1e9);
+		route = line;
+	}
+	const uint64_t lo = range_lo + done_to, hi = range_hi;
+	if (r.error.empty() && !r.refused && lo < hi) {
+		const StreamResult r2 = stream_range(ix, in.fd, lo, hi, o.rest_chunk(pack_rest), o.range_readers(), pack_rest ? o.pack_threads : 0);
+		route += pack_rest ? "; rest of the range: framed + packed by host threads" : "; rest of the range: framed on the device";
+		if (!r2.error.empty()) r.error = r2.error;
+		if (r2.nrec) r.last = done_to + r2.last;
+		r.nrec += r2.nrec; r.used = done_to + r2.used; r.refused = r2.refused;
+	}
+	return r;
+}
+
+// Default ingest: the file is a byte stream to the device(s).  One replica takes all of it; several take one contiguous range
+// each, cut at record starts, all at once.  A range's text is framed + packed by host threads (what was packed while the index
+// was being opened is submitted first) or copied up as it is and framed on the device -- whichever runs faster HERE: the
+// pre-packer has measured its rate, vg_link_rate() the link's.  Whatever the stream refuses (from the first chunk with a line
+// beyond fgets' 1023 characters on) and the (possibly truncated) tail of the file go through the host reader, which
+// reproduces the reference's four-fgets framing exactly, stale buffers included; with several replicas a refusal anywhere but
+// in the last range means the ranges after it were framed out of step with the reference, so everything is reset and framed
+// on the host.
+static HostHandover ranged_route(const GenoOptions &o, const FastqInput &in, const std::vector<vg_index *> &ix, const std::vector<vg_read_store *> &store, const std::vector<std::unique_ptr<PrePacker>> &pre)
+{
+	HostHandover hand;
+	if (!in.cuts_ok) {                                               // no record start found where one should be: the host reader takes the file
+		fprintf(stderr, "vargeno: no FASTQ record start within 1 MiB of a range boundary: the whole file is framed on the host (slower)\n");
+		return hand;
+	}
+	const int ngpu = o.ngpu;
+	const std::vector<uint64_t> &cut = in.cut;
+	const double link = o.pack_threads > 0 ? vg_link_rate(0) : 0.0;    // bytes/s of text the device-side framing can be fed at
+	std::vector<StreamResult> res((size_t)ngpu);
+	std::vector<std::string> route((size_t)ngpu);
+	std::vector<std::thread> th;
+	for (int g = 0; g < ngpu; g++)
+		if (cut[(size_t)g] < cut[(size_t)g + 1] || g == 0)
+			th.emplace_back([&, g] { res[(size_t)g] = ingest_range(o, in, g, link, ix[(size_t)g], store[(size_t)g], pre[(size_t)g].get(), route[(size_t)g]); });
+	for (auto &t : th) t.join();
+	for (int g = 0; g < ngpu; g++) if (!res[(size_t)g].error.empty()) { fprintf(stderr, "vargeno: %s\n", res[(size_t)g].error.c_str()); exit(EXIT_FAILURE); }
+	if (o.verbose) for (int g = 0; g < ngpu; g++) if (!route[(size_t)g].empty()) fprintf(stderr, "ingest, replica %d: %s\n", g, route[(size_t)g].c_str());
+	int last_range = 0;                                              // the last range that holds bytes
+	for (int g = 0; g < ngpu; g++) if (cut[(size_t)g] < cut[(size_t)g + 1]) last_range = g;
+	bool in_step = true;
+	for (int g = 0; g < last_range; g++) if (res[(size_t)g].used != cut[(size_t)g + 1] - cut[(size_t)g]) in_step = false;
+	if (in_step) {
+		for (int g = 0; g <= last_range; g++) hand.total += res[(size_t)g].nrec;
+		for (int g = last_range; g >= 0; g--) if (res[(size_t)g].nrec) { hand.prime_from = cut[(size_t)g] + res[(size_t)g].last; break; }
+		hand.host_from = cut[(size_t)last_range] + res[(size_t)last_range].used;    // the incomplete tail, or everything from a refused chunk on
+		hand.next_gpu = last_range;
+	} else {
+		// (the file has been streamed once already: a 2x or larger slowdown that must not pass silently)
+		fprintf(stderr, "vargeno: a FASTQ range before the last one was refused by the stream framing (a line beyond 1023 characters?): "
+		                "counters reset, the whole file is framed on the host\n");
+		for (auto *h : ix) VG_CHECK(vg_counts_reset(h));
+	}
+	return hand;
+}
+
+// A stream that is read once: what went into the read stores while the index opened first, then the packer's batches
+// straight into the read loops until the stream ends (or is refused)
+static HostHandover once_only_route(const GenoOptions &o, PipeIngest &pipe_in, const std::vector<vg_index *> &ix, const std::vector<vg_read_store *> &store)
+{
+	const int ngpu = o.ngpu;
+	for (int g = 0; g < ngpu; g++) if (store[(size_t)g]) { VG_CHECK(vg_read_store_flush(store[(size_t)g])); }
+	pipe_in.attach();
+	pipe_in.finish();
+	for (int g = 0; g < ngpu; g++) if (store[(size_t)g] && vg_read_store_reads(store[(size_t)g])) VG_CHECK(vg_reads_submit_store(ix[(size_t)g], store[(size_t)g]));
+	if (!pipe_in.error.empty()) { fprintf(stderr, "vargeno: %s\n", pipe_in.error.c_str()); exit(EXIT_FAILURE); }
+	if (o.verbose) fprintf(stderr, "ingest, replica 0: the FASTQ is not a regular file: one descriptor read once, %lu reads framed + packed by %d host threads (%lu into the read stores while the index opened, %lu straight into the read loop), "
+	                               "%.2f GB of text in %.2f s (%.2f GB/s), dealt to %d copier threads%s\n", (unsigned long)pipe_in.records, std::max(1, o.pack_threads * ngpu), (unsigned long)pipe_in.to_store, (unsigned long)pipe_in.direct,
+	                       (double)pipe_in.bytes_read / 1e9, pipe_in.seconds, pipe_in.seconds > 0 ? (double)pipe_in.bytes_read / 1e9 / pipe_in.seconds : 0.0, pipe_in.copiers, pipe_in.refused ? "; the stream framing refused a chunk: the host reader takes the rest" : "");
+	return HostHandover{pipe_in.records, pipe_in.consumed, pipe_in.records ? pipe_in.last : UINT64_MAX, 0};
+}
+
+// The host reader: the file from hand.host_from on -- or, for a stream that is read once, the bytes still in memory and then the
+// descriptor (never a second open: a FIFO has lost its writer by then).  Returns the job's reads: the route's and its own.
+static uint64_t host_reader_tail(const GenoOptions &o, const std::string &fastq, int fd, const PipeIngest *pipe_in, const std::vector<vg_index *> &ix, const HostHandover &hand)
+{
+	uint64_t total = hand.total;
+	int next_gpu = hand.next_gpu;
+	std::unique_ptr<vgh::FastqReader> rdp(pipe_in ? new vgh::FastqReader(fd, pipe_in->span_base, pipe_in->spans) : new vgh::FastqReader(fastq));
+	vgh::FastqReader &rd = *rdp;
+	vgh::ReadBatch rb;
+	if (!o.host_framing && hand.prime_from != UINT64_MAX) {   // re-read the last framed record: it only fills the line buffers
+		rd.seek(hand.prime_from);
+		rb.clear();
+		(void)rd.next(rb, 1);
+	}
+	if (!o.host_framing) rd.seek(hand.host_from);
+	for (;;) {
+		rb.clear();
+		const uint64_t n = rd.next(rb, o.batch);
+		if (!n) break;
+		total += n;
+		VG_CHECK(vg_reads_submit(ix[(size_t)next_gpu], rb.bases.data(), rb.quals.data(), rb.offsets.data(), n));
+		next_gpu = (next_gpu + 1) % o.ngpu;
+	}
+	return total;
+}
+
+// The per-site counters of the whole job, as the caller wants them.  false: said on stderr
+static bool fetch_counts(const GenoOptions &o, std::vector<vg_index *> &ix, vgh::SiteCounts &sc)
+{
 	{
 		// util.c:103: the reference aborts on a read with a character other than ACGTN (and writes no VCF); the library counts
 		// such reads whether or not event counting is on
 		vg_stats st;
 		uint64_t invalid = 0;
 		for (auto *h : ix) { VG_CHECK(vg_stats_get(h, &st)); invalid += st.reads_invalid; }
-		if (invalid) { fprintf(stderr, "vargeno: %lu reads contain a character other than ACGTN (the reference aborts on these)\n", (unsigned long)invalid); return EXIT_FAILURE; }
+		if (invalid) { fprintf(stderr, "vargeno: %lu reads contain a character other than ACGTN (the reference aborts on these)\n", (unsigned long)invalid); return false; }
 	}
 	// one process, n devices: one RCCL all-reduce of the per-site counters over xGMI (VARGENO_FORCE_RCCL=1 also sends a
 	// single device through it, which is the identity)
-	if (ngpu > 1 || env_int("VARGENO_FORCE_RCCL", 0)) VG_CHECK(vg_counts_allreduce_devices(ix.data(), ngpu));
-	vgh::SiteCounts sc;
+	if (o.ngpu > 1 || o.force_rccl) VG_CHECK(vg_counts_allreduce_devices(ix.data(), o.ngpu));
 	const uint64_t ns = vg_num_sites(ix[0]);
 	sc.pos.resize(ns); sc.ref_freq.resize(ns); sc.alt_freq.resize(ns); sc.ref_cnt.resize(ns); sc.alt_cnt.resize(ns);
 	VG_CHECK(vg_sites_fetch(ix[0], sc.pos.data(), nullptr, nullptr, sc.ref_freq.data(), sc.alt_freq.data()));
 	VG_CHECK(vg_counts_fetch(ix[0], sc.ref_cnt.data(), sc.alt_cnt.data()));
-	if (const char *dump = getenv("VARGENO_DUMP_COUNTS")) {              // the saturated counters as the caller gets them: ref counts, then alt counts, one byte per site
+	if (const char *dump = o.dump_counts) {                              // the saturated counters as the caller gets them: ref counts, then alt counts, one byte per site
 		FILE *f = fopen(dump, "wb");
-		if (!f || fwrite(sc.ref_cnt.data(), 1, ns, f) != ns || fwrite(sc.alt_cnt.data(), 1, ns, f) != ns) { fprintf(stderr, "vargeno: cannot write %s\n", dump); return EXIT_FAILURE; }
+		if (!f || fwrite(sc.ref_cnt.data(), 1, ns, f) != ns || fwrite(sc.alt_cnt.data(), 1, ns, f) != ns) { fprintf(stderr, "vargeno: cannot write %s\n", dump); return false; }
 		fclose(f);
 	}
+	return true;
+}
+
+// VARGENO_VERBOSE=1: where the wall time went (t[0] the start, then: index loaded, reads counted, VCF written)
+static void verbose_report(uint64_t total, int ngpu, const struct timespec t[4])
+{
+	struct timespec t1; clock_gettime(CLOCK_MONOTONIC, &t1);
+	fprintf(stderr, "reads: %lu  gpus: %d  wall: %.3f s = index load %.3f + FASTQ->counters %.3f (%.2f M reads/s) + call/VCF %.3f + close %.3f\n", (unsigned long)total, ngpu,
+	        secs(t[0], t1), secs(t[0], t[1]), secs(t[1], t[2]), (double)total / secs(t[1], t[2]) / 1e6, secs(t[2], t[3]), secs(t[3], t1));
+	// how long the process has existed (its start time in /proc/self/stat, 10 ms ticks, against the boot clock): what the loader
+	// and the HIP runtime's static start-up took before main() is that minus the wall time above
+	if (FILE *f = fopen("/proc/self/stat", "r")) {
+		char buf[2048]; const size_t n = fread(buf, 1, sizeof buf - 1, f); buf[n] = 0; fclose(f);
+		const char *q = strrchr(buf, ')');
+		unsigned long long start = 0; int field = 2;
+		for (q = q ? q + 1 : buf; q && *q && field < 22; ) { q = strchr(q + 1, ' '); field++; if (field == 21 && q) start = strtoull(q + 1, nullptr, 10); }
+		struct timespec bt; clock_gettime(CLOCK_BOOTTIME, &bt);
+		if (start) fprintf(stderr, "process: alive for %.2f s at this point\n", (double)bt.tv_sec + 1e-9 * (double)bt.tv_nsec - (double)start / (double)sysconf(_SC_CLK_TCK));
+	}
+}
+
+static int run_geno(const std::string &prefix, const std::string &fastq, const std::string &vcf_in, const std::string &vcf_out)
+{
+	const clock_t begin = clock();
+	struct timespec t[4]; clock_gettime(CLOCK_MONOTONIC, &t[0]);       // the start; then: index loaded, reads counted, VCF written
+	std::vector<vgh::ChrLen> chrlens = vgh::read_chrlens(prefix + ".chrlens");
+	const int have = vg_device_count();
+	if (have <= 0) { fprintf(stderr, "vargeno: no HIP device found (this build has no CPU path)\n"); return EXIT_FAILURE; }
+	const GenoOptions o(have);
+
+	fprintf(stderr, "Initializing...\n");
+	// ---- the FASTQ file first: where the replicas' ranges are cut, and -- what needs no device -- framing + packing of their text on
+	//      host threads, started BEFORE the index is opened and running beside it
+	FastqInput in;
+	if (!open_fastq(fastq, o, in)) return EXIT_FAILURE;
+	std::vector<vg_read_store *> store((size_t)o.ngpu, nullptr);
+	std::vector<vg_index *> ix((size_t)o.ngpu, nullptr);
+	std::unique_ptr<PipeIngest> pipe_in;
+	std::vector<std::unique_ptr<PrePacker>> pre;
+	if (in.once_only) pipe_in = start_pipe_ingest(o, in.fd, store, ix);
+	else pre = start_prepackers(o, in, store);
+	// the SNP list is read now, beside the index open (the VCF pass at the end of the job starts from its bytes)
+	std::string vcf_text;
+	bool vcf_ok = false;
+	std::thread vcf_reader([&] { vcf_ok = vgh::read_whole_file(vcf_in, vcf_text); });
+	struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } vcf_joiner{vcf_reader};
+	if (!open_indexes(prefix, o, store, ix, pipe_in != nullptr)) return EXIT_FAILURE;
+	for (auto *h : ix) VG_CHECK(vg_set_stats(h, o.stats));
+	if (o.verbose) { fprintf(stderr, "index replica: %s\n", vg_index_plan(ix[0])); fprintf(stderr, "index start-up: %s\n", vg_index_open_report(ix[0])); }
+
+	fprintf(stderr, "Processing...\n");
+	clock_gettime(CLOCK_MONOTONIC, &t[1]);
+	// ---- one ingest route (ranged_route has the long story), then the host reader for whatever the route left
+	HostHandover hand;
+	if (pipe_in) hand = once_only_route(o, *pipe_in, ix, store);
+	else if (!o.host_framing) {
+		hand = ranged_route(o, in, ix, store, pre);
+		pre.clear();
+		close(in.fd);
+	}
+	const uint64_t total = host_reader_tail(o, fastq, in.fd, pipe_in.get(), ix, hand);
+	for (auto *h : ix) VG_CHECK(vg_sync(h));
+	clock_gettime(CLOCK_MONOTONIC, &t[2]);
+	vgh::SiteCounts sc;
+	if (!fetch_counts(o, ix, sc)) return EXIT_FAILURE;
 	if (vcf_reader.joinable()) vcf_reader.join();
 	vgh::write_genotyped_vcf(sc, chrlens, vcf_in, vcf_out, vcf_ok ? &vcf_text : nullptr);
-	struct timespec t_vcf; clock_gettime(CLOCK_MONOTONIC, &t_vcf);
+	clock_gettime(CLOCK_MONOTONIC, &t[3]);
 	// The output is complete and closed.  What is left is giving back ~240 GB of device memory and the page-locked buffers, which the
 	// operating system does for a process that ends anyway: an orderly vg_index_close + runtime shut-down took 0.7 + 0.9 s of an
 	// 7 s job at hg38 scale (profiles/job_tail_r05.txt), so the command line ends here unless VARGENO_ORDERLY_EXIT=1 asks for the
 	// full tear-down (tests that look for leaks, sanitizer runs).
-	const bool orderly = env_int("VARGENO_ORDERLY_EXIT", 0) != 0;
-	if (orderly) { for (auto *h : ix) vg_index_close(h); for (auto *rs : store) vg_read_store_destroy(rs); }
+	if (o.orderly_exit) { for (auto *h : ix) vg_index_close(h); for (auto *rs : store) vg_read_store_destroy(rs); }
 	const double cpu = (double)(clock() - begin) / CLOCKS_PER_SEC;
 	printf("Time: %f sec\n", cpu);                                       // qv.cc:1749-1751 prints CPU seconds
-	if (verbose) {
-		struct timespec t1; clock_gettime(CLOCK_MONOTONIC, &t1);
-		fprintf(stderr, "reads: %lu  gpus: %d  wall: %.3f s = index load %.3f + FASTQ->counters %.3f (%.2f M reads/s) + call/VCF %.3f + close %.3f\n", (unsigned long)total, ngpu,
-		        secs(t0, t1), secs(t0, t_loaded), secs(t_loaded, t_reads), (double)total / secs(t_loaded, t_reads) / 1e6, secs(t_reads, t_vcf), secs(t_vcf, t1));
-		// how long the process has existed (its start time in /proc/self/stat, 10 ms ticks, against the boot clock): what the loader
-		// and the HIP runtime's static start-up took before main() is that minus the wall time above
-		if (FILE *f = fopen("/proc/self/stat", "r")) {
-			char buf[2048]; const size_t n = fread(buf, 1, sizeof buf - 1, f); buf[n] = 0; fclose(f);
-			const char *q = strrchr(buf, ')');
-			unsigned long long start = 0; int field = 2;
-			for (q = q ? q + 1 : buf; q && *q && field < 22; ) { q = strchr(q + 1, ' '); field++; if (field == 21 && q) start = strtoull(q + 1, nullptr, 10); }
-			struct timespec bt; clock_gettime(CLOCK_BOOTTIME, &bt);
-			if (start) fprintf(stderr, "process: alive for %.2f s at this point\n", (double)bt.tv_sec + 1e-9 * (double)bt.tv_nsec - (double)start / (double)sysconf(_SC_CLK_TCK));
-		}
-	}
-	if (!orderly) { fflush(stdout); fflush(stderr); _exit(EXIT_SUCCESS); }
+	if (o.verbose) verbose_report(total, o.ngpu, t);
+	if (!o.orderly_exit) { fflush(stdout); fflush(stderr); _exit(EXIT_SUCCESS); }
 	return EXIT_SUCCESS;
 }
 
@@ -900,7 +975,8 @@ int main(int argc, const char *argv[])
 			if (fd < 0) throw vgh::Error{std::string("cannot open ") + argv[2]};
 			const uint64_t chunk = argc > 3 ? (uint64_t)atoll(argv[3]) : (1ull << 20);
 			std::vector<std::string> lines;
-			const bool quiet = env_int("VARGENO_FQPIPE_QUIET", 0) != 0;          // (a rate probe of the route: count, print nothing)
+			const GenoOptions o(0);
+			const bool quiet = o.fqpipe_quiet;                                   // (a rate probe of the route: count, print nothing)
 			uint64_t counted = 0;
 			auto one = [&](uint64_t nch, const uint64_t *km, uint64_t meta) {
 				if (quiet) { counted += 1 + (nch & 0); return; }
@@ -912,7 +988,7 @@ int main(int argc, const char *argv[])
 				lines.push_back(l + hx);
 			};
 			std::vector<vg_read_store *> none(1, nullptr);
-			PipeIngest pin(fd, chunk, argc > 4 ? atoi(argv[4]) : 2, none, [&](size_t, const uint64_t *k, const uint64_t *m, const uint64_t *o, uint64_t n) -> std::string {
+			PipeIngest pin(fd, chunk, argc > 4 ? atoi(argv[4]) : 2, o.pipe_copiers, none, [&](size_t, const uint64_t *k, const uint64_t *m, const uint64_t *o, uint64_t n) -> std::string {
 				for (uint64_t r = 0; r < n; r++) one(o[r + 1] - o[r], k + o[r], m[r]);
 				return std::string();
 			});
