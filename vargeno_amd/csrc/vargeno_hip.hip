@@ -931,10 +931,15 @@ struct vg_index {
 	// (profiles/ab_tail_streams_r05.txt): more streams than hardware queues, and the main stream shares one.)
 	hipStream_t tail2 = nullptr;
 	hipStream_t ingest = nullptr;                   // FASTQ framing + pack kernel of the next batch, under the current batch's wave kernel
-	int pack_overlap = -1;                          // the pack kernel of batch k+1 on the ingest stream, under batch k's wave kernel: 1 always, 0 never (VG_PACK_OVERLAP), -1: for small batches.
-	                                                // Off by default: nothing fits beside a full set of main-tier workgroups (4 x 128 VGPRs per SIMD), so the
-	                                                // two kernels only take turns on the CUs -- same reads/s (hg38 scale: 4.21 vs 4.26 ms per 8 M reads), but the
-	                                                // wave kernel's duration then includes the time it spent waiting for the pack kernel (4.18 vs 3.55 ms)
+	int pack_overlap = -1;                          // the pack kernel of batch k+1 on the ingest stream, under batch k's wave kernel: 1 always, 0 never (VG_PACK_OVERLAP), -1: small batches
+	                                                // always, large ones when the main stream is busy (enqueue_batch has the rules and the measurements behind them).
+	                                                // A pack workgroup (4 x 68 VGPRs, 10 752 B of LDS) does not fit beside FOUR main-tier workgroups of a CU (4 x 116 VGPRs per
+	                                                // SIMD, 4 x 38 928 B), it fits beside three.  With its full grid (16 workgroups per CU) the pack kernel therefore takes the CUs
+	                                                // in turns with the wave kernel and the step gains nothing (hg38 scale, 8 M reads: 2.742 against 2.750 / 2.764 ms); with ONE
+	                                                // workgroup per CU it runs for about a wave kernel's duration beside three main-tier workgroups per CU: 2.60 against 2.69 / 2.71
+	uint32_t pack_corun_wgs = 0;                    // the pack kernel's grid when it runs beside the wave kernel of a large batch: one workgroup per CU (VG_PACK_CORUN_WGS)
+	uint64_t pack_small_reads = 2u << 20;           // batches of up to this many reads are "small" (VG_PACK_SMALL_READS: the tests send the fixtures' batches down the large batches' path)
+	hipEvent_t last_e2 = nullptr;                   // the end of the wave kernel enqueued last (a slot's e2): not reached yet = the main stream is busy
 	bool ingest_stream = true;                      // VG_NO_INGEST_STREAM: FASTQ framing on the main stream too
 	DevIndex d{};
 	DevArena arena;                       // the index's device memory (vg_arena.h): permanent arrays and the temporaries of its construction
@@ -1318,6 +1323,8 @@ static int init_handle(vg_index *ix, int device)
 	}
 	HIP_TRY(hipStreamCreateWithFlags(&ix->ingest, hipStreamNonBlocking));
 	if (const char *e = getenv("VG_PACK_OVERLAP")) ix->pack_overlap = atoi(e) != 0 ? 1 : 0;
+	if (const char *e = getenv("VG_PACK_CORUN_WGS")) ix->pack_corun_wgs = (uint32_t)std::max(1, atoi(e));
+	if (const char *e = getenv("VG_PACK_SMALL_READS")) ix->pack_small_reads = strtoull(e, nullptr, 10);
 	ix->ingest_stream = getenv("VG_NO_INGEST_STREAM") == nullptr;
 	for (Slot &sl : ix->slot) HIP_TRY(hipHostMalloc((void **)&sl.h_ctr, 64, hipHostMallocDefault));
 	for (Slot &sl : ix->slot) { HIP_TRY(hipEventCreate(&sl.e0)); HIP_TRY(hipEventCreate(&sl.e1)); HIP_TRY(hipEventCreate(&sl.e2)); HIP_TRY(hipEventCreate(&sl.e3)); HIP_TRY(hipEventCreate(&sl.e4)); HIP_TRY(hipEventCreate(&sl.e5)); HIP_TRY(hipEventCreateWithFlags(&sl.e_fq, hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&sl.e_in, hipEventDisableTiming)); }
@@ -2222,12 +2229,30 @@ static int enqueue_batch(vg_index *ix, Slot &sl, const uint8_t *d_bases, const u
 	uint32_t *ctr = sl.ctr;
 	const unsigned g1 = (unsigned)std::min<uint64_t>((n_reads + 255) / 256, (uint64_t)ix->lane_grid_blocks);
 	if (!ix->force_generic) {
-		// main stream: pack, then the wave tier.  (Packing batch k+1 on a third stream under batch k's wave kernel was measured
-		// with 8 M-read batches and lost 12 %: two co-scheduled kernels split the CUs.  With batches of a million reads the
-		// launch gaps between the dependent kernels of one stream weigh more than that: chr22-scale, 1 M reads per step,
-		// 0.384 -> 0.352 ms per step (profiles/ab_chr22_pack_overlap_r05.txt) -- so small batches do overlap.)
+		const bool big = !STATS && ix->d.mx == nullptr;                // an index without the merged view: the kernel built for it
+		const bool sdx = !STATS && !big && ix->d.dx != nullptr && ix->d.dx_bits < 32u;      // a direct table of fewer than 2^32 buckets: the instantiation that compares (F, lo32)
+		// The pack kernel goes in front of the wave tier on the main stream, or onto the ingest stream, where batch k+1's runs while
+		// batch k's wave kernel does.  What was measured (profiles/ab_hg38_r07_pack_corun.txt has the runs, DESIGN.md §4 the table):
+		//  * batches of a million reads: the launch gaps between the dependent kernels of one stream weigh most; chr22-scale, 1 M reads per
+		//    step, 0.384 -> 0.352 ms with the pack kernel, full grid, on the ingest stream (profiles/ab_chr22_pack_overlap_r05.txt);
+		//  * 8 M-read batches, full grid (16 workgroups per CU): no gain with today's kernels (2.742 against 2.750 / 2.764 ms per step), a
+		//    loss with round 3's (2.779 -> 2.865).  A pack workgroup fits beside three main-tier workgroups of a CU, not beside four: where
+		//    one is placed, a main-tier workgroup is not, and a full grid takes every CU in turn with the wave kernel;
+		//  * 8 M-read batches, ONE pack workgroup per CU: it stays beside three main-tier workgroups per CU for about the wave kernel's
+		//    whole duration (pack 0.53 -> 2.3 ms, wave kernel 2.12 -> 2.51 ms as its events see it: 5 % of that is the fourth workgroup
+		//    it lacks on a CU, the rest is shared memory bandwidth) and the step gets shorter, 2.69-2.71 -> 2.60 ms; two per CU: 2.63.
+		// So a large batch takes the ingest stream with the small grid -- when the wave kernel of the batch before is still running or
+		// waiting on the main stream.  When it is not (a handle's first batch, a caller that synchronises after every batch) there is
+		// nothing to run beside, and a pack kernel of one workgroup per CU would take 2.3 ms instead of 0.53: main stream, full grid.
+		// Not measured, hence left as they were: the instantiations for an index without the merged view and for a direct table of
+		// fewer than 2^32 buckets with large batches, and the counting build.
 		hipStream_t ps = ix->stream;
-		if (ix->ingest && (ix->pack_overlap == 1 || (ix->pack_overlap < 0 && n_reads <= (2u << 20)))) ps = ix->ingest;
+		bool corun = false;
+		if (ix->ingest) {
+			const bool small = n_reads <= ix->pack_small_reads;
+			if (ix->pack_overlap == 1 || (ix->pack_overlap < 0 && small)) { ps = ix->ingest; corun = !small; }
+			else if (ix->pack_overlap < 0 && !packed && !STATS && !big && !sdx && ix->last_e2 && hipEventQuery(ix->last_e2) == hipErrorNotReady) { ps = ix->ingest; corun = true; }
+		}
 		if (produced_on && produced_on != ps) {                     // a batch gathered by the FASTQ framing on the ingest stream
 			HIP_TRY(hipEventRecord(sl.e_in, produced_on));
 			HIP_TRY(hipStreamWaitEvent(ps, sl.e_in, 0));
@@ -2238,7 +2263,7 @@ static int enqueue_batch(vg_index *ix, Slot &sl, const uint8_t *d_bases, const u
 		// reads per tile of the pack kernel: as many as the mean read length lets fit its LDS stream (64 up to 160 bases)
 		const uint64_t mean_len = n_reads ? (total_bases + n_reads - 1) / n_reads : 1;
 		const uint32_t pack_tr = (uint32_t)std::max<uint64_t>(4, std::min<uint64_t>(PACK_T, (uint64_t)PACK_T * PACK_MAXLEN / std::max<uint64_t>(mean_len, 1)));
-		const unsigned pgrid = (unsigned)std::min<uint64_t>((n_reads + (uint64_t)pack_tr * PACK_WPB - 1) / ((uint64_t)pack_tr * PACK_WPB), (uint64_t)ix->cus * pack_bpc);
+		const unsigned pgrid = (unsigned)std::min<uint64_t>((n_reads + (uint64_t)pack_tr * PACK_WPB - 1) / ((uint64_t)pack_tr * PACK_WPB), corun ? (uint64_t)(ix->pack_corun_wgs ? ix->pack_corun_wgs : ix->cus) : (uint64_t)ix->cus * pack_bpc);
 		const bool fused = VG_FUSE_PACK && !packed && !getenv("VG_NO_FUSE");          // the main tier encodes the reads itself (experiment)
 		const FuseIn fin{fused ? d_bases : nullptr, d_quals, d_gate, &ctr[3]}, nofuse{nullptr, nullptr, nullptr, nullptr};
 		if (!packed && !fused) vg_pack_kernel<<<pgrid, PACK_T * PACK_WPB, 0, ps>>>(d_bases, d_quals, d_offsets, n_reads, sl.pk_kmer, sl.pk_meta, &ctr[3], d_n_reads, d_gate, pack_tr);
@@ -2250,12 +2275,11 @@ static int enqueue_batch(vg_index *ix, Slot &sl, const uint8_t *d_bases, const u
 		HIP_TRY(hipEventRecord(sl.e5, ix->stream));               // the wave kernel's own start
 		ix->cnt4_dirty = true;
 		const unsigned wgrid = (unsigned)std::min<uint64_t>((n_reads + 64 * W1_WPB - 1) / (64 * W1_WPB), (uint64_t)ix->wave_grid / W1_WPB);
-		const bool big = !STATS && ix->d.mx == nullptr;                // an index without the merged view: the kernel built for it
-		const bool sdx = !STATS && !big && ix->d.dx != nullptr && ix->d.dx_bits < 32u;      // a direct table of fewer than 2^32 buckets: the instantiation that compares (F, lo32)
 		if (big) vg_wave_kernel_big<W1_ECAP, W1_NCAP, W1_WPB><<<wgrid, 64 * W1_WPB, 0, ix->stream>>>(ix->d, sl.pk_kmer, sl.pk_meta, d_offsets, n_reads, nullptr, d_n_reads, sl.listA, &ctr[0], &ctr[4], ix->work_chunk, ix->d_stats, fin);
 		else if (sdx) vg_wave_kernel<false, W1_ECAP, W1_NCAP, W1_WPB, true><<<wgrid, 64 * W1_WPB, 0, ix->stream>>>(ix->d, sl.pk_kmer, sl.pk_meta, d_offsets, n_reads, nullptr, d_n_reads, sl.listA, &ctr[0], &ctr[4], ix->work_chunk, ix->d_stats, fin);
 		else vg_wave_kernel<STATS, W1_ECAP, W1_NCAP, W1_WPB><<<wgrid, 64 * W1_WPB, 0, ix->stream>>>(ix->d, sl.pk_kmer, sl.pk_meta, d_offsets, n_reads, nullptr, d_n_reads, sl.listA, &ctr[0], &ctr[4], ix->work_chunk, ix->d_stats, fin);
 		HIP_TRY(hipEventRecord(sl.e2, ix->stream));
+		ix->last_e2 = sl.e2;
 		// tail stream, the deep tier: the same kernel with deeper tables over the spill list (single-wave workgroups of 42 KB of LDS).
 		// ONE deep tier (r04; r03 had a 40 + 16 tier in front of it): it starts the moment the main tier's workgroups retire, while
 		// the CUs are free.  A tier enqueued behind another one found the NEXT batch's main-tier kernel on every CU and was only placed
