@@ -27,6 +27,7 @@
 #include <condition_variable>
 #include <mutex>
 #include <chrono>
+#include <initializer_list>
 #include <map>
 #include <memory>
 #include <string>
@@ -897,27 +898,71 @@ struct ScratchBuf {
 	size_t bytes = 0;
 };
 
+struct NoCopy { NoCopy() = default; NoCopy(const NoCopy &) = delete; NoCopy &operator=(const NoCopy &) = delete; };
+// A buffer of a batch slot, device memory or page-locked host memory: grow-only, sized by its user before every batch.  A block that
+// is too small is freed BEFORE the new one is asked for, and the capacity is zero meanwhile: a failed allocation leaves
+// {nullptr, 0}, never a stale size.  The new block holds exactly `count` elements.
+template <class T, bool PINNED>
+struct SlotBuf : NoCopy {
+	T *p = nullptr;
+	uint64_t cap = 0;                                   // elements
+	~SlotBuf() { release(); }
+	int reserve(uint64_t count, const char *what)
+	{
+		if (count <= cap) return VG_OK;
+		release();
+		const hipError_t e = PINNED ? hipHostMalloc((void **)&p, (size_t)count * sizeof(T), hipHostMallocDefault) : hipMalloc((void **)&p, (size_t)count * sizeof(T));
+		if (e != hipSuccess) { p = nullptr; return fail(e == hipErrorOutOfMemory ? VG_ENOMEM : VG_ENODEV, PINNED ? "hipHostMalloc(%s): %s" : "hipMalloc(%s): %s", what, hipGetErrorString(e)); }
+		cap = count;
+		return VG_OK;
+	}
+	void release()
+	{
+		if (p) (void)(PINNED ? hipHostFree(p) : hipFree(p));
+		p = nullptr; cap = 0;
+	}
+};
+template <class T> using DevBuf = SlotBuf<T, false>;
+template <class T> using PinnedBuf = SlotBuf<T, true>;
+// Buffers that share one capacity: all of them are freed before any is allocated (that bounds peak memory), and the last one has
+// the size only when all of them have it.
+template <class B>
+static int reserve_together(std::initializer_list<B *> bufs, uint64_t count, const char *what)
+{
+	if (count <= (*(bufs.end() - 1))->cap) return VG_OK;
+	for (B *b : bufs) b->release();
+	for (B *b : bufs) { const int rc = b->reserve(count, what); if (rc) return rc; }
+	return VG_OK;
+}
+struct SlotEvent : NoCopy {
+	hipEvent_t e = nullptr;
+	~SlotEvent() { if (e) (void)hipEventDestroy(e); }
+	operator hipEvent_t() const { return e; }
+};
+
 // Per-batch resources.  A handle keeps NSLOT batches in flight: the wave tier of batch k+1 runs on the
 // main stream while the (rare, latency-bound) lane tiers of batch k finish on the tail stream.
+// (The buffers and events give themselves back when the handle is deleted: vg_index_close.)
 constexpr int NSLOT = 3;            // (5 and 8 were measured: no gain at 8 M-read batches, 10-30 % slower at 1 M -- more pack kernels run ahead and get in the wave kernel's way)
 struct Slot {
-	uint32_t *listA = nullptr, *listB = nullptr, *listC = nullptr;  uint64_t list_cap = 0;   // spill lists: main -> deep tier (A), deep tier -> lane tier (B), lost (C)
+	DevBuf<uint32_t> listA, listB, listC;   // spill lists, one capacity (reserve_together): main -> deep tier (A), deep tier -> lane tier (B), lost (C)
 	uint32_t *ctr = nullptr;              // [0] wave-tier overflow, [1] lane-tier overflow, [2] lost -- this batch
-	uint32_t *h_ctr = nullptr;            // page-locked copy of ctr[0..3], made on the tail stream when the batch's tiers are done
+	PinnedBuf<uint32_t> h_ctr;            // page-locked copy of ctr[0..3], made on the tail stream when the batch's tiers are done
 	// what the generic lane tier needs should the deep tier leave reads behind: it is only launched then (harvest), never empty
 	const uint8_t *lt_bases = nullptr, *lt_quals = nullptr; const uint64_t *lt_offsets = nullptr; const uint32_t *lt_gate = nullptr; bool lt_packed = false, lt_stats = false, lt_enqueued = false, lt_late = false;      // lt_late: the deep tier's leftovers went through vg_late_collect (the per-batch lane tier then only has the residual list: listA, ctr[6])
-	uint64_t *pk_kmer = nullptr, *pk_meta = nullptr;  uint64_t pk_kmer_cap = 0, pk_meta_cap = 0;   // packed reads of this batch
-	uint8_t *st_bases = nullptr, *st_quals = nullptr; uint64_t *st_offsets = nullptr;   // staging of vg_reads_submit / vg_fastq_submit
-	uint32_t *st_gate = nullptr; uint64_t st_gate_cap = 0;                              // gate words of a batch framed on the device
-	uint64_t *hp_kmers = nullptr, *hp_meta = nullptr, *hp_offsets = nullptr; uint64_t hp_kmers_cap = 0, hp_reads_cap = 0;   // page-locked HOST staging of a batch framed + packed on the host
-	uint8_t *fq_text = nullptr; uint32_t *fq_lines = nullptr, *fq_tiles = nullptr; uint64_t fq_text_cap = 0, fq_lines_cap = 0, fq_tiles_cap = 0;   // FASTQ framing
-	void *fq_tmp = nullptr; uint64_t fq_tmp_cap = 0;                 // scan scratch (grow-only: no allocation per chunk)
-	FqChunk *fq_chunk = nullptr;                                     // this chunk's framing results, device resident
+	DevBuf<uint64_t> pk_kmer, pk_meta;                                // packed reads of this batch
+	DevBuf<uint8_t> st_bases, st_quals; DevBuf<uint64_t> st_offsets;  // staging of vg_reads_submit / vg_fastq_submit
+	DevBuf<uint32_t> st_gate;                                         // gate words of a batch framed on the device
+	PinnedBuf<uint64_t> hp_kmers, hp_meta, hp_offsets;                // page-locked HOST staging of a batch framed + packed on the host (hp_meta and hp_offsets: one capacity)
+	DevBuf<uint8_t> fq_text; DevBuf<uint32_t> fq_lines, fq_tiles;     // FASTQ framing
+	DevBuf<uint8_t> fq_tmp;                                           // scan scratch, bytes (grow-only: no allocation per chunk)
+	DevBuf<FqChunk> fq_chunk;                                         // this chunk's framing results (one FqChunk), device resident
 	uint64_t fq_text_len = 0;                                        // bytes of text copied into fq_text (after the FQ_CARRY gap)
-	hipEvent_t e_in = nullptr;                                       // the batch's buffers are complete (when another stream produced them)
-	hipEvent_t e_fq = nullptr; bool fq_tail_wanted = false;          // the NEXT chunk's prepare kernel reads this text's tail: recorded after it
-	uint64_t stage_bytes = 0, stage_quals_bytes = 0, stage_reads = 0;      // capacities of st_bases, st_quals, st_offsets
-	hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr, e4 = nullptr, e5 = nullptr;
+	SlotEvent e_in;                                                  // the batch's buffers are complete (when another stream produced them)
+	SlotEvent e_fq; bool fq_tail_wanted = false;                     // the NEXT chunk's prepare kernel reads this text's tail: recorded after it
+	// the batch's timeline (harvest reads the times between them): the pack kernel on its stream; the wave kernel (main tier) on the main
+	// stream; the deep tier behind it on the tail stream; the batch's counters on the host, behind the last of its tiers
+	SlotEvent pack_begin, pack_end, wave_begin, wave_end, deep_end, batch_done;
 	bool busy = false;
 };
 
@@ -939,8 +984,11 @@ struct vg_index {
 	                                                // workgroup per CU it runs for about a wave kernel's duration beside three main-tier workgroups per CU: 2.60 against 2.69 / 2.71
 	uint32_t pack_corun_wgs = 0;                    // the pack kernel's grid when it runs beside the wave kernel of a large batch: one workgroup per CU (VG_PACK_CORUN_WGS)
 	uint64_t pack_small_reads = 2u << 20;           // batches of up to this many reads are "small" (VG_PACK_SMALL_READS: the tests send the fixtures' batches down the large batches' path)
-	hipEvent_t last_e2 = nullptr;                   // the end of the wave kernel enqueued last (a slot's e2): not reached yet = the main stream is busy
+	int pack_bpc = 16;                              // the pack kernel's full grid: workgroups (of PACK_WPB tiles at a time) per CU (VG_PACK_BPC)
+	bool fuse_pack = VG_FUSE_PACK;                  // the main tier encodes the reads itself (experiment: a build with -DVG_FUSE_PACK; VG_NO_FUSE turns it off)
+	hipEvent_t last_wave_end = nullptr;             // the end of the wave kernel enqueued last (a slot's wave_end): not reached yet = the main stream is busy
 	bool ingest_stream = true;                      // VG_NO_INGEST_STREAM: FASTQ framing on the main stream too
+	hipStream_t ingest_or_main() const { return ingest_stream ? ingest : stream; }     // where framing, and the copies of a packed batch, go
 	DevIndex d{};
 	DevArena arena;                       // the index's device memory (vg_arena.h): permanent arrays and the temporaries of its construction
 	std::vector<void *> owned;            // device allocations of the index made with hipMalloc (small handle-lifetime buffers; everything, when the arena could not be set up)
@@ -971,6 +1019,7 @@ struct vg_index {
 	int lane_grid_blocks = 0, wave_grid = 0;
 	uint32_t work_chunk = 128;            // reads a main-tier wave pulls from the launch's work counter at a time (VG_WORK_CHUNK)
 	uint32_t w2_chunk = 8, w2_wpc = 3;    // deep tier: reads a wave pulls at a time (VG_W2_CHUNK), workgroups per CU of its grid (VG_W2_WPC)
+	bool w2_full_grid = false;            // ... and that grid for every batch, whatever the lists before were like (VG_W2_FULL_GRID)
 	FqStream *d_fq = nullptr;             // FASTQ stream state (vg_fastq_stream_*)
 	bool fq_open = false; int fq_prev_slot = -1;
 	uint64_t max_device_bytes = 0;        // the caller's budget for this replica (vg_index_open_ex; 0: the whole device)
@@ -1090,20 +1139,12 @@ extern "C" void vg_index_close(vg_index *ix)
 	if (ix->ingest) (void)hipStreamSynchronize(ix->ingest);
 	for (void *p : ix->owned) (void)hipFree(p);
 	ix->arena.destroy();
-	for (Slot &sl : ix->slot) {
-		void *extra[] = {sl.listA, sl.listB, sl.listC, sl.st_bases, sl.st_quals, sl.st_gate, sl.st_offsets, sl.pk_kmer, sl.pk_meta, sl.fq_text, sl.fq_lines, sl.fq_tiles, sl.fq_tmp, sl.fq_chunk};
-		for (void *p : extra) if (p) (void)hipFree(p);
-		hipEvent_t evs[] = {sl.e0, sl.e1, sl.e2, sl.e3, sl.e4, sl.e5, sl.e_fq, sl.e_in};
-		for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e);
-		void *host[] = {sl.hp_kmers, sl.hp_meta, sl.hp_offsets, sl.h_ctr};
-		for (void *p : host) if (p) (void)hipHostFree(p);
-	}
 	delete ix->packer;
 	if (ix->stream) (void)hipStreamDestroy(ix->stream);
 	if (ix->tail) (void)hipStreamDestroy(ix->tail);
 	if (ix->tail2) (void)hipStreamDestroy(ix->tail2);
 	if (ix->ingest) (void)hipStreamDestroy(ix->ingest);
-	delete ix;
+	delete ix;                            // (the batch slots' buffers and events go with it)
 }
 
 // Wall time of the phases of vg_index_open / vg_index_create (start-up is SURVEY.md §8f-4): kept in the handle (vg_index_open_report),
@@ -1325,9 +1366,15 @@ static int init_handle(vg_index *ix, int device)
 	if (const char *e = getenv("VG_PACK_OVERLAP")) ix->pack_overlap = atoi(e) != 0 ? 1 : 0;
 	if (const char *e = getenv("VG_PACK_CORUN_WGS")) ix->pack_corun_wgs = (uint32_t)std::max(1, atoi(e));
 	if (const char *e = getenv("VG_PACK_SMALL_READS")) ix->pack_small_reads = strtoull(e, nullptr, 10);
+	if (const char *e = getenv("VG_PACK_BPC")) ix->pack_bpc = std::max(1, atoi(e));
+	if (getenv("VG_NO_FUSE")) ix->fuse_pack = false;
 	ix->ingest_stream = getenv("VG_NO_INGEST_STREAM") == nullptr;
-	for (Slot &sl : ix->slot) HIP_TRY(hipHostMalloc((void **)&sl.h_ctr, 64, hipHostMallocDefault));
-	for (Slot &sl : ix->slot) { HIP_TRY(hipEventCreate(&sl.e0)); HIP_TRY(hipEventCreate(&sl.e1)); HIP_TRY(hipEventCreate(&sl.e2)); HIP_TRY(hipEventCreate(&sl.e3)); HIP_TRY(hipEventCreate(&sl.e4)); HIP_TRY(hipEventCreate(&sl.e5)); HIP_TRY(hipEventCreateWithFlags(&sl.e_fq, hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&sl.e_in, hipEventDisableTiming)); }
+	for (Slot &sl : ix->slot) {
+		int rc = sl.h_ctr.reserve(16, "batch counters");
+		if (rc) return rc;
+		for (SlotEvent *ev : {&sl.pack_begin, &sl.pack_end, &sl.wave_begin, &sl.wave_end, &sl.deep_end, &sl.batch_done}) HIP_TRY(hipEventCreate(&ev->e));
+		for (SlotEvent *ev : {&sl.e_fq, &sl.e_in}) HIP_TRY(hipEventCreateWithFlags(&ev->e, hipEventDisableTiming));
+	}
 	hipDeviceProp_t prop;
 	HIP_TRY(hipGetDeviceProperties(&prop, device));
 	ix->cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
@@ -1339,6 +1386,7 @@ static int init_handle(vg_index *ix, int device)
 	if (const char *e = getenv("VG_WORK_CHUNK")) ix->work_chunk = (uint32_t)std::max(1, atoi(e));
 	if (const char *e = getenv("VG_W2_CHUNK")) ix->w2_chunk = (uint32_t)std::max(1, atoi(e));
 	if (const char *e = getenv("VG_W2_WPC")) ix->w2_wpc = (uint32_t)std::max(1, atoi(e));
+	ix->w2_full_grid = getenv("VG_W2_FULL_GRID") != nullptr;
 	return VG_OK;
 }
 
@@ -2144,31 +2192,37 @@ extern "C" uint32_t vg_index_views(const vg_index *ix)
 // ------------------------------------------------------------------------------------------------
 // read batches
 // ------------------------------------------------------------------------------------------------
+// vg_lane_kernel, the counting build (stats) or the plain one
+template <class... A>
+static void launch_lane(bool stats, unsigned grid, unsigned block, hipStream_t st, const A &...a)
+{
+	if (stats) vg_lane_kernel<true><<<grid, block, 0, st>>>(a...);
+	else vg_lane_kernel<false><<<grid, block, 0, st>>>(a...);
+}
+
 static int harvest(vg_index *ix, Slot &sl)
 {
 	if (!sl.busy) return VG_OK;
-	HIP_TRY(hipEventSynchronize(sl.e3));
+	HIP_TRY(hipEventSynchronize(sl.batch_done));
 	// reads left for the per-batch lane tier: what the late store did not take (ctr[6]), or -- VG_FORCE_GENERIC, VG_NO_LATE_STORE -- all of listB
-	const uint32_t resid = sl.lt_late ? sl.h_ctr[6] : sl.h_ctr[1];
-	uint32_t *const r_list = sl.lt_late ? sl.listA : sl.listB, *const r_cnt = sl.lt_late ? &sl.ctr[6] : &sl.ctr[1];
+	const uint32_t resid = sl.lt_late ? sl.h_ctr.p[6] : sl.h_ctr.p[1];
+	uint32_t *const r_list = sl.lt_late ? sl.listA.p : sl.listB.p, *const r_cnt = sl.lt_late ? &sl.ctr[6] : &sl.ctr[1];
 	if (resid) ix->lane_tier_seen = true;
 	if (resid && !sl.lt_enqueued) {
 		// the lane machine with its lists in HBM finishes them now
-		if (sl.lt_stats) vg_lane_kernel<true><<<ix->big.s.nlanes / 64, 64, 0, ix->tail2>>>(ix->d, ix->big.s, sl.lt_bases, sl.lt_quals, sl.lt_offsets, 0, r_list, r_cnt, sl.listC, &sl.ctr[2], ix->d_stats, nullptr, sl.lt_gate, sl.pk_kmer, sl.pk_meta, sl.lt_packed);
-		else vg_lane_kernel<false><<<ix->big.s.nlanes / 64, 64, 0, ix->tail2>>>(ix->d, ix->big.s, sl.lt_bases, sl.lt_quals, sl.lt_offsets, 0, r_list, r_cnt, sl.listC, &sl.ctr[2], ix->d_stats, nullptr, sl.lt_gate, sl.pk_kmer, sl.pk_meta, sl.lt_packed);
+		launch_lane(sl.lt_stats, ix->big.s.nlanes / 64, 64, ix->tail2, ix->d, ix->big.s, sl.lt_bases, sl.lt_quals, sl.lt_offsets, 0, r_list, r_cnt, sl.listC.p, &sl.ctr[2], ix->d_stats, nullptr, sl.lt_gate, sl.pk_kmer.p, sl.pk_meta.p, sl.lt_packed);
 		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpyAsync(sl.h_ctr, sl.ctr, 32, hipMemcpyDeviceToHost, ix->tail2));
+		HIP_TRY(hipMemcpyAsync(sl.h_ctr.p, sl.ctr, 32, hipMemcpyDeviceToHost, ix->tail2));
 		HIP_TRY(hipStreamSynchronize(ix->tail2));
 	}
-	for (int i = 0; i < 4; i++) ix->cum[i] += sl.h_ctr[i];
+	for (int i = 0; i < 4; i++) ix->cum[i] += sl.h_ctr.p[i];
 	// the deep tier's grid follows the lists it has been getting (enqueue_batch): the larger of this batch's and half the hint before
-	ix->spill_hint = std::max<uint32_t>(sl.h_ctr[0], ix->spill_hint / 2);
+	ix->spill_hint = std::max<uint32_t>(sl.h_ctr.p[0], ix->spill_hint / 2);
 	ix->spill_known = true;
-	float a = 0, b = 0, c = 0, t = 0;
-	HIP_TRY(hipEventElapsedTime(&a, sl.e0, sl.e1)); HIP_TRY(hipEventElapsedTime(&b, sl.e5, sl.e2));
-	float w2 = 0;
-	HIP_TRY(hipEventElapsedTime(&c, sl.e2, sl.e3)); HIP_TRY(hipEventElapsedTime(&t, sl.e0, sl.e3)); HIP_TRY(hipEventElapsedTime(&w2, sl.e2, sl.e4));
-	ix->t_pack += a; ix->t_main += b; ix->t_tail += c; ix->t_total += t; ix->t_w2 += w2; ix->t_batches++;
+	float pack = 0, wave = 0, tail = 0, total = 0, w2 = 0;
+	HIP_TRY(hipEventElapsedTime(&pack, sl.pack_begin, sl.pack_end)); HIP_TRY(hipEventElapsedTime(&wave, sl.wave_begin, sl.wave_end));
+	HIP_TRY(hipEventElapsedTime(&tail, sl.wave_end, sl.batch_done)); HIP_TRY(hipEventElapsedTime(&total, sl.pack_begin, sl.batch_done)); HIP_TRY(hipEventElapsedTime(&w2, sl.wave_end, sl.deep_end));
+	ix->t_pack += pack; ix->t_main += wave; ix->t_tail += tail; ix->t_total += total; ix->t_w2 += w2; ix->t_batches++;
 	sl.busy = false;
 	return VG_OK;
 }
@@ -2183,8 +2237,7 @@ static int run_late_store(vg_index *ix)
 	const uint64_t n = st[1];
 	if (st[0] == 0) return VG_OK;
 	if (n) {
-		if (ix->late_stats) vg_lane_kernel<true><<<ix->big.s.nlanes / 64, 64, 0, ix->tail>>>(ix->d, ix->big.s, nullptr, nullptr, ix->late.offsets, n, nullptr, nullptr, ix->late.lost, ix->late.lost_n, ix->d_stats, nullptr, nullptr, ix->late.kmers, ix->late.meta, true);
-		else vg_lane_kernel<false><<<ix->big.s.nlanes / 64, 64, 0, ix->tail>>>(ix->d, ix->big.s, nullptr, nullptr, ix->late.offsets, n, nullptr, nullptr, ix->late.lost, ix->late.lost_n, ix->d_stats, nullptr, nullptr, ix->late.kmers, ix->late.meta, true);
+		launch_lane(ix->late_stats, ix->big.s.nlanes / 64, 64, ix->tail, ix->d, ix->big.s, nullptr, nullptr, ix->late.offsets, n, nullptr, nullptr, ix->late.lost, ix->late.lost_n, ix->d_stats, nullptr, nullptr, ix->late.kmers, ix->late.meta, true);
 		HIP_TRY(hipGetLastError());
 	}
 	uint32_t lost = 0;
@@ -2219,74 +2272,95 @@ static int finish_pending(vg_index *ix)
 	return VG_OK;
 }
 
+// The pack kernel goes in front of the wave tier on the main stream, or onto the ingest stream, where batch k+1's runs while
+// batch k's wave kernel does.  What was measured (profiles/ab_hg38_r07_pack_corun.txt has the runs, DESIGN.md §4 the table):
+//  * batches of a million reads: the launch gaps between the dependent kernels of one stream weigh most; chr22-scale, 1 M reads per
+//    step, 0.384 -> 0.352 ms with the pack kernel, full grid, on the ingest stream (profiles/ab_chr22_pack_overlap_r05.txt);
+//  * 8 M-read batches, full grid (16 workgroups per CU): no gain with today's kernels (2.742 against 2.750 / 2.764 ms per step), a
+//    loss with round 3's (2.779 -> 2.865).  A pack workgroup fits beside three main-tier workgroups of a CU, not beside four: where
+//    one is placed, a main-tier workgroup is not, and a full grid takes every CU in turn with the wave kernel;
+//  * 8 M-read batches, ONE pack workgroup per CU: it stays beside three main-tier workgroups per CU for about the wave kernel's
+//    whole duration (pack 0.53 -> 2.3 ms, wave kernel 2.12 -> 2.51 ms as its events see it: 5 % of that is the fourth workgroup
+//    it lacks on a CU, the rest is shared memory bandwidth) and the step gets shorter, 2.69-2.71 -> 2.60 ms; two per CU: 2.63.
+// So a large batch takes the ingest stream with the small grid -- when the wave kernel of the batch before is still running or
+// waiting on the main stream.  When it is not (a handle's first batch, a caller that synchronises after every batch) there is
+// nothing to run beside, and a pack kernel of one workgroup per CU would take 2.3 ms instead of 0.53: main stream, full grid.
+// Not measured, hence left as they were: the instantiations for an index without the merged view and for a direct table of
+// fewer than 2^32 buckets with large batches, and the counting build.
+struct PackPlan { hipStream_t stream; bool corun; };
+// packed: no pack kernel, the copies of the packed form take its place.  headline: the wave kernel is the headline instantiation.
+static PackPlan plan_pack(const vg_index *ix, uint64_t n_reads, bool packed, bool headline)
+{
+	if (!ix->ingest) return {ix->stream, false};
+	const bool small = n_reads <= ix->pack_small_reads;
+	if (ix->pack_overlap == 1 || (ix->pack_overlap < 0 && small)) return {ix->ingest, !small};
+	if (ix->pack_overlap < 0 && !packed && headline && ix->last_wave_end && hipEventQuery(ix->last_wave_end) == hipErrorNotReady) return {ix->ingest, true};
+	return {ix->stream, false};
+}
+
+// A batch's first step, on the stream its first kernel goes to: wait for the stream that produced its buffers (a batch gathered by the
+// FASTQ framing, or copied up, on the ingest stream), zero its counters, mark its start.
+static int begin_batch(Slot &sl, hipStream_t on, hipStream_t produced_on)
+{
+	if (produced_on && produced_on != on) {
+		HIP_TRY(hipEventRecord(sl.e_in, produced_on));
+		HIP_TRY(hipStreamWaitEvent(on, sl.e_in, 0));
+	}
+	HIP_TRY(hipMemsetAsync(sl.ctr, 0, 64, on));
+	HIP_TRY(hipEventRecord(sl.pack_begin, on));
+	return VG_OK;
+}
+
+// One tier of the wave machine (<W1_*>: the main tier, <W3_*, 1>: the deep tier): the kernel built for an index without the merged
+// view (big), the instantiation that compares (F, lo32) (sdx), or the general one, as the counting build (stats) or the plain one.
+template <int ECAP, int NCAP, int WPB, class... A>
+static void launch_wave(bool big, bool sdx, bool stats, unsigned grid, hipStream_t st, const A &...a)
+{
+	if (big) vg_wave_kernel_big<ECAP, NCAP, WPB><<<grid, 64 * WPB, 0, st>>>(a...);
+	else if (sdx) vg_wave_kernel<false, ECAP, NCAP, WPB, true><<<grid, 64 * WPB, 0, st>>>(a...);
+	else if (stats) vg_wave_kernel<true, ECAP, NCAP, WPB><<<grid, 64 * WPB, 0, st>>>(a...);
+	else vg_wave_kernel<false, ECAP, NCAP, WPB><<<grid, 64 * WPB, 0, st>>>(a...);
+}
+
 // One batch = pack -> wave tier on the main stream, then lane tier (mid scratch) -> lane tier (deep scratch)
 // on the tail stream; the list launches size themselves from device counters, so nothing waits for the host.
 // n_reads: the batch's size, or (d_n_reads given) an upper bound of the size the device holds at d_n_reads
 // packed: the batch is already packed (sl.pk_kmer / sl.pk_meta hold it, d_offsets = 32 x chunks before each read): no pack kernel
-template <bool STATS>
-static int enqueue_batch(vg_index *ix, Slot &sl, const uint8_t *d_bases, const uint8_t *d_quals, const uint32_t *d_gate, const uint64_t *d_offsets, uint64_t n_reads, hipStream_t produced_on, const uint32_t *d_n_reads, const bool packed, const uint64_t total_bases)
+static int enqueue_batch(vg_index *ix, Slot &sl, const bool stats, const uint8_t *d_bases, const uint8_t *d_quals, const uint32_t *d_gate, const uint64_t *d_offsets, uint64_t n_reads, hipStream_t produced_on, const uint32_t *d_n_reads, const bool packed, const uint64_t total_bases)
 {
 	uint32_t *ctr = sl.ctr;
-	const unsigned g1 = (unsigned)std::min<uint64_t>((n_reads + 255) / 256, (uint64_t)ix->lane_grid_blocks);
+	int rc;
 	if (!ix->force_generic) {
-		const bool big = !STATS && ix->d.mx == nullptr;                // an index without the merged view: the kernel built for it
-		const bool sdx = !STATS && !big && ix->d.dx != nullptr && ix->d.dx_bits < 32u;      // a direct table of fewer than 2^32 buckets: the instantiation that compares (F, lo32)
-		// The pack kernel goes in front of the wave tier on the main stream, or onto the ingest stream, where batch k+1's runs while
-		// batch k's wave kernel does.  What was measured (profiles/ab_hg38_r07_pack_corun.txt has the runs, DESIGN.md §4 the table):
-		//  * batches of a million reads: the launch gaps between the dependent kernels of one stream weigh most; chr22-scale, 1 M reads per
-		//    step, 0.384 -> 0.352 ms with the pack kernel, full grid, on the ingest stream (profiles/ab_chr22_pack_overlap_r05.txt);
-		//  * 8 M-read batches, full grid (16 workgroups per CU): no gain with today's kernels (2.742 against 2.750 / 2.764 ms per step), a
-		//    loss with round 3's (2.779 -> 2.865).  A pack workgroup fits beside three main-tier workgroups of a CU, not beside four: where
-		//    one is placed, a main-tier workgroup is not, and a full grid takes every CU in turn with the wave kernel;
-		//  * 8 M-read batches, ONE pack workgroup per CU: it stays beside three main-tier workgroups per CU for about the wave kernel's
-		//    whole duration (pack 0.53 -> 2.3 ms, wave kernel 2.12 -> 2.51 ms as its events see it: 5 % of that is the fourth workgroup
-		//    it lacks on a CU, the rest is shared memory bandwidth) and the step gets shorter, 2.69-2.71 -> 2.60 ms; two per CU: 2.63.
-		// So a large batch takes the ingest stream with the small grid -- when the wave kernel of the batch before is still running or
-		// waiting on the main stream.  When it is not (a handle's first batch, a caller that synchronises after every batch) there is
-		// nothing to run beside, and a pack kernel of one workgroup per CU would take 2.3 ms instead of 0.53: main stream, full grid.
-		// Not measured, hence left as they were: the instantiations for an index without the merged view and for a direct table of
-		// fewer than 2^32 buckets with large batches, and the counting build.
-		hipStream_t ps = ix->stream;
-		bool corun = false;
-		if (ix->ingest) {
-			const bool small = n_reads <= ix->pack_small_reads;
-			if (ix->pack_overlap == 1 || (ix->pack_overlap < 0 && small)) { ps = ix->ingest; corun = !small; }
-			else if (ix->pack_overlap < 0 && !packed && !STATS && !big && !sdx && ix->last_e2 && hipEventQuery(ix->last_e2) == hipErrorNotReady) { ps = ix->ingest; corun = true; }
-		}
-		if (produced_on && produced_on != ps) {                     // a batch gathered by the FASTQ framing on the ingest stream
-			HIP_TRY(hipEventRecord(sl.e_in, produced_on));
-			HIP_TRY(hipStreamWaitEvent(ps, sl.e_in, 0));
-		}
-		HIP_TRY(hipMemsetAsync(ctr, 0, 64, ps));
-		HIP_TRY(hipEventRecord(sl.e0, ps));
-		static const int pack_bpc = getenv("VG_PACK_BPC") ? std::max(1, atoi(getenv("VG_PACK_BPC"))) : 16;          // workgroups (of PACK_WPB tiles at a time) per CU
+		const bool big = !stats && ix->d.mx == nullptr;                // an index without the merged view: the kernel built for it
+		const bool sdx = !stats && !big && ix->d.dx != nullptr && ix->d.dx_bits < 32u;      // a direct table of fewer than 2^32 buckets: the instantiation that compares (F, lo32)
+		const PackPlan pp = plan_pack(ix, n_reads, packed, !stats && !big && !sdx);
+		hipStream_t ps = pp.stream;
+		if ((rc = begin_batch(sl, ps, produced_on))) return rc;
 		// reads per tile of the pack kernel: as many as the mean read length lets fit its LDS stream (64 up to 160 bases)
 		const uint64_t mean_len = n_reads ? (total_bases + n_reads - 1) / n_reads : 1;
 		const uint32_t pack_tr = (uint32_t)std::max<uint64_t>(4, std::min<uint64_t>(PACK_T, (uint64_t)PACK_T * PACK_MAXLEN / std::max<uint64_t>(mean_len, 1)));
-		const unsigned pgrid = (unsigned)std::min<uint64_t>((n_reads + (uint64_t)pack_tr * PACK_WPB - 1) / ((uint64_t)pack_tr * PACK_WPB), corun ? (uint64_t)(ix->pack_corun_wgs ? ix->pack_corun_wgs : ix->cus) : (uint64_t)ix->cus * pack_bpc);
-		const bool fused = VG_FUSE_PACK && !packed && !getenv("VG_NO_FUSE");          // the main tier encodes the reads itself (experiment)
+		const unsigned pgrid = (unsigned)std::min<uint64_t>((n_reads + (uint64_t)pack_tr * PACK_WPB - 1) / ((uint64_t)pack_tr * PACK_WPB), pp.corun ? (uint64_t)(ix->pack_corun_wgs ? ix->pack_corun_wgs : ix->cus) : (uint64_t)ix->cus * ix->pack_bpc);
+		const bool fused = ix->fuse_pack && !packed;                 // the main tier encodes the reads itself (experiment)
 		const FuseIn fin{fused ? d_bases : nullptr, d_quals, d_gate, &ctr[3]}, nofuse{nullptr, nullptr, nullptr, nullptr};
-		if (!packed && !fused) vg_pack_kernel<<<pgrid, PACK_T * PACK_WPB, 0, ps>>>(d_bases, d_quals, d_offsets, n_reads, sl.pk_kmer, sl.pk_meta, &ctr[3], d_n_reads, d_gate, pack_tr);
-		HIP_TRY(hipEventRecord(sl.e1, ps));
-		if (ps != ix->stream) HIP_TRY(hipStreamWaitEvent(ix->stream, sl.e1, 0));
+		if (!packed && !fused) vg_pack_kernel<<<pgrid, PACK_T * PACK_WPB, 0, ps>>>(d_bases, d_quals, d_offsets, n_reads, sl.pk_kmer.p, sl.pk_meta.p, &ctr[3], d_n_reads, d_gate, pack_tr);
+		HIP_TRY(hipEventRecord(sl.pack_end, ps));
+		if (ps != ix->stream) HIP_TRY(hipStreamWaitEvent(ix->stream, sl.pack_end, 0));
 		// The previous batch's deep-list tier (tail stream) runs under this batch's pack kernel and, for what is left of it,
 		// under the head of this batch's wave kernel: its few single-wave workgroups drain while the main tier pulls its work
 		// dynamically, which costs less than holding the wave kernel back for them (0.71 -> 0.66 ms per 1 M-read step).
-		HIP_TRY(hipEventRecord(sl.e5, ix->stream));               // the wave kernel's own start
+		HIP_TRY(hipEventRecord(sl.wave_begin, ix->stream));       // the wave kernel's own start
 		ix->cnt4_dirty = true;
 		const unsigned wgrid = (unsigned)std::min<uint64_t>((n_reads + 64 * W1_WPB - 1) / (64 * W1_WPB), (uint64_t)ix->wave_grid / W1_WPB);
-		if (big) vg_wave_kernel_big<W1_ECAP, W1_NCAP, W1_WPB><<<wgrid, 64 * W1_WPB, 0, ix->stream>>>(ix->d, sl.pk_kmer, sl.pk_meta, d_offsets, n_reads, nullptr, d_n_reads, sl.listA, &ctr[0], &ctr[4], ix->work_chunk, ix->d_stats, fin);
-		else if (sdx) vg_wave_kernel<false, W1_ECAP, W1_NCAP, W1_WPB, true><<<wgrid, 64 * W1_WPB, 0, ix->stream>>>(ix->d, sl.pk_kmer, sl.pk_meta, d_offsets, n_reads, nullptr, d_n_reads, sl.listA, &ctr[0], &ctr[4], ix->work_chunk, ix->d_stats, fin);
-		else vg_wave_kernel<STATS, W1_ECAP, W1_NCAP, W1_WPB><<<wgrid, 64 * W1_WPB, 0, ix->stream>>>(ix->d, sl.pk_kmer, sl.pk_meta, d_offsets, n_reads, nullptr, d_n_reads, sl.listA, &ctr[0], &ctr[4], ix->work_chunk, ix->d_stats, fin);
-		HIP_TRY(hipEventRecord(sl.e2, ix->stream));
-		ix->last_e2 = sl.e2;
+		launch_wave<W1_ECAP, W1_NCAP, W1_WPB>(big, sdx, stats, wgrid, ix->stream, ix->d, sl.pk_kmer.p, sl.pk_meta.p, d_offsets, n_reads, nullptr, d_n_reads, sl.listA.p, &ctr[0], &ctr[4], ix->work_chunk, ix->d_stats, fin);
+		HIP_TRY(hipEventRecord(sl.wave_end, ix->stream));
+		ix->last_wave_end = sl.wave_end;
 		// tail stream, the deep tier: the same kernel with deeper tables over the spill list (single-wave workgroups of 42 KB of LDS).
 		// ONE deep tier (r04; r03 had a 40 + 16 tier in front of it): it starts the moment the main tier's workgroups retire, while
 		// the CUs are free.  A tier enqueued behind another one found the NEXT batch's main-tier kernel on every CU and was only placed
 		// when that kernel's workgroups retired, 2.2 ms later -- the tail stream was busy for a whole step, the handle's batch slots
 		// waited for it and the main stream idled 0.2 ms per step (profiles/timeline_hg38_r04_three_tiers.txt).  With vote keys instead
 		// of context lists the deep tier has 0.005-0.3 % of the reads to do, not 10 %.
-		HIP_TRY(hipStreamWaitEvent(ix->tail, sl.e2, 0));
+		HIP_TRY(hipStreamWaitEvent(ix->tail, sl.wave_end, 0));
 		// The deep tier's grid: single-wave workgroups of 42 KB of LDS that can only be PLACED where a main-tier workgroup has retired --
 		// by then the next batch's kernels want the same CUs.  A full grid (3 per CU) for a list of 20 reads took 0.30 ms beside a
 		// 0.32 ms main kernel at chr22 scale (profiles/rocprof_summary_r05_chr22.txt).  The list's size is only known on the device, but
@@ -2294,33 +2368,26 @@ static int enqueue_batch(vg_index *ix, Slot &sl, const uint8_t *d_bases, const u
 		// wave's pull, and a floor), the full grid until a batch has been harvested.  A list longer than expected is still finished --
 		// the waves pull their work from a counter and their pulls grow with the list -- just by fewer waves.
 		unsigned w2grid = (unsigned)std::min<uint64_t>((n_reads + 63) / 64, (uint64_t)ix->cus * ix->w2_wpc);
-		if (ix->spill_known && !getenv("VG_W2_FULL_GRID")) w2grid = std::min<unsigned>(w2grid, std::max<unsigned>(32u, (2u * ix->spill_hint + ix->w2_chunk - 1) / ix->w2_chunk + 16u));
-		if (big) vg_wave_kernel_big<W3_ECAP, W3_NCAP, 1><<<w2grid, 64, 0, ix->tail>>>(ix->d, sl.pk_kmer, sl.pk_meta, d_offsets, 0, sl.listA, &ctr[0], sl.listB, &ctr[1], &ctr[5], ix->w2_chunk, ix->d_stats, nofuse);
-		else if (sdx) vg_wave_kernel<false, W3_ECAP, W3_NCAP, 1, true><<<w2grid, 64, 0, ix->tail>>>(ix->d, sl.pk_kmer, sl.pk_meta, d_offsets, 0, sl.listA, &ctr[0], sl.listB, &ctr[1], &ctr[5], ix->w2_chunk, ix->d_stats, nofuse);
-		else vg_wave_kernel<STATS, W3_ECAP, W3_NCAP, 1><<<w2grid, 64, 0, ix->tail>>>(ix->d, sl.pk_kmer, sl.pk_meta, d_offsets, 0, sl.listA, &ctr[0], sl.listB, &ctr[1], &ctr[5], ix->w2_chunk, ix->d_stats, nofuse);
+		if (ix->spill_known && !ix->w2_full_grid) w2grid = std::min<unsigned>(w2grid, std::max<unsigned>(32u, (2u * ix->spill_hint + ix->w2_chunk - 1) / ix->w2_chunk + 16u));
+		launch_wave<W3_ECAP, W3_NCAP, 1>(big, sdx, stats, w2grid, ix->tail, ix->d, sl.pk_kmer.p, sl.pk_meta.p, d_offsets, 0, sl.listA.p, &ctr[0], sl.listB.p, &ctr[1], &ctr[5], ix->w2_chunk, ix->d_stats, nofuse);
 		// what the deep tier leaves behind goes to the handle's late store (the lane machine runs over it once, at the next
 		// synchronisation); the slot only keeps what the store cannot take (listA is free again: the deep tier has consumed it)
 		sl.lt_late = ix->late.state != nullptr;
 		if (sl.lt_late) {
-			vg_late_collect<<<4, 256, 0, ix->tail>>>(ix->late, sl.pk_kmer, sl.pk_meta, d_offsets, sl.listB, &ctr[1], sl.listA, &ctr[6]);
-			ix->late_dirty = true; ix->late_stats = STATS;
+			vg_late_collect<<<4, 256, 0, ix->tail>>>(ix->late, sl.pk_kmer.p, sl.pk_meta.p, d_offsets, sl.listB.p, &ctr[1], sl.listA.p, &ctr[6]);
+			ix->late_dirty = true; ix->late_stats = stats;
 		}
-		HIP_TRY(hipEventRecord(sl.e4, ix->tail));
 	} else {
 		sl.lt_late = false;
-		if (produced_on && produced_on != ix->stream) {             // a batch gathered by the FASTQ framing on the ingest stream
-			HIP_TRY(hipEventRecord(sl.e_in, produced_on));
-			HIP_TRY(hipStreamWaitEvent(ix->stream, sl.e_in, 0));
-		}
-		HIP_TRY(hipMemsetAsync(ctr, 0, 64, ix->stream));
-		HIP_TRY(hipEventRecord(sl.e0, ix->stream));
-		HIP_TRY(hipEventRecord(sl.e1, ix->stream));
-		HIP_TRY(hipEventRecord(sl.e5, ix->stream));
-		vg_lane_kernel<STATS><<<g1, 256, 0, ix->stream>>>(ix->d, ix->mid.s, d_bases, d_quals, d_offsets, n_reads, nullptr, d_n_reads, sl.listB, &ctr[1], ix->d_stats, packed ? nullptr : &ctr[3], d_gate, sl.pk_kmer, sl.pk_meta, packed);
-		HIP_TRY(hipEventRecord(sl.e2, ix->stream));
-		HIP_TRY(hipStreamWaitEvent(ix->tail, sl.e2, 0));
-		HIP_TRY(hipEventRecord(sl.e4, ix->tail));
+		const unsigned g1 = (unsigned)std::min<uint64_t>((n_reads + 255) / 256, (uint64_t)ix->lane_grid_blocks);
+		if ((rc = begin_batch(sl, ix->stream, produced_on))) return rc;
+		HIP_TRY(hipEventRecord(sl.pack_end, ix->stream));
+		HIP_TRY(hipEventRecord(sl.wave_begin, ix->stream));
+		launch_lane(stats, g1, 256, ix->stream, ix->d, ix->mid.s, d_bases, d_quals, d_offsets, n_reads, nullptr, d_n_reads, sl.listB.p, &ctr[1], ix->d_stats, packed ? nullptr : &ctr[3], d_gate, sl.pk_kmer.p, sl.pk_meta.p, packed);
+		HIP_TRY(hipEventRecord(sl.wave_end, ix->stream));
+		HIP_TRY(hipStreamWaitEvent(ix->tail, sl.wave_end, 0));
 	}
+	HIP_TRY(hipEventRecord(sl.deep_end, ix->tail));
 	// ... and the generic lane machine with the deep HBM scratch for whatever is left -- LATER, and only if anything is (r05): the
 	// batch's counters come to the host behind its tiers, and harvest() launches the lane tier when they say that the deep tier left
 	// reads behind (0-5 reads per 8 M at hg38 scale, mostly none).  Through r04 the kernel was enqueued unconditionally: 64 workgroups
@@ -2329,15 +2396,18 @@ static int enqueue_batch(vg_index *ix, Slot &sl, const uint8_t *d_bases, const u
 	// (a workload whose batches DO leave reads for the lane tier -- long reads, tiny list capacities in the tests -- gets the kernel
 	// enqueued behind the deep tier as before, from the first batch that showed it on: a launch at harvest time would stall the host
 	// and the tail stream once per batch)
-	sl.lt_bases = d_bases; sl.lt_quals = d_quals; sl.lt_offsets = d_offsets; sl.lt_gate = d_gate; sl.lt_packed = packed; sl.lt_stats = STATS;
+	sl.lt_bases = d_bases; sl.lt_quals = d_quals; sl.lt_offsets = d_offsets; sl.lt_gate = d_gate; sl.lt_packed = packed; sl.lt_stats = stats;
 	sl.lt_enqueued = ix->lane_tier_seen;
 	// (the lane tiers, once a workload needs them, and the counter copies behind them go to `tail2`; a workload that never does keeps
 	// to the one tail stream -- chr22-scale steps are 3 % slower with the fourth stream in use: profiles/ab_tail_streams_r05.txt)
 	hipStream_t lt = ix->tail;
-	if (sl.lt_enqueued) { lt = ix->tail2; HIP_TRY(hipStreamWaitEvent(lt, sl.e4, 0)); }
-	if (sl.lt_enqueued) vg_lane_kernel<STATS><<<ix->big.s.nlanes / 64, 64, 0, lt>>>(ix->d, ix->big.s, d_bases, d_quals, d_offsets, 0, sl.lt_late ? sl.listA : sl.listB, sl.lt_late ? &ctr[6] : &ctr[1], sl.listC, &ctr[2], ix->d_stats, nullptr, d_gate, sl.pk_kmer, sl.pk_meta, packed);
-	HIP_TRY(hipMemcpyAsync(sl.h_ctr, ctr, 32, hipMemcpyDeviceToHost, lt));
-	HIP_TRY(hipEventRecord(sl.e3, lt));
+	if (sl.lt_enqueued) {
+		lt = ix->tail2;
+		HIP_TRY(hipStreamWaitEvent(lt, sl.deep_end, 0));
+		launch_lane(stats, ix->big.s.nlanes / 64, 64, lt, ix->d, ix->big.s, d_bases, d_quals, d_offsets, 0, sl.lt_late ? sl.listA.p : sl.listB.p, sl.lt_late ? &ctr[6] : &ctr[1], sl.listC.p, &ctr[2], ix->d_stats, nullptr, d_gate, sl.pk_kmer.p, sl.pk_meta.p, packed);
+	}
+	HIP_TRY(hipMemcpyAsync(sl.h_ctr.p, ctr, 32, hipMemcpyDeviceToHost, lt));
+	HIP_TRY(hipEventRecord(sl.batch_done, lt));
 	HIP_TRY(hipGetLastError());
 	sl.busy = true;
 	return VG_OK;
@@ -2353,6 +2423,16 @@ static int acquire_slot(vg_index *ix, Slot **out)
 	return VG_OK;
 }
 
+// The slot's packed-read buffers and spill lists for a batch of n_reads reads in n_chunks 32-base chunks.  The slot is idle
+// (acquire_slot harvested it), so its buffers may be replaced.
+static int size_slot(Slot &sl, uint64_t n_reads, uint64_t n_chunks)
+{
+	int rc;
+	if ((rc = sl.pk_kmer.reserve(n_chunks + 2, "packed reads"))) return rc;
+	if ((rc = sl.pk_meta.reserve(n_reads + 1, "packed reads' flag words"))) return rc;
+	return reserve_together({&sl.listA, &sl.listB, &sl.listC}, n_reads, "spill lists");
+}
+
 // produced_on: the stream whose earlier work fills the batch buffers (nullptr: they are complete already).
 // d_n_reads: the batch was framed on the device and only the device knows its size; n_reads and total_bases are then upper bounds.
 static int launch_batch(vg_index *ix, Slot &sl, const uint8_t *d_bases, const uint8_t *d_quals, const uint64_t *d_offsets, uint64_t n_reads, hipStream_t produced_on = nullptr,
@@ -2365,20 +2445,10 @@ static int launch_batch(vg_index *ix, Slot &sl, const uint8_t *d_bases, const ui
 	if (!d_n_reads) HIP_TRY(hipMemcpy(&total, d_offsets + n_reads, 8, hipMemcpyDeviceToHost));
 	if (total >= (1ull << 37)) return fail(VG_ETOOBIG, "a batch of 2^37 bases or more (the kernels address a batch's 32-base slots with 32 bits)");
 	if (total && (!d_bases || (!d_quals && !d_gate))) return fail(VG_EINVAL, "null argument: a batch with bases needs the base text and its quality strings or gate words");
-	const uint64_t need_k = (total >> 5) + 2, need_m = n_reads + 1;
-	// the slot is idle (acquire_slot harvested it), so its buffers may be replaced
-	if (need_k > sl.pk_kmer_cap) { if (sl.pk_kmer) (void)hipFree(sl.pk_kmer); sl.pk_kmer = nullptr; sl.pk_kmer_cap = 0; HIP_TRY(hipMalloc((void **)&sl.pk_kmer, need_k * 8)); sl.pk_kmer_cap = need_k; }
-	if (need_m > sl.pk_meta_cap) { if (sl.pk_meta) (void)hipFree(sl.pk_meta); sl.pk_meta = nullptr; sl.pk_meta_cap = 0; HIP_TRY(hipMalloc((void **)&sl.pk_meta, need_m * 8)); sl.pk_meta_cap = need_m; }
-	if (n_reads > sl.list_cap) {
-		uint32_t **lists[] = {&sl.listA, &sl.listB, &sl.listC};
-		sl.list_cap = 0;                                        // a failed allocation below must not leave the old size behind
-		for (uint32_t **l : lists) { if (*l) (void)hipFree(*l); *l = nullptr; }
-		for (uint32_t **l : lists) HIP_TRY(hipMalloc((void **)l, (size_t)n_reads * 4));
-		sl.list_cap = n_reads;
-	}
+	int rc = size_slot(sl, n_reads, total >> 5);
+	if (rc) return rc;
 	const uint64_t tb = d_n_reads ? 0ull : total;                // (a batch framed on the device: sizes are upper bounds, the mean length is unknown here)
-	return ix->stats_enabled ? enqueue_batch<true>(ix, sl, d_bases, d_quals, d_gate, d_offsets, n_reads, produced_on, d_n_reads, false, tb)
-	                         : enqueue_batch<false>(ix, sl, d_bases, d_quals, d_gate, d_offsets, n_reads, produced_on, d_n_reads, false, tb);
+	return enqueue_batch(ix, sl, ix->stats_enabled, d_bases, d_quals, d_gate, d_offsets, n_reads, produced_on, d_n_reads, false, tb);
 }
 
 extern "C" int vg_reads_process_device(vg_index *ix, const uint8_t *d_bases, const uint8_t *d_quals, const uint64_t *d_offsets, uint64_t n_reads)
@@ -2410,34 +2480,40 @@ static int launch_packed(vg_index *ix, Slot &sl, const uint64_t *kmers, const ui
 {
 	if (n_reads >= (1ull << 32) - (1ull << 24)) return fail(VG_EINVAL, "more than 2^32 - 2^24 reads in one batch");
 	if (n_chunks >= (1ull << 32)) return fail(VG_ETOOBIG, "a batch of 2^32 chunks or more");
-	const uint64_t need_k = n_chunks + 2, need_m = n_reads + 1;
-	if (need_k > sl.pk_kmer_cap) { if (sl.pk_kmer) (void)hipFree(sl.pk_kmer); sl.pk_kmer = nullptr; sl.pk_kmer_cap = 0; HIP_TRY(hipMalloc((void **)&sl.pk_kmer, need_k * 8)); sl.pk_kmer_cap = need_k; }
-	if (need_m > sl.pk_meta_cap) { if (sl.pk_meta) (void)hipFree(sl.pk_meta); sl.pk_meta = nullptr; sl.pk_meta_cap = 0; HIP_TRY(hipMalloc((void **)&sl.pk_meta, need_m * 8)); sl.pk_meta_cap = need_m; }
-	if (n_reads + 1 > sl.stage_reads) {
-		if (sl.st_offsets) (void)hipFree(sl.st_offsets);
-		sl.st_offsets = nullptr; sl.stage_reads = 0;
-		HIP_TRY(hipMalloc((void **)&sl.st_offsets, (n_reads + 1) * 8));
-		sl.stage_reads = n_reads + 1;
-	}
-	if (n_reads > sl.list_cap) {
-		uint32_t **lists[] = {&sl.listA, &sl.listB, &sl.listC};
-		sl.list_cap = 0;
-		for (uint32_t **l : lists) { if (*l) (void)hipFree(*l); *l = nullptr; }
-		for (uint32_t **l : lists) HIP_TRY(hipMalloc((void **)l, (size_t)n_reads * 4));
-		sl.list_cap = n_reads;
-	}
+	int rc;
+	if ((rc = size_slot(sl, n_reads, n_chunks)) || (rc = sl.st_offsets.reserve(n_reads + 1, "read offsets"))) return rc;
 	if (copy_on) {
 		// (hipMemcpyDefault: the source is page-locked host memory, or -- a read store's batch -- device memory)
-		if (n_chunks) HIP_TRY(hipMemcpyAsync(sl.pk_kmer, kmers, n_chunks * 8, hipMemcpyDefault, copy_on));
-		HIP_TRY(hipMemcpyAsync(sl.pk_meta, meta, n_reads * 8, hipMemcpyDefault, copy_on));
-		HIP_TRY(hipMemcpyAsync(sl.st_offsets, offsets, (n_reads + 1) * 8, hipMemcpyDefault, copy_on));
+		if (n_chunks) HIP_TRY(hipMemcpyAsync(sl.pk_kmer.p, kmers, n_chunks * 8, hipMemcpyDefault, copy_on));
+		HIP_TRY(hipMemcpyAsync(sl.pk_meta.p, meta, n_reads * 8, hipMemcpyDefault, copy_on));
+		HIP_TRY(hipMemcpyAsync(sl.st_offsets.p, offsets, (n_reads + 1) * 8, hipMemcpyDefault, copy_on));
 	} else {
-		if (n_chunks) HIP_TRY(hipMemcpy(sl.pk_kmer, kmers, n_chunks * 8, hipMemcpyHostToDevice));
-		HIP_TRY(hipMemcpy(sl.pk_meta, meta, n_reads * 8, hipMemcpyHostToDevice));
-		HIP_TRY(hipMemcpy(sl.st_offsets, offsets, (n_reads + 1) * 8, hipMemcpyHostToDevice));
+		if (n_chunks) HIP_TRY(hipMemcpy(sl.pk_kmer.p, kmers, n_chunks * 8, hipMemcpyHostToDevice));
+		HIP_TRY(hipMemcpy(sl.pk_meta.p, meta, n_reads * 8, hipMemcpyHostToDevice));
+		HIP_TRY(hipMemcpy(sl.st_offsets.p, offsets, (n_reads + 1) * 8, hipMemcpyHostToDevice));
 	}
-	return ix->stats_enabled ? enqueue_batch<true>(ix, sl, nullptr, nullptr, nullptr, sl.st_offsets, n_reads, copy_on, nullptr, true, 0)
-	                         : enqueue_batch<false>(ix, sl, nullptr, nullptr, nullptr, sl.st_offsets, n_reads, copy_on, nullptr, true, 0);
+	return enqueue_batch(ix, sl, ix->stats_enabled, nullptr, nullptr, nullptr, sl.st_offsets.p, n_reads, copy_on, nullptr, true, 0);
+}
+
+// The check of a packed batch that a caller hands in (vg_reads_submit_packed*, vg_read_store_push): monotone chunk offsets from 0,
+// at most 31 chunks per read, no reserved bit in a flag word.  Gives the batch's chunk count and its reads with a character other
+// than ACGTN.
+static int check_packed(const uint64_t *kmers, const uint64_t *meta, const uint64_t *chunk_offsets, uint64_t n_reads, uint64_t &n_chunks, uint64_t &invalid)
+{
+	if (chunk_offsets[0] != 0) return fail(VG_EINVAL, "chunk_offsets[0] must be 0");
+	uint64_t n_invalid = 0, bad = 0;
+	for (uint64_t i = 0; i < n_reads; i++) {                     // (branch-free: one pass over three arrays, the compiler vectorises it)
+		const uint64_t d = chunk_offsets[i + 1] - chunk_offsets[i];
+		bad |= (chunk_offsets[i + 1] < chunk_offsets[i] ? 1ull : 0ull) | (d > 31 ? 2ull : 0ull) | ((meta[i] & 0x3FFFFFFF00000000ull) ? 4ull : 0ull);
+		n_invalid += meta[i] >> 63;
+	}
+	if (bad & 1ull) return fail(VG_EINVAL, "chunk offsets not monotone");
+	if (bad & 2ull) return fail(VG_EBADREAD, "a packed read of more than 31 chunks (a FASTQ line the reference can read holds at most 1022 bases, qv.cc:700)");
+	if (bad & 4ull) return fail(VG_EINVAL, "a packed read's flag word has reserved bits set (bits 0-31: gate bits, 62: N inside the read, 63: another character; nothing else)");
+	n_chunks = chunk_offsets[n_reads];
+	invalid = n_invalid;
+	if (n_chunks && !kmers) return fail(VG_EINVAL, "null argument");
+	return VG_OK;
 }
 
 // pinned: the caller's arrays are page-locked and stay untouched until vg_sync -- the copies are asynchronous (ingest stream) and
@@ -2446,34 +2522,16 @@ static int launch_packed(vg_index *ix, Slot &sl, const uint64_t *kmers, const ui
 static int submit_packed_impl(vg_index *ix, const uint64_t *kmers, const uint64_t *meta, const uint64_t *chunk_offsets, uint64_t n_reads, bool pinned)
 {
 	HIP_TRY(hipSetDevice(ix->device));
-	if (chunk_offsets[0] != 0) return fail(VG_EINVAL, "chunk_offsets[0] must be 0");
-	uint64_t invalid = 0, bad = 0;
-	for (uint64_t i = 0; i < n_reads; i++) {                     // (branch-free: one pass over three arrays, the compiler vectorises it)
-		const uint64_t d = chunk_offsets[i + 1] - chunk_offsets[i];
-		bad |= (chunk_offsets[i + 1] < chunk_offsets[i] ? 1ull : 0ull) | (d > 31 ? 2ull : 0ull) | ((meta[i] & 0x3FFFFFFF00000000ull) ? 4ull : 0ull);
-		invalid += meta[i] >> 63;
-	}
-	if (bad & 1ull) return fail(VG_EINVAL, "chunk offsets not monotone");
-	if (bad & 2ull) return fail(VG_EBADREAD, "a packed read of more than 31 chunks (a FASTQ line the reference can read holds at most 1022 bases, qv.cc:700)");
-	if (bad & 4ull) return fail(VG_EINVAL, "a packed read's flag word has reserved bits set (bits 0-31: gate bits, 62: N inside the read, 63: another character; nothing else)");
-	const uint64_t n_chunks = chunk_offsets[n_reads];
-	if (n_chunks && !kmers) return fail(VG_EINVAL, "null argument");
-	Slot *sl = nullptr;
-	int rc = acquire_slot(ix, &sl);
+	uint64_t n_chunks = 0, invalid = 0;
+	int rc = check_packed(kmers, meta, chunk_offsets, n_reads, n_chunks, invalid);
 	if (rc) return rc;
+	Slot *sl = nullptr;
+	if ((rc = acquire_slot(ix, &sl))) return rc;
 	// the flat-batch offsets of the trimmed reads (32 x chunks before each), in the slot's page-locked staging
-	if (n_reads + 1 > sl->hp_reads_cap) {
-		if (sl->hp_meta) (void)hipHostFree(sl->hp_meta);
-		if (sl->hp_offsets) (void)hipHostFree(sl->hp_offsets);
-		sl->hp_meta = sl->hp_offsets = nullptr; sl->hp_reads_cap = 0;
-		const uint64_t cap = (n_reads + 1) * 5 / 4;
-		if (hipHostMalloc((void **)&sl->hp_meta, cap * 8, hipHostMallocDefault) != hipSuccess || hipHostMalloc((void **)&sl->hp_offsets, cap * 8, hipHostMallocDefault) != hipSuccess)
-			return fail(VG_ENOMEM, "hipHostMalloc(packed staging) failed");
-		sl->hp_reads_cap = cap;
-	}
-	for (uint64_t i = 0; i <= n_reads; i++) sl->hp_offsets[i] = 32 * chunk_offsets[i];
-	hipStream_t is = ix->ingest_stream ? ix->ingest : ix->stream;
-	rc = launch_packed(ix, *sl, kmers, meta, sl->hp_offsets, n_reads, n_chunks, is);
+	if (n_reads + 1 > sl->hp_offsets.cap && (rc = reserve_together({&sl->hp_meta, &sl->hp_offsets}, (n_reads + 1) * 5 / 4, "packed staging"))) return rc;
+	for (uint64_t i = 0; i <= n_reads; i++) sl->hp_offsets.p[i] = 32 * chunk_offsets[i];
+	hipStream_t is = ix->ingest_or_main();
+	rc = launch_packed(ix, *sl, kmers, meta, sl->hp_offsets.p, n_reads, n_chunks, is);
 	if (rc == VG_OK && !pinned) HIP_TRY(hipStreamSynchronize(is));          // the caller's arrays are free again
 	if (rc == VG_OK) ix->host_invalid += invalid;
 	return rc;
@@ -2551,18 +2609,9 @@ extern "C" int vg_read_store_push(vg_read_store *rs, const uint64_t *kmers, cons
 		HIP_TRY(hipSetDevice(rs->device));
 		HIP_TRY(hipStreamSynchronize(rs->stream));               // the arrays of the push before this one are free again
 		if (n_reads == 0) return VG_OK;
-		if (chunk_offsets[0] != 0) return fail(VG_EINVAL, "chunk_offsets[0] must be 0");
-		uint64_t invalid = 0, bad = 0;
-		for (uint64_t i = 0; i < n_reads; i++) {
-			const uint64_t d = chunk_offsets[i + 1] - chunk_offsets[i];
-			bad |= (chunk_offsets[i + 1] < chunk_offsets[i] ? 1ull : 0ull) | (d > 31 ? 2ull : 0ull) | ((meta[i] & 0x3FFFFFFF00000000ull) ? 4ull : 0ull);
-			invalid += meta[i] >> 63;
-		}
-		if (bad & 1ull) return fail(VG_EINVAL, "chunk offsets not monotone");
-		if (bad & 2ull) return fail(VG_EBADREAD, "a packed read of more than 31 chunks (a FASTQ line the reference can read holds at most 1022 bases, qv.cc:700)");
-		if (bad & 4ull) return fail(VG_EINVAL, "a packed read's flag word has reserved bits set (bits 0-31: gate bits, 62: N inside the read, 63: another character; nothing else)");
-		const uint64_t n_chunks = chunk_offsets[n_reads];
-		if (n_chunks && !kmers) return fail(VG_EINVAL, "null argument");
+		uint64_t n_chunks = 0, invalid = 0;
+		const int rc = check_packed(kmers, meta, chunk_offsets, n_reads, n_chunks, invalid);
+		if (rc) return rc;
 		if (n_reads >= (1ull << 32) - (1ull << 24) || n_chunks >= (1ull << 32)) return fail(VG_ETOOBIG, "a batch of 2^32 chunks or more");
 		auto up = [](uint64_t b) { return (b + 255) & ~255ull; };
 		const uint64_t need = up((n_chunks + 2) * 8) + up(n_reads * 8) + up((n_reads + 1) * 8);
@@ -2590,7 +2639,7 @@ extern "C" int vg_reads_submit_store(vg_index *ix, vg_read_store *rs)
 	return guarded([&]() -> int {
 		HIP_TRY(hipSetDevice(ix->device));
 		HIP_TRY(hipStreamSynchronize(rs->stream));               // everything pushed is in device memory
-		hipStream_t is = ix->ingest_stream ? ix->ingest : ix->stream;
+		hipStream_t is = ix->ingest_or_main();
 		for (const StoredBatch &b : rs->batches) {
 			Slot *sl = nullptr;
 			int rc = acquire_slot(ix, &sl);
@@ -2623,47 +2672,18 @@ static int submit_impl(vg_index *ix, const uint8_t *bases, const uint8_t *quals,
 	int rc = acquire_slot(ix, &slp);
 	if (rc) return rc;
 	Slot &sl = *slp;
-	if (total + 64 > sl.stage_bytes) {
-		if (sl.st_bases) (void)hipFree(sl.st_bases);
-		sl.st_bases = nullptr; sl.stage_bytes = 0;
-		HIP_TRY(hipMalloc((void **)&sl.st_bases, total + 64));
-		sl.stage_bytes = total + 64;
-	}
-	if (total + 64 > sl.stage_quals_bytes) {
-		if (sl.st_quals) (void)hipFree(sl.st_quals);
-		sl.st_quals = nullptr; sl.stage_quals_bytes = 0;
-		HIP_TRY(hipMalloc((void **)&sl.st_quals, total + 64));
-		sl.stage_quals_bytes = total + 64;
-	}
-	if (n_reads + 1 > sl.stage_reads) {
-		if (sl.st_offsets) (void)hipFree(sl.st_offsets);
-		sl.st_offsets = nullptr; sl.stage_reads = 0;
-		HIP_TRY(hipMalloc((void **)&sl.st_offsets, (n_reads + 1) * 8));
-		sl.stage_reads = n_reads + 1;
-	}
+	if ((rc = sl.st_bases.reserve(total + 64, "base text")) || (rc = sl.st_quals.reserve(total + 64, "quality strings")) || (rc = sl.st_offsets.reserve(n_reads + 1, "read offsets"))) return rc;
 	std::vector<uint64_t> rel;
 	const uint64_t *off = offsets;
 	if (base0) { rel.resize(n_reads + 1); for (uint64_t i = 0; i <= n_reads; i++) rel[i] = offsets[i] - base0; off = rel.data(); }
 	// plain (blocking) copies: when they return the caller's buffers are free again; kernels of earlier batches keep running
-	HIP_TRY(hipMemcpy(sl.st_bases, bases + base0, total, hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(sl.st_quals, quals + base0, total, hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(sl.st_offsets, off, (n_reads + 1) * 8, hipMemcpyHostToDevice));
-	return launch_batch(ix, sl, sl.st_bases, sl.st_quals, sl.st_offsets, n_reads);
+	HIP_TRY(hipMemcpy(sl.st_bases.p, bases + base0, total, hipMemcpyHostToDevice));
+	HIP_TRY(hipMemcpy(sl.st_quals.p, quals + base0, total, hipMemcpyHostToDevice));
+	HIP_TRY(hipMemcpy(sl.st_offsets.p, off, (n_reads + 1) * 8, hipMemcpyHostToDevice));
+	return launch_batch(ix, sl, sl.st_bases.p, sl.st_quals.p, sl.st_offsets.p, n_reads);
 }
 
 // ---- FASTQ text in, framed and processed on the device (replaces the four fgets() + strlen of qv.cc:760-784) ---------------
-template <class T>
-static int grow_dev(T **p, uint64_t &cap, uint64_t need)
-{
-	if (need <= cap) return VG_OK;
-	if (*p) (void)hipFree(*p);
-	*p = nullptr; cap = 0;
-	hipError_t e = hipMalloc((void **)p, (size_t)need * sizeof(T));
-	if (e != hipSuccess) return fail(VG_ENOMEM, "hipMalloc(FASTQ staging): %s", hipGetErrorString(e));
-	cap = need;
-	return VG_OK;
-}
-
 // CPUs this process may actually use: the hardware threads, capped by a cgroup CPU quota (cpu.max: "<quota> <period>" -- the GPU
 // boxes of this pool give a container 16 CPUs' worth of time on a 256-thread host; threads beyond the quota only take time from
 // each other, and a spinning one takes it from the working ones)
@@ -2721,26 +2741,12 @@ static int push_packed(vg_index *ix, const uint8_t *text, uint64_t nbytes)
 	if (rc) return rc;
 	Slot &sl = *slp;
 	const uint64_t need_r = vgp::Packer::reads_cap(nbytes) + 1, need_k = vgp::Packer::kmers_cap(nbytes);
-	if (need_k > sl.hp_kmers_cap) {
-		if (sl.hp_kmers) (void)hipHostFree(sl.hp_kmers);
-		sl.hp_kmers = nullptr; sl.hp_kmers_cap = 0;
-		if (hipHostMalloc((void **)&sl.hp_kmers, need_k * 8, hipHostMallocDefault) != hipSuccess) return fail(VG_ENOMEM, "hipHostMalloc(packed staging) failed");
-		sl.hp_kmers_cap = need_k;
-	}
-	if (need_r > sl.hp_reads_cap) {
-		if (sl.hp_meta) (void)hipHostFree(sl.hp_meta);
-		if (sl.hp_offsets) (void)hipHostFree(sl.hp_offsets);
-		sl.hp_meta = sl.hp_offsets = nullptr; sl.hp_reads_cap = 0;
-		if (hipHostMalloc((void **)&sl.hp_meta, need_r * 8, hipHostMallocDefault) != hipSuccess || hipHostMalloc((void **)&sl.hp_offsets, need_r * 8, hipHostMallocDefault) != hipSuccess)
-			return fail(VG_ENOMEM, "hipHostMalloc(packed staging) failed");
-		sl.hp_reads_cap = need_r;
-	}
+	if ((rc = sl.hp_kmers.reserve(need_k, "packed staging")) || (rc = reserve_together({&sl.hp_meta, &sl.hp_offsets}, need_r, "packed staging"))) return rc;
 	vgp::Staging st;
-	st.kmers = sl.hp_kmers; st.kmers_cap = sl.hp_kmers_cap; st.meta = sl.hp_meta; st.offsets = sl.hp_offsets; st.reads_cap = sl.hp_reads_cap;
+	st.kmers = sl.hp_kmers.p; st.kmers_cap = sl.hp_kmers.cap; st.meta = sl.hp_meta.p; st.offsets = sl.hp_offsets.p; st.reads_cap = sl.hp_offsets.cap;
 	const vgp::ChunkResult r = ix->packer->push(text, nbytes, st);
 	if (r.n_reads == 0) return VG_OK;                            // (a refused block poisons the stream; the records framed before it are still this batch)
-	hipStream_t is = ix->ingest_stream ? ix->ingest : ix->stream;
-	rc = launch_packed(ix, sl, sl.hp_kmers, sl.hp_meta, sl.hp_offsets, r.n_reads, r.n_chunks, is);
+	rc = launch_packed(ix, sl, sl.hp_kmers.p, sl.hp_meta.p, sl.hp_offsets.p, r.n_reads, r.n_chunks, ix->ingest_or_main());
 	if (rc == VG_OK) ix->host_invalid += r.n_invalid;
 	return rc;
 }
@@ -2750,8 +2756,7 @@ extern "C" int vg_fastq_stream_begin(vg_index *ix)
 	if (!ix) return fail(VG_EINVAL, "null argument");
 	ix->fq_packed = false;
 	HIP_TRY(hipSetDevice(ix->device));
-	hipStream_t is = ix->ingest_stream ? ix->ingest : ix->stream;
-	HIP_TRY(hipMemsetAsync(ix->d_fq, 0, sizeof(FqStream), is));
+	HIP_TRY(hipMemsetAsync(ix->d_fq, 0, sizeof(FqStream), ix->ingest_or_main()));
 	ix->fq_open = true; ix->fq_prev_slot = -1;
 	return VG_OK;
 }
@@ -2771,7 +2776,7 @@ extern "C" int vg_fastq_stream_push(vg_index *ix, const uint8_t *text, uint64_t 
 	int rc = acquire_slot(ix, &slp);
 	if (rc) return rc;
 	Slot &sl = *slp;
-	hipStream_t is = ix->ingest_stream ? ix->ingest : ix->stream;
+	hipStream_t is = ix->ingest_or_main();
 	// the chunk after this slot's last one copied the tail of its text on the ingest stream: that must have happened before
 	// the text is overwritten (the slot's own batch being finished does not imply it)
 	if (sl.fq_tail_wanted) { HIP_TRY(hipEventSynchronize(sl.e_fq)); sl.fq_tail_wanted = false; }
@@ -2779,58 +2784,43 @@ extern "C" int vg_fastq_stream_push(vg_index *ix, const uint8_t *text, uint64_t 
 	const uint64_t span = (uint64_t)FQ_CARRY + nbytes;
 	const uint64_t n_tiles = (span + FQ_TILE - 1) / FQ_TILE;
 	const uint64_t cap_lines = span / 8 + 16, cap_rec = cap_lines / 4 + 1;
-	if ((rc = grow_dev(&sl.fq_text, sl.fq_text_cap, n_tiles * FQ_TILE + 64))) return rc;
-	if ((rc = grow_dev(&sl.fq_tiles, sl.fq_tiles_cap, n_tiles + 2))) return rc;
-	if ((rc = grow_dev(&sl.fq_lines, sl.fq_lines_cap, cap_lines + 2))) return rc;
-	if (!sl.fq_chunk) { uint64_t one = 0; if ((rc = grow_dev(&sl.fq_chunk, one, 1))) return rc; }
-	if (cap_rec + 2 > sl.stage_reads) {
-		if (sl.st_offsets) (void)hipFree(sl.st_offsets);
-		sl.st_offsets = nullptr; sl.stage_reads = 0;
-		HIP_TRY(hipMalloc((void **)&sl.st_offsets, (cap_rec + 2) * 8));
-		sl.stage_reads = cap_rec + 2;
-	}
-	if (span + 64 > sl.stage_bytes) {                               // the bases of a chunk are shorter than its text
-		if (sl.st_bases) (void)hipFree(sl.st_bases);
-		sl.st_bases = nullptr; sl.stage_bytes = 0;
-		HIP_TRY(hipMalloc((void **)&sl.st_bases, span + 64));
-		sl.stage_bytes = span + 64;
-	}
-	if ((rc = grow_dev(&sl.st_gate, sl.st_gate_cap, cap_rec + 2))) return rc;
-	{
-		uint8_t *tmp = (uint8_t *)sl.fq_tmp;
-		const uint64_t need = vg_dev_scan_temp_bytes(n_tiles + 1, cap_rec + 1);
-		if ((rc = grow_dev(&tmp, sl.fq_tmp_cap, need))) { sl.fq_tmp = tmp; return rc; }
-		sl.fq_tmp = tmp;
-	}
-	HIP_TRY(hipMemcpy(sl.fq_text + FQ_CARRY, text, nbytes, hipMemcpyHostToDevice));
+	if ((rc = sl.fq_text.reserve(n_tiles * FQ_TILE + 64, "FASTQ text"))) return rc;
+	if ((rc = sl.fq_tiles.reserve(n_tiles + 2, "FASTQ tiles"))) return rc;
+	if ((rc = sl.fq_lines.reserve(cap_lines + 2, "FASTQ lines"))) return rc;
+	if ((rc = sl.fq_chunk.reserve(1, "FASTQ chunk"))) return rc;
+	if ((rc = sl.st_offsets.reserve(cap_rec + 2, "read offsets"))) return rc;
+	if ((rc = sl.st_bases.reserve(span + 64, "base text"))) return rc;              // the bases of a chunk are shorter than its text
+	if ((rc = sl.st_gate.reserve(cap_rec + 2, "gate words"))) return rc;
+	if ((rc = sl.fq_tmp.reserve(vg_dev_scan_temp_bytes(n_tiles + 1, cap_rec + 1), "scan scratch"))) return rc;
+	HIP_TRY(hipMemcpy(sl.fq_text.p + FQ_CARRY, text, nbytes, hipMemcpyHostToDevice));
 	sl.fq_text_len = nbytes;
 	const uint8_t *prev_end = nullptr;
-	if (ix->fq_prev_slot >= 0) { const Slot &pv = ix->slot[ix->fq_prev_slot]; prev_end = pv.fq_text + FQ_CARRY + pv.fq_text_len; }
-	vg_fqs_prepare<<<1, 256, 0, is>>>(ix->d_fq, sl.fq_chunk, prev_end, sl.fq_text, (uint32_t)nbytes);
+	if (ix->fq_prev_slot >= 0) { const Slot &pv = ix->slot[ix->fq_prev_slot]; prev_end = pv.fq_text.p + FQ_CARRY + pv.fq_text_len; }
+	vg_fqs_prepare<<<1, 256, 0, is>>>(ix->d_fq, sl.fq_chunk.p, prev_end, sl.fq_text.p, (uint32_t)nbytes);
 	if (ix->fq_prev_slot >= 0) { Slot &pv = ix->slot[ix->fq_prev_slot]; HIP_TRY(hipEventRecord(pv.e_fq, is)); pv.fq_tail_wanted = true; }
-	vg_fq_count_newlines<<<(unsigned)n_tiles, 256, 0, is>>>(sl.fq_text, sl.fq_chunk, sl.fq_tiles);
-	HIP_TRY(hipMemsetAsync(sl.fq_tiles + n_tiles, 0, 4, is));
+	vg_fq_count_newlines<<<(unsigned)n_tiles, 256, 0, is>>>(sl.fq_text.p, sl.fq_chunk.p, sl.fq_tiles.p);
+	HIP_TRY(hipMemsetAsync(sl.fq_tiles.p + n_tiles, 0, 4, is));
 	HIP_TRY(hipGetLastError());
-	int se = vg_dev_exclusive_scan_u32(sl.fq_tiles, sl.fq_tiles, n_tiles + 1, is, sl.fq_tmp, sl.fq_tmp_cap);
+	int se = vg_dev_exclusive_scan_u32(sl.fq_tiles.p, sl.fq_tiles.p, n_tiles + 1, is, sl.fq_tmp.p, sl.fq_tmp.cap);
 	if (se != 0) return fail(VG_ENODEV, "device scan failed: %s", hipGetErrorString((hipError_t)se));
-	const uint32_t *d_n_lines = sl.fq_tiles + n_tiles;
-	vg_fq_line_starts<<<(unsigned)n_tiles, 256, 0, is>>>(sl.fq_text, sl.fq_chunk, sl.fq_tiles, sl.fq_lines, (uint32_t)cap_lines);
-	vg_fq_record_lengths<<<1024, 256, 0, is>>>(sl.fq_lines, d_n_lines, sl.fq_chunk, sl.st_offsets, (uint32_t)cap_rec, (uint32_t)cap_lines);
+	const uint32_t *d_n_lines = sl.fq_tiles.p + n_tiles;
+	vg_fq_line_starts<<<(unsigned)n_tiles, 256, 0, is>>>(sl.fq_text.p, sl.fq_chunk.p, sl.fq_tiles.p, sl.fq_lines.p, (uint32_t)cap_lines);
+	vg_fq_record_lengths<<<1024, 256, 0, is>>>(sl.fq_lines.p, d_n_lines, sl.fq_chunk.p, sl.st_offsets.p, (uint32_t)cap_rec, (uint32_t)cap_lines);
 	HIP_TRY(hipGetLastError());
-	se = vg_dev_exclusive_scan_u64(sl.st_offsets, sl.st_offsets, cap_rec + 1, is, sl.fq_tmp, sl.fq_tmp_cap);
+	se = vg_dev_exclusive_scan_u64(sl.st_offsets.p, sl.st_offsets.p, cap_rec + 1, is, sl.fq_tmp.p, sl.fq_tmp.cap);
 	if (se != 0) return fail(VG_ENODEV, "device scan failed: %s", hipGetErrorString((hipError_t)se));
-	vg_fqs_finish<<<1, 1, 0, is>>>(ix->d_fq, sl.fq_chunk, d_n_lines, sl.fq_lines, sl.st_offsets, (uint32_t)cap_rec);
-	vg_fq_gather<<<(unsigned)std::min<uint64_t>((cap_rec + 3) / 4, (uint64_t)ix->cus * 32), 256, 0, is>>>(sl.fq_text, sl.fq_lines, sl.st_offsets, sl.fq_chunk, sl.st_bases, sl.st_gate);
+	vg_fqs_finish<<<1, 1, 0, is>>>(ix->d_fq, sl.fq_chunk.p, d_n_lines, sl.fq_lines.p, sl.st_offsets.p, (uint32_t)cap_rec);
+	vg_fq_gather<<<(unsigned)std::min<uint64_t>((cap_rec + 3) / 4, (uint64_t)ix->cus * 32), 256, 0, is>>>(sl.fq_text.p, sl.fq_lines.p, sl.st_offsets.p, sl.fq_chunk.p, sl.st_bases.p, sl.st_gate.p);
 	HIP_TRY(hipGetLastError());
 	ix->fq_prev_slot = slot_no;
-	return launch_batch(ix, sl, sl.st_bases, nullptr, sl.st_offsets, cap_rec, is, &sl.fq_chunk->n_reads, span, sl.st_gate);
+	return launch_batch(ix, sl, sl.st_bases.p, nullptr, sl.st_offsets.p, cap_rec, is, &sl.fq_chunk.p->n_reads, span, sl.st_gate.p);
 }
 
 static int fq_collect(vg_index *ix, bool drain, uint64_t *n_records, uint64_t *consumed, uint64_t *last_record_start, int *refused)
 {
 	HIP_TRY(hipSetDevice(ix->device));
 	if (drain) { int rc = finish_pending(ix); if (rc) return rc; }
-	else HIP_TRY(hipStreamSynchronize(ix->ingest_stream ? ix->ingest : ix->stream));       // framing only: the read loop runs on
+	else HIP_TRY(hipStreamSynchronize(ix->ingest_or_main()));       // framing only: the read loop runs on
 	FqStream h;
 	HIP_TRY(hipMemcpy(&h, ix->d_fq, sizeof h, hipMemcpyDeviceToHost));
 	if (n_records) *n_records = h.records;
