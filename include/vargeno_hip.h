@@ -261,6 +261,35 @@ int  vg_sites_fetch(vg_index *ix, uint32_t *pos, uint8_t *ref_base, uint8_t *alt
 int  vg_counts_fetch(vg_index *ix, uint8_t *ref_cnt, uint8_t *alt_cnt);    /* clamped at 63     */
 int  vg_counts_reset(vg_index *ix);
 
+/* Sample planes: several samples against ONE resident index.  The reference genotypes one sample per process: the counters it hands
+ * to the caller (qv.cc:1573-1626) are the only per-sample state of its read loop, the dictionaries are read-only.  A PLANE is that
+ * state for one sample on the device: the exact sums (8 bytes per SNP site) and the wave kernel's base-indexed counters (16 bytes
+ * per site, + 16): 24 * vg_num_sites + 16 bytes of HBM per plane -- 240 MB at 10 M sites --, taken outside the handle's plan and
+ * counted by vg_index_device_bytes.  Everything else (tables, views, scratch) is shared.  A handle is born with plane 0; a caller
+ * that never reserves sees exactly the behaviour of a handle without planes.
+ *   vg_samples_reserve      grows the handle to n_samples planes (1 .. 65 535; a smaller number than it has: VG_EINVAL).  Existing
+ *                           planes keep their contents, new ones start at zero.  VG_ENOMEM leaves the handle as it was.  Implies vg_sync
+ *   vg_num_samples          planes of the handle (1 for a fresh one)
+ *   vg_sample_select        no synchronisation, no device work: may be called between any two submits (out of range: VG_EINVAL).
+ *                           Every read-taking call -- vg_reads_submit*, vg_reads_process_device*, vg_reads_submit_store,
+ *                           vg_fastq_submit -- counts its batches into the sample selected AT THE CALL, whatever is selected when
+ *                           they run; batches of different samples are in flight together.  A FASTQ stream belongs to the sample
+ *                           selected at vg_fastq_stream_begin*: selecting another one while it is open does not move it.
+ *                           vg_counts_fetch, vg_counts_device_ptr, vg_counts_allreduce and vg_counts_allreduce_devices act on the
+ *                           selected sample (the last one wants the same selection on all handles: VG_EINVAL otherwise)
+ *   vg_sample_selected      the sample selected now (0 for a fresh handle)
+ *   vg_sample_reset         zeroes ONE sample's counters and its invalid-read count (implies vg_sync).  vg_counts_reset stays what
+ *                           it was: all counters -- now of all planes -- and the handle-wide event counts
+ *   vg_sample_invalid_reads reads of the sample that the reference would have aborted on (a character outside ACGTNacgtn,
+ *                           util.c:103), since open / vg_counts_reset / vg_sample_reset of it.  Implies vg_sync
+ * vg_stats stays handle-wide: the sum over the samples since open / vg_counts_reset. */
+int      vg_samples_reserve(vg_index *ix, uint32_t n_samples);
+uint32_t vg_num_samples(const vg_index *ix);
+int      vg_sample_select(vg_index *ix, uint32_t sample);
+uint32_t vg_sample_selected(const vg_index *ix);
+int      vg_sample_reset(vg_index *ix, uint32_t sample);
+int      vg_sample_invalid_reads(vg_index *ix, uint32_t sample, uint64_t *out);
+
 /* Device pointer to the raw u32 counter array, length 2 * vg_num_sites: [2*s] = ref, [2*s+1] = alt
  * (the call first drains the batches in flight).
  * This is the ONE buffer that crosses GPUs: sum it over ranks (RCCL all-reduce over xGMI) before

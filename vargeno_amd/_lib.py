@@ -21,7 +21,8 @@ SYMBOLS = ["vg_last_error", "vg_build_id", "vg_device_count", "vg_device_memory"
            "vg_index_device_bytes", "vg_index_views", "vg_reads_submit", "vg_reads_process_device", "vg_reads_process_device_gated", "vg_reads_submit_packed", "vg_reads_submit_packed_async", "vg_read_store_create", "vg_read_store_push", "vg_read_store_flush", "vg_read_store_reads", "vg_read_store_bytes_used", "vg_reads_submit_store", "vg_read_store_destroy", "vg_fastq_submit", "vg_fastq_stream_begin", "vg_fastq_stream_begin_packed", "vg_fastq_stream_push", "vg_fastq_stream_end",
            "vg_packer_create", "vg_packer_destroy", "vg_packer_begin", "vg_packer_reads_cap", "vg_packer_kmers_cap", "vg_packer_push", "vg_packer_end", "vg_sync", "vg_stats_get",
            "vg_set_stats", "vg_timing_get", "vg_num_sites", "vg_sites_fetch", "vg_counts_fetch", "vg_counts_reset",
-           "vg_counts_device_ptr", "vg_counts_allreduce", "vg_counts_allreduce_devices"]
+           "vg_counts_device_ptr", "vg_counts_allreduce", "vg_counts_allreduce_devices",
+           "vg_samples_reserve", "vg_num_samples", "vg_sample_select", "vg_sample_selected", "vg_sample_reset", "vg_sample_invalid_reads"]
 
 
 class VgStats(C.Structure):
@@ -142,6 +143,18 @@ def lib():
         L.vg_counts_device_ptr.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]
         L.vg_counts_allreduce.argtypes = [vp, vp]
         L.vg_counts_allreduce_devices.argtypes = [C.POINTER(vp), C.c_int]
+        try:
+            L.vg_samples_reserve.argtypes = [vp, C.c_uint32]
+            L.vg_num_samples.argtypes = [vp]
+            L.vg_num_samples.restype = C.c_uint32
+            L.vg_sample_select.argtypes = [vp, C.c_uint32]
+            L.vg_sample_selected.argtypes = [vp]
+            L.vg_sample_selected.restype = C.c_uint32
+            L.vg_sample_reset.argtypes = [vp, C.c_uint32]
+            L.vg_sample_invalid_reads.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint64)]
+        except AttributeError:
+            if not os.environ.get("VARGENO_HIP_LIB"):                   # (an older build loaded for an A/B run has no sample planes)
+                raise
         # The library is a build product that travels next to its sources (not in git): refuse a stale one.  Its build id is the
         # sha256 of the sources it was compiled from (csrc/Makefile); VARGENO_HIP_LIB (A/B variants) opts out.
         if not os.environ.get("VARGENO_HIP_LIB"):

@@ -218,9 +218,44 @@ class GenoIndex:
         check(lib().vg_sites_fetch(self._h, _ptr(pos), *[_ptr(x) for x in u8]))
         return dict(pos=pos, ref_base=u8[0], alt_base=u8[1], ref_freq=u8[2], alt_freq=u8[3])
 
-    def counts(self, copy=True):
-        """Clamped counters (ref, alt).  copy=False: views of a page-locked buffer that the next call overwrites (the device-to-host
+    # ---- sample planes: several samples against one resident index (vg_samples_reserve ...) ----------------------
+    def reserve_samples(self, n):
+        """Grow the handle to n sample planes (24 bytes of device memory per site each); existing planes keep their counts."""
+        check(lib().vg_samples_reserve(self._h, int(n)))
+
+    @property
+    def num_samples(self):
+        return int(lib().vg_num_samples(self._h))
+
+    @property
+    def selected(self):
+        return int(lib().vg_sample_selected(self._h))
+
+    def select(self, s):
+        """The sample that the batches submitted from now on count into, and that counts() / the all-reduces act on.  No
+        synchronisation: batches of different samples are in flight together."""
+        check(lib().vg_sample_select(self._h, int(s)))
+
+    def reset_sample(self, s):
+        check(lib().vg_sample_reset(self._h, int(s)))
+
+    def invalid_reads(self, s):
+        """Reads of sample s that the reference would have aborted on."""
+        n = C.c_uint64()
+        check(lib().vg_sample_invalid_reads(self._h, int(s), C.byref(n)))
+        return int(n.value)
+
+    def counts(self, copy=True, sample=None):
+        """Clamped counters (ref, alt) of the selected sample, or of `sample` (the selection is restored).  copy=False: views of a
+        page-locked buffer that the next call overwrites (the device-to-host
         copy then runs at link speed instead of through the runtime's pageable staging: bench.py's timed fetch)."""
+        if sample is not None:
+            before = self.selected
+            self.select(sample)
+            try:
+                return self.counts(copy=copy)
+            finally:
+                self.select(before)
         n = self.num_sites
         if copy:
             r, a = np.empty(n, np.uint8), np.empty(n, np.uint8)

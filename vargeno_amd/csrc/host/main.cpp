@@ -1,6 +1,7 @@
 // main.cpp -- the `vargeno` command line of the drop-in (reference front-end: src/qv.cc:1853-2395).
 //   vargeno index <ref.fa> <snps.vcf> <prefix>
 //   vargeno geno  <prefix> <reads.fq> <snps.vcf> <out.vcf>
+//   vargeno cohort <prefix> <manifest> <snps.vcf>     many samples against ONE resident index (no reference counterpart; run_cohort)
 // Same positional arguments, file names, messages and exit codes as upstream.  `geno` drives the
 // HIP library through the C-ABI of include/vargeno_hip.h only.  Extra knobs come from the
 // environment so that the argument list stays the reference's:
@@ -27,6 +28,7 @@
 //   VARGENO_HOST_FASTQ=1  frame the FASTQ on the host (the reference's four fgets per record) instead of on the device
 //   VARGENO_PIPE_COPIERS=n  a FASTQ that is not a regular file: copier threads the one reader deals the pipe's pages to (default 4, at most 16;
 //                         0: the plain read() loop; see PipeIngest)
+//   VARGENO_COHORT_INFLIGHT=n  cohort: samples genotyped at the same time, each in a sample plane of its own (default 4)
 //   VARGENO_VERBOSE=1     stderr: the index plan and start-up report, one "ingest, replica g:" line per route taken, the "reads:" line with
 //                         the wall time phase by phase; index: the "cuts:" line
 //   VARGENO_STATS=1       the kernel's counting build: events per read (vg_set_stats; off by default here, it carries ~50 more registers per lane)
@@ -77,6 +79,7 @@ static void print_help()
 	fprintf(stderr, "------  -----------                   ----------\n");
 	fprintf(stderr, "index   Generate index            <input FASTA> <input SNPs in VCF> <index_prefix>\n");
 	fprintf(stderr, "geno    Perform genotyping        <index_prefix> <input FASTQ> <input SNPs in VCF> <output file in VCF>\n");
+	fprintf(stderr, "cohort  Genotype many samples     <index_prefix> <manifest: one <input FASTQ><TAB><output file in VCF> per line> <input SNPs in VCF>\n");
 }
 static void arg_check(int argc, int expected)
 {
@@ -119,6 +122,7 @@ struct GenoOptions {
 	const int pipe_copiers = std::min(16, std::max(0, env_int("VARGENO_PIPE_COPIERS", 4)));
 	const uint64_t budget = (uint64_t)(atof(env_str("VARGENO_MAX_DEVICE_GB")) * 1e9);                   // 0: not given
 	const int stats = env_int("VARGENO_STATS", 0);
+	const int cohort_inflight = std::max(1, env_int("VARGENO_COHORT_INFLIGHT", 4));      // cohort: samples in flight together = sample planes per replica
 	const bool force_rccl = env_int("VARGENO_FORCE_RCCL", 0) != 0, orderly_exit = env_int("VARGENO_ORDERLY_EXIT", 0) != 0, fqpipe_quiet = env_int("VARGENO_FQPIPE_QUIET", 0) != 0;
 	const char *const dump_counts = getenv("VARGENO_DUMP_COUNTS");
 	explicit GenoOptions(int devices) : have(devices)
@@ -804,28 +808,48 @@ static HostHandover once_only_route(const GenoOptions &o, PipeIngest &pipe_in, c
 
 // The host reader: the file from hand.host_from on -- or, for a stream that is read once, the bytes still in memory and then the
 // descriptor (never a second open: a FIFO has lost its writer by then).  Returns the job's reads: the route's and its own.
-static uint64_t host_reader_tail(const GenoOptions &o, const std::string &fastq, int fd, const PipeIngest *pipe_in, const std::vector<vg_index *> &ix, const HostHandover &hand)
+// submit(replica, batch, n): hands a host-framed batch to a replica's read loop (`geno`: vg_reads_submit; `cohort`: the same after
+// selecting the sample's plane, under the replica's mutex).  whole_file: VARGENO_HOST_FASTQ=1, no route ran before.
+typedef std::function<void(int, const vgh::ReadBatch &, uint64_t)> BatchSubmit;
+static uint64_t host_reader_tail(const GenoOptions &o, const std::string &fastq, int fd, const PipeIngest *pipe_in, const HostHandover &hand, bool whole_file, const BatchSubmit &submit)
 {
 	uint64_t total = hand.total;
 	int next_gpu = hand.next_gpu;
 	std::unique_ptr<vgh::FastqReader> rdp(pipe_in ? new vgh::FastqReader(fd, pipe_in->span_base, pipe_in->spans) : new vgh::FastqReader(fastq));
 	vgh::FastqReader &rd = *rdp;
 	vgh::ReadBatch rb;
-	if (!o.host_framing && hand.prime_from != UINT64_MAX) {   // re-read the last framed record: it only fills the line buffers
+	if (!whole_file && hand.prime_from != UINT64_MAX) {       // re-read the last framed record: it only fills the line buffers
 		rd.seek(hand.prime_from);
 		rb.clear();
 		(void)rd.next(rb, 1);
 	}
-	if (!o.host_framing) rd.seek(hand.host_from);
+	if (!whole_file) rd.seek(hand.host_from);
 	for (;;) {
 		rb.clear();
 		const uint64_t n = rd.next(rb, o.batch);
 		if (!n) break;
 		total += n;
-		VG_CHECK(vg_reads_submit(ix[(size_t)next_gpu], rb.bases.data(), rb.quals.data(), rb.offsets.data(), n));
+		submit(next_gpu, rb, n);
 		next_gpu = (next_gpu + 1) % o.ngpu;
 	}
 	return total;
+}
+
+// What the caller needs of the sites themselves (the same for every sample of a cohort)
+static void fetch_sites(vg_index *ix, vgh::SiteCounts &sc)
+{
+	const uint64_t ns = vg_num_sites(ix);
+	sc.pos.resize(ns); sc.ref_freq.resize(ns); sc.alt_freq.resize(ns);
+	VG_CHECK(vg_sites_fetch(ix, sc.pos.data(), nullptr, nullptr, sc.ref_freq.data(), sc.alt_freq.data()));
+}
+// The counters of the sample selected on every replica, summed over the replicas.  One process, n devices: one RCCL all-reduce of
+// the per-site counters over xGMI (VARGENO_FORCE_RCCL=1 also sends a single device through it, which is the identity)
+static void fetch_selected_counts(const GenoOptions &o, std::vector<vg_index *> &ix, vgh::SiteCounts &sc)
+{
+	if (o.ngpu > 1 || o.force_rccl) VG_CHECK(vg_counts_allreduce_devices(ix.data(), o.ngpu));
+	const uint64_t ns = vg_num_sites(ix[0]);
+	sc.ref_cnt.resize(ns); sc.alt_cnt.resize(ns);
+	VG_CHECK(vg_counts_fetch(ix[0], sc.ref_cnt.data(), sc.alt_cnt.data()));
 }
 
 // The per-site counters of the whole job, as the caller wants them.  false: said on stderr
@@ -839,13 +863,9 @@ static bool fetch_counts(const GenoOptions &o, std::vector<vg_index *> &ix, vgh:
 		for (auto *h : ix) { VG_CHECK(vg_stats_get(h, &st)); invalid += st.reads_invalid; }
 		if (invalid) { fprintf(stderr, "vargeno: %lu reads contain a character other than ACGTN (the reference aborts on these)\n", (unsigned long)invalid); return false; }
 	}
-	// one process, n devices: one RCCL all-reduce of the per-site counters over xGMI (VARGENO_FORCE_RCCL=1 also sends a
-	// single device through it, which is the identity)
-	if (o.ngpu > 1 || o.force_rccl) VG_CHECK(vg_counts_allreduce_devices(ix.data(), o.ngpu));
-	const uint64_t ns = vg_num_sites(ix[0]);
-	sc.pos.resize(ns); sc.ref_freq.resize(ns); sc.alt_freq.resize(ns); sc.ref_cnt.resize(ns); sc.alt_cnt.resize(ns);
-	VG_CHECK(vg_sites_fetch(ix[0], sc.pos.data(), nullptr, nullptr, sc.ref_freq.data(), sc.alt_freq.data()));
-	VG_CHECK(vg_counts_fetch(ix[0], sc.ref_cnt.data(), sc.alt_cnt.data()));
+	fetch_sites(ix[0], sc);
+	fetch_selected_counts(o, ix, sc);
+	const uint64_t ns = sc.pos.size();
 	if (const char *dump = o.dump_counts) {                              // the saturated counters as the caller gets them: ref counts, then alt counts, one byte per site
 		FILE *f = fopen(dump, "wb");
 		if (!f || fwrite(sc.ref_cnt.data(), 1, ns, f) != ns || fwrite(sc.alt_cnt.data(), 1, ns, f) != ns) { fprintf(stderr, "vargeno: cannot write %s\n", dump); return false; }
@@ -911,7 +931,9 @@ static int run_geno(const std::string &prefix, const std::string &fastq, const s
 		pre.clear();
 		close(in.fd);
 	}
-	const uint64_t total = host_reader_tail(o, fastq, in.fd, pipe_in.get(), ix, hand);
+	const uint64_t total = host_reader_tail(o, fastq, in.fd, pipe_in.get(), hand, o.host_framing, [&ix](int g, const vgh::ReadBatch &rb, uint64_t n) {
+		VG_CHECK(vg_reads_submit(ix[(size_t)g], rb.bases.data(), rb.quals.data(), rb.offsets.data(), n));
+	});
 	for (auto *h : ix) VG_CHECK(vg_sync(h));
 	clock_gettime(CLOCK_MONOTONIC, &t[2]);
 	vgh::SiteCounts sc;
@@ -931,6 +953,134 @@ static int run_geno(const std::string &prefix, const std::string &fastq, const s
 	return EXIT_SUCCESS;
 }
 
+// ---- `vargeno cohort`: many samples against one resident index ----------------------------------------------------------------
+// `geno` pays vg_index_open (seconds) per sample and holds the device alone while a decompressor feeds it at a few hundred MB/s.
+// Here the index is opened once per replica and K samples are in flight together, each counting into a sample plane of its own
+// (vg_samples_reserve / vg_sample_select): K worker threads take the manifest's entries in turn, every one through the once-only
+// route (PipeIngest: the path is opened ONCE, whatever it is), attached at once -- nothing is packed ahead of the open, no ranges,
+// no device framing.  A handle takes one caller at a time: select + submit happen under the replica's mutex.
+struct CohortSample { std::string fastq, out; int line = 0; };
+
+// The manifest: one "<reads.fq><TAB><out.vcf>" per line; blank lines and lines that start with '#' are skipped.  false: said on stderr
+static bool read_manifest(const std::string &path, std::vector<CohortSample> &samples)
+{
+	std::string text;
+	if (!vgh::read_whole_file(path, text)) { fprintf(stderr, "vargeno: cannot open the manifest %s\n", path.c_str()); return false; }
+	int line = 0;
+	for (size_t at = 0; at < text.size();) {
+		size_t nl = text.find('\n', at);
+		if (nl == std::string::npos) nl = text.size();
+		std::string ln = text.substr(at, nl - at);
+		at = nl + 1;
+		line++;
+		if (!ln.empty() && ln.back() == '\r') ln.pop_back();
+		if (ln.empty() || ln[0] == '#') continue;
+		const size_t tab = ln.find('\t');
+		if (tab == std::string::npos || tab == 0 || tab + 1 >= ln.size()) { fprintf(stderr, "vargeno: %s line %d: expected <input FASTQ><TAB><output file in VCF>\n", path.c_str(), line); return false; }
+		CohortSample s;
+		s.fastq = ln.substr(0, tab); s.out = ln.substr(tab + 1); s.line = line;
+		for (const CohortSample &before : samples)
+			if (before.out == s.out) { fprintf(stderr, "vargeno: %s line %d: output file %s is already the output of line %d\n", path.c_str(), line, s.out.c_str(), before.line); return false; }
+		samples.push_back(s);
+	}
+	if (samples.empty()) { fprintf(stderr, "vargeno: the manifest %s names no sample\n", path.c_str()); return false; }
+	return true;
+}
+
+static int run_cohort(const std::string &prefix, const std::string &manifest, const std::string &vcf_in)
+{
+	struct timespec t0; clock_gettime(CLOCK_MONOTONIC, &t0);
+	std::vector<CohortSample> samples;
+	if (!read_manifest(manifest, samples)) return EXIT_FAILURE;      // (before any device is touched)
+	std::vector<vgh::ChrLen> chrlens = vgh::read_chrlens(prefix + ".chrlens");
+	const int have = vg_device_count();
+	if (have <= 0) { fprintf(stderr, "vargeno: no HIP device found (this build has no CPU path)\n"); return EXIT_FAILURE; }
+	const GenoOptions o(have);
+	const int K = (int)std::min<size_t>(samples.size(), (size_t)o.cohort_inflight);
+
+	fprintf(stderr, "Initializing...\n");
+	std::string vcf_text;
+	bool vcf_ok = false;
+	std::thread vcf_reader([&] { vcf_ok = vgh::read_whole_file(vcf_in, vcf_text); });
+	struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } vcf_joiner{vcf_reader};
+	const std::vector<vg_read_store *> no_store((size_t)o.ngpu, nullptr);
+	std::vector<vg_index *> ix((size_t)o.ngpu, nullptr);
+	if (!open_indexes(prefix, o, no_store, ix, false)) return EXIT_FAILURE;
+	for (auto *h : ix) { VG_CHECK(vg_set_stats(h, o.stats)); VG_CHECK(vg_samples_reserve(h, (uint32_t)K)); }
+	if (o.verbose) { fprintf(stderr, "index replica: %s\n", vg_index_plan(ix[0])); fprintf(stderr, "index start-up: %s\n", vg_index_open_report(ix[0])); }
+	vcf_reader.join();
+	if (!vcf_ok) { fprintf(stderr, "Error opening: %s . You have failed.\n", vcf_in.c_str()); return EXIT_FAILURE; }
+	vgh::SiteCounts sites;
+	fetch_sites(ix[0], sites);
+	struct timespec t1; clock_gettime(CLOCK_MONOTONIC, &t1);
+
+	fprintf(stderr, "Processing...\n");
+	std::vector<std::mutex> mu((size_t)o.ngpu);                       // one caller at a time per handle
+	std::atomic<size_t> next{0};
+	std::atomic<int> failed{0};
+	auto worker = [&](uint32_t plane) {
+		for (;;) {
+			const size_t at = next.fetch_add(1);
+			if (at >= samples.size()) return;
+			const CohortSample &s = samples[at];
+			struct timespec a; clock_gettime(CLOCK_MONOTONIC, &a);
+			const int fd = open(s.fastq.c_str(), O_RDONLY);
+			if (fd < 0) { fprintf(stderr, "vargeno: %s line %d: cannot open %s\n", manifest.c_str(), s.line, s.fastq.c_str()); failed.store(1); continue; }
+			(void)fcntl(fd, F_SETPIPE_SZ, 1 << 20);
+			uint64_t total = 0;
+			{
+				PipeIngest pin(fd, o.pipe_chunk(), std::max(1, o.pack_threads / K), o.pipe_copiers, no_store,
+				               [&](size_t g, const uint64_t *k, const uint64_t *m, const uint64_t *off, uint64_t n) -> std::string {
+					               std::lock_guard<std::mutex> lock(mu[g]);
+					               if (vg_sample_select(ix[g], plane) != VG_OK) return std::string("vg_sample_select failed: ") + vg_last_error();
+					               return vg_reads_submit_packed(ix[g], k, m, off, n) == VG_OK ? std::string() : std::string("vg_reads_submit_packed failed: ") + vg_last_error();
+				               });
+				pin.attach();
+				pin.finish();
+				if (!pin.error.empty()) { fprintf(stderr, "vargeno: %s line %d: %s\n", manifest.c_str(), s.line, pin.error.c_str()); exit(EXIT_FAILURE); }
+				// what the packer refused, and the possibly truncated tail: the host reader, into the same plane
+				const HostHandover hand{pin.records, pin.consumed, pin.records ? pin.last : UINT64_MAX, 0};
+				total = host_reader_tail(o, s.fastq, fd, &pin, hand, false, [&](int g, const vgh::ReadBatch &rb, uint64_t n) {
+					std::lock_guard<std::mutex> lock(mu[(size_t)g]);
+					VG_CHECK(vg_sample_select(ix[(size_t)g], plane));
+					VG_CHECK(vg_reads_submit(ix[(size_t)g], rb.bases.data(), rb.quals.data(), rb.offsets.data(), n));
+				});
+			}
+			close(fd);
+			// the sample is complete: its plane summed over the replicas, fetched and zeroed for the worker's next sample
+			vgh::SiteCounts sc;
+			uint64_t invalid = 0;
+			{
+				for (auto &m : mu) m.lock();
+				for (auto *h : ix) VG_CHECK(vg_sample_select(h, plane));
+				for (auto *h : ix) { uint64_t bad = 0; VG_CHECK(vg_sample_invalid_reads(h, plane, &bad)); invalid += bad; }
+				if (!invalid) fetch_selected_counts(o, ix, sc);
+				for (auto *h : ix) VG_CHECK(vg_sample_reset(h, plane));
+				for (auto &m : mu) m.unlock();
+			}
+			if (invalid) {
+				// util.c:103: the reference aborts on such a read and writes no VCF; the other samples go on
+				fprintf(stderr, "vargeno: %s line %d: %lu reads of %s contain a character other than ACGTN (the reference aborts on these): no VCF written\n", manifest.c_str(), s.line, (unsigned long)invalid, s.fastq.c_str());
+				failed.store(1);
+				continue;
+			}
+			sc.pos = sites.pos; sc.ref_freq = sites.ref_freq; sc.alt_freq = sites.alt_freq;
+			try { vgh::write_genotyped_vcf(sc, chrlens, vcf_in, s.out, &vcf_text); }
+			catch (const vgh::Error &e) { fprintf(stderr, "vargeno: %s line %d: %s\n", manifest.c_str(), s.line, e.msg.c_str()); failed.store(1); continue; }
+			if (o.verbose) { struct timespec b; clock_gettime(CLOCK_MONOTONIC, &b); fprintf(stderr, "sample, line %d: reads: %lu  plane: %u  open -> VCF: %.3f s\n", s.line, (unsigned long)total, plane, secs(a, b)); }
+		}
+	};
+	std::vector<std::thread> th;
+	for (int w = 0; w < K; w++) th.emplace_back(worker, (uint32_t)w);
+	for (auto &t : th) t.join();
+	struct timespec t2; clock_gettime(CLOCK_MONOTONIC, &t2);
+	if (o.verbose) fprintf(stderr, "cohort: samples: %lu  in flight: %d  gpus: %d  index load %.3f s  wall: %.3f s\n", (unsigned long)samples.size(), K, o.ngpu, secs(t0, t1), secs(t0, t2));
+	const int status = failed.load() ? EXIT_FAILURE : EXIT_SUCCESS;
+	if (o.orderly_exit) { for (auto *h : ix) vg_index_close(h); return status; }
+	fflush(stdout); fflush(stderr);
+	_exit(status);                                                    // (as `geno`: the outputs are closed, the operating system takes the memory back)
+}
+
 int main(int argc, const char *argv[])
 {
 	if (argc < 2) { print_help(); return 0; }
@@ -946,6 +1096,9 @@ int main(int argc, const char *argv[])
 		} else if (opt == "geno") {
 			arg_check(argc, 4);
 			return run_geno(argv[2], argv[3], argv[4], argv[5]);
+		} else if (opt == "cohort") {
+			arg_check(argc, 3);
+			return run_cohort(argv[2], argv[3], argv[4]);
 		} else if (opt == "fqcheck") {
 			// hidden: the host FASTQ framing alone -- one line per record: read length, then the read and the quality
 			// characters the path can see (no device needed; tests/test_host_tools.py)

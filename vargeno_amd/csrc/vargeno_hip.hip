@@ -560,9 +560,13 @@ __global__ __launch_bounds__(PACK_T * PACK_WPB) void vg_pack_kernel(const uint8_
 	}
 }
 
-// base-indexed counters of the wave kernel -> the ref / alt sums (and zero them for the next round)
-__global__ void vg_fold_counters(uint32_t *__restrict__ cnt4, const uint8_t *__restrict__ site_ba, uint32_t *__restrict__ cnt, uint64_t n_sites)
+// base-indexed counters of the wave kernel -> the ref / alt sums (and zero them for the next round): one launch for every sample
+// plane that has taken increments since the last fold -- blockIdx.y walks the list of their numbers (one entry, plane 0, for a
+// handle that never reserved a second plane)
+__global__ void vg_fold_counters(const PlanePtr *__restrict__ planes, const uint32_t *__restrict__ dirty, const uint8_t *__restrict__ site_ba, uint64_t n_sites)
 {
+	const PlanePtr pl = planes[dirty[blockIdx.y]];
+	uint32_t *__restrict__ const cnt4 = pl.cnt4, *__restrict__ const cnt = pl.cnt;
 	for (uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n_sites; s += (uint64_t)gridDim.x * blockDim.x) {
 		uint4 v = ((const uint4 *)cnt4)[s];
 		if ((v.x | v.y | v.z | v.w) == 0) continue;
@@ -593,8 +597,10 @@ template <bool STATS>
 __global__ __launch_bounds__(256) void vg_lane_kernel(DevIndex d, Scratch s, const uint8_t *__restrict__ bases, const uint8_t *__restrict__ quals,
                                                       const uint64_t *__restrict__ offsets, uint64_t n_reads_arg, const uint32_t *__restrict__ read_ids,
                                                       const uint32_t *__restrict__ n_ids, uint32_t *overflow_list, uint32_t *overflow_count, unsigned long long *stats, uint32_t *invalid_reads,
-                                                      const uint32_t *__restrict__ gate, const uint64_t *__restrict__ pk_kmer, const uint64_t *__restrict__ pk_meta, const bool packed)
+                                                      const uint32_t *__restrict__ gate, const uint64_t *__restrict__ pk_kmer, const uint64_t *__restrict__ pk_meta, const bool packed,
+                                                      const PlanePtr *__restrict__ planes, const uint16_t *__restrict__ plane_tag)
 {
+	// planes != nullptr (the run over the late store only): read r counts into the sample plane its tag names, not into d.cnt
 	const uint64_t n_reads = n_ids ? (uint64_t)*n_ids : n_reads_arg;          // a list launch (or a device-framed batch) is sized on the device: no host round trip
 	const uint32_t gtid = blockIdx.x * blockDim.x + threadIdx.x;
 	const uint32_t stride = gridDim.x * blockDim.x;
@@ -619,6 +625,7 @@ __global__ __launch_bounds__(256) void vg_lane_kernel(DevIndex d, Scratch s, con
 		L.st.add(S_READS, 1);
 		L.st.add(S_INGEST, 9 * n);
 		L.overflow = false;
+		if (planes) L.cnt = planes[plane_tag[rid]].cnt;
 
 		int cls = 0;
 		if (packed) cls = (pmeta & PK_INVALID) ? 2 : (pmeta & PK_SKIP_N) ? 1 : 0;
@@ -663,14 +670,19 @@ __global__ __launch_bounds__(256) void vg_lane_kernel(DevIndex d, Scratch s, con
 // over the store ONCE, when the caller next synchronises (finish_pending).  One 64-bit atomic reserves a read's place and its
 // chunks' (reads << 32 | chunks: both cursors move together, so the offsets stay a prefix sum); what does not fit -- or has more
 // chunks than a flag word has gate bits -- goes to the residual list and takes the per-batch lane launch as before.
+// The store mixes the reads of every batch since the last synchronisation, and those batches may belong to different samples:
+// each read carries the number of its sample plane (tag), and the lane machine's run bumps that plane.
+constexpr uint32_t VG_MAX_SAMPLES = 65535;                               // (a tag is 16 bits wide)
 struct LateStore {
 	uint64_t *kmers = nullptr, *meta = nullptr, *offsets = nullptr;      // [cap_chunks + 2], [cap_reads], [cap_reads + 1] (offsets in bases: 32 x chunks before)
+	uint16_t *tag = nullptr;                                             // [cap_reads] sample plane of the read's batch
 	unsigned long long *state = nullptr;                                 // [0] reads << 32 | chunks reserved so far, [1] reads that fit (a prefix)
 	uint32_t *lost = nullptr, *lost_n = nullptr;                         // reads that outgrew the lane machine's deep scratch too
 	uint32_t cap_reads = 0, cap_chunks = 0;
 };
 __global__ __launch_bounds__(256) void vg_late_collect(LateStore ls, const uint64_t *__restrict__ pk_kmer, const uint64_t *__restrict__ pk_meta, const uint64_t *__restrict__ offsets,
-                                                       const uint32_t *__restrict__ list, const uint32_t *__restrict__ n_list, uint32_t *__restrict__ residual, uint32_t *__restrict__ n_residual)
+                                                       const uint32_t *__restrict__ list, const uint32_t *__restrict__ n_list, uint32_t *__restrict__ residual, uint32_t *__restrict__ n_residual,
+                                                       const uint32_t plane)
 {
 	const uint32_t n = *n_list;
 	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
@@ -684,6 +696,7 @@ __global__ __launch_bounds__(256) void vg_late_collect(LateStore ls, const uint6
 			if (r < ls.cap_reads && c0 + nch <= ls.cap_chunks) {
 				for (uint32_t c = 0; c < nch; c++) ls.kmers[c0 + c] = pk_kmer[(off >> 5) + c];
 				ls.meta[r] = pk_meta[rid];
+				ls.tag[r] = (uint16_t)plane;
 				ls.offsets[r] = 32ull * c0;
 				ls.offsets[r + 1] = 32ull * (c0 + nch);
 				atomicMax(&ls.state[1], (unsigned long long)(r + 1));
@@ -964,6 +977,15 @@ struct Slot {
 	// stream; the deep tier behind it on the tail stream; the batch's counters on the host, behind the last of its tiers
 	SlotEvent pack_begin, pack_end, wave_begin, wave_end, deep_end, batch_done;
 	bool busy = false;
+	uint32_t plane = 0;                                              // the sample this batch belongs to (acquire_slot): every tier of the batch counts into that plane
+};
+
+// One sample's counters and what else is kept per sample.  Plane 0 is d.cnt / d.cnt4 (inside the arena); a further plane is one
+// block of 24 * n_sites + 16 bytes outside the plan (vg_samples_reserve): cnt4 first, cnt behind it.
+struct Plane {
+	PlanePtr p{nullptr, nullptr};
+	bool dirty = false;                   // cnt4 holds increments not yet folded into cnt
+	uint64_t invalid = 0;                 // reads of this sample the reference would have aborted on, since open / vg_counts_reset / vg_sample_reset
 };
 
 struct vg_index {
@@ -996,7 +1018,12 @@ struct vg_index {
 	uint64_t arena_misses = 0, arena_miss_bytes = 0;      // requests the arena had no room for (served by hipMalloc)
 	uint64_t dev_bytes = 0;               // device memory of the index: hipMalloc'ed buffers (counted as they are made) + the arena's mapped chunks (counted when construction is over)
 	uint64_t n_sites = 0;
-	bool cnt4_dirty = false;                           // base-indexed counters hold increments not yet folded into d.cnt
+	std::vector<Plane> planes;                         // sample planes: [0] = d.cnt / d.cnt4; grown by vg_samples_reserve
+	uint32_t cur_sample = 0;                           // the selected sample (vg_sample_select): new batches, fetch, all-reduce
+	uint32_t fq_sample = 0;                            // the sample of the open FASTQ stream: the one selected at its begin
+	PlanePtr *d_planes = nullptr;                      // [VG_MAX_SAMPLES] device copy of the planes' pointers (late-store run, fold)
+	uint32_t *d_dirty = nullptr;                       // [VG_MAX_SAMPLES] numbers of the planes the next fold takes ...
+	std::vector<uint32_t> dirty_up;                    // ... as last copied up: a handle with one plane never copies again
 	std::vector<uint32_t> site_pos;
 	std::vector<uint8_t> site_ref, site_alt, site_rf, site_af;
 	ScratchBuf mid, big;                  // lane-tier scratch: every lane x 64 contexts; a few lanes x 16384 contexts
@@ -1836,8 +1863,16 @@ static int build_on_device(vg_index *ix, DevCols &c, const ViewPlan &plan, uint6
 		ls.cap_reads = 1u << 16; ls.cap_chunks = 1u << 20;
 		if (const char *e = getenv("VG_LATE_READS")) { ls.cap_reads = (uint32_t)std::max(1, atoi(e)); ls.cap_chunks = std::min<uint32_t>(ls.cap_chunks, 32u * ls.cap_reads); }
 		if ((rc = dev_alloc(ix, &ls.kmers, (uint64_t)ls.cap_chunks + 2, false, true)) || (rc = dev_alloc(ix, &ls.meta, ls.cap_reads, false, true)) || (rc = dev_alloc(ix, &ls.offsets, (uint64_t)ls.cap_reads + 1, false, true)) ||
-		    (rc = dev_alloc(ix, &ls.lost, ls.cap_reads, false, true)) || (rc = dev_alloc(ix, &ls.lost_n, 1, true, true)) || (rc = dev_alloc(ix, &ls.state, 2, true, true))) return rc;
+		    (rc = dev_alloc(ix, &ls.lost, ls.cap_reads, false, true)) || (rc = dev_alloc(ix, &ls.lost_n, 1, true, true)) || (rc = dev_alloc(ix, &ls.state, 2, true, true)) ||
+		    (rc = dev_alloc(ix, &ls.tag, ls.cap_reads, true, true))) return rc;
 	}
+	// sample planes: plane 0 is the counters above; the table and the fold's list have their full width from the start (1.25 MiB),
+	// so that vg_samples_reserve adds the planes' own bytes and nothing else
+	if ((rc = dev_alloc(ix, &ix->d_planes, VG_MAX_SAMPLES, false, true)) || (rc = dev_alloc(ix, &ix->d_dirty, VG_MAX_SAMPLES, true, true))) return rc;
+	ix->planes.assign(1, Plane());
+	ix->planes[0].p = PlanePtr{ix->d.cnt, ix->d.cnt4};
+	ix->dirty_up.assign(1, 0u);
+	HIP_TRY(hipMemcpy(ix->d_planes, &ix->planes[0].p, sizeof(PlanePtr), hipMemcpyHostToDevice));
 	for (Slot &sl : ix->slot) if ((rc = dev_alloc(ix, &sl.ctr, 16, true, true))) return rc;       // [0..2] spill counts, [3] invalid reads, [4],[5] work counters of the two wave tiers, [6] reads left for the per-batch lane tier
 	if ((rc = dev_alloc(ix, &ix->d_clamped, 2 * ix->n_sites + 2, false, true))) return rc;
 	if ((rc = dev_alloc(ix, &ix->d_fq, 1, true, true))) return rc;
@@ -2200,6 +2235,14 @@ static void launch_lane(bool stats, unsigned grid, unsigned block, hipStream_t s
 	else vg_lane_kernel<false><<<grid, block, 0, st>>>(a...);
 }
 
+// the index as the kernels of a batch of sample `plane` see it: the shared tables, that plane's counters
+static DevIndex plane_view(const vg_index *ix, uint32_t plane)
+{
+	DevIndex v = ix->d;
+	v.cnt = ix->planes[plane].p.cnt; v.cnt4 = ix->planes[plane].p.cnt4;
+	return v;
+}
+
 static int harvest(vg_index *ix, Slot &sl)
 {
 	if (!sl.busy) return VG_OK;
@@ -2209,13 +2252,14 @@ static int harvest(vg_index *ix, Slot &sl)
 	uint32_t *const r_list = sl.lt_late ? sl.listA.p : sl.listB.p, *const r_cnt = sl.lt_late ? &sl.ctr[6] : &sl.ctr[1];
 	if (resid) ix->lane_tier_seen = true;
 	if (resid && !sl.lt_enqueued) {
-		// the lane machine with its lists in HBM finishes them now
-		launch_lane(sl.lt_stats, ix->big.s.nlanes / 64, 64, ix->tail2, ix->d, ix->big.s, sl.lt_bases, sl.lt_quals, sl.lt_offsets, 0, r_list, r_cnt, sl.listC.p, &sl.ctr[2], ix->d_stats, nullptr, sl.lt_gate, sl.pk_kmer.p, sl.pk_meta.p, sl.lt_packed);
+		// the lane machine with its lists in HBM finishes them now, into the batch's plane
+		launch_lane(sl.lt_stats, ix->big.s.nlanes / 64, 64, ix->tail2, plane_view(ix, sl.plane), ix->big.s, sl.lt_bases, sl.lt_quals, sl.lt_offsets, 0, r_list, r_cnt, sl.listC.p, &sl.ctr[2], ix->d_stats, nullptr, sl.lt_gate, sl.pk_kmer.p, sl.pk_meta.p, sl.lt_packed, nullptr, nullptr);
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipMemcpyAsync(sl.h_ctr.p, sl.ctr, 32, hipMemcpyDeviceToHost, ix->tail2));
 		HIP_TRY(hipStreamSynchronize(ix->tail2));
 	}
 	for (int i = 0; i < 4; i++) ix->cum[i] += sl.h_ctr.p[i];
+	ix->planes[sl.plane].invalid += sl.h_ctr.p[3];
 	// the deep tier's grid follows the lists it has been getting (enqueue_batch): the larger of this batch's and half the hint before
 	ix->spill_hint = std::max<uint32_t>(sl.h_ctr.p[0], ix->spill_hint / 2);
 	ix->spill_known = true;
@@ -2237,7 +2281,7 @@ static int run_late_store(vg_index *ix)
 	const uint64_t n = st[1];
 	if (st[0] == 0) return VG_OK;
 	if (n) {
-		launch_lane(ix->late_stats, ix->big.s.nlanes / 64, 64, ix->tail, ix->d, ix->big.s, nullptr, nullptr, ix->late.offsets, n, nullptr, nullptr, ix->late.lost, ix->late.lost_n, ix->d_stats, nullptr, nullptr, ix->late.kmers, ix->late.meta, true);
+		launch_lane(ix->late_stats, ix->big.s.nlanes / 64, 64, ix->tail, ix->d, ix->big.s, nullptr, nullptr, ix->late.offsets, n, nullptr, nullptr, ix->late.lost, ix->late.lost_n, ix->d_stats, nullptr, nullptr, ix->late.kmers, ix->late.meta, true, ix->d_planes, ix->late.tag);
 		HIP_TRY(hipGetLastError());
 	}
 	uint32_t lost = 0;
@@ -2262,12 +2306,18 @@ static int finish_pending(vg_index *ix)
 	if (ix->ingest) HIP_TRY(hipStreamSynchronize(ix->ingest));
 	for (Slot &sl : ix->slot) { int rc = harvest(ix, sl); if (rc) return rc; }
 	{ int rc = run_late_store(ix); if (rc) return rc; }
-	if (ix->cnt4_dirty && ix->n_sites) {
-		vg_fold_counters<<<(unsigned)std::min<uint64_t>((ix->n_sites + 255) / 256, 4096), 256, 0, ix->stream>>>(ix->d.cnt4, ix->d.site_ba, ix->d.cnt, ix->n_sites);
+	// every plane that took increments, in ONE launch
+	std::vector<uint32_t> dirty;
+	for (uint32_t s = 0; s < (uint32_t)ix->planes.size(); s++) if (ix->planes[s].dirty) { dirty.push_back(s); ix->planes[s].dirty = false; }
+	if (!dirty.empty() && ix->n_sites) {
+		if (dirty != ix->dirty_up) {
+			HIP_TRY(hipMemcpy(ix->d_dirty, dirty.data(), dirty.size() * 4, hipMemcpyHostToDevice));
+			ix->dirty_up = dirty;
+		}
+		vg_fold_counters<<<dim3((unsigned)std::min<uint64_t>((ix->n_sites + 255) / 256, 4096), (unsigned)dirty.size()), 256, 0, ix->stream>>>(ix->d_planes, ix->d_dirty, ix->d.site_ba, ix->n_sites);
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipStreamSynchronize(ix->stream));
 	}
-	ix->cnt4_dirty = false;
 	if (ix->cum[2]) return fail(VG_ENOMEM, "a read produced more hit contexts than the deep scratch holds (the reference overruns MAX_HITS=2000 long before, qv.cc:709)");
 	return VG_OK;
 }
@@ -2330,6 +2380,7 @@ static int enqueue_batch(vg_index *ix, Slot &sl, const bool stats, const uint8_t
 {
 	uint32_t *ctr = sl.ctr;
 	int rc;
+	const DevIndex dv = plane_view(ix, sl.plane);                    // the batch's sample: its counters, the shared tables
 	if (!ix->force_generic) {
 		const bool big = !stats && ix->d.mx == nullptr;                // an index without the merged view: the kernel built for it
 		const bool sdx = !stats && !big && ix->d.dx != nullptr && ix->d.dx_bits < 32u;      // a direct table of fewer than 2^32 buckets: the instantiation that compares (F, lo32)
@@ -2349,9 +2400,9 @@ static int enqueue_batch(vg_index *ix, Slot &sl, const bool stats, const uint8_t
 		// under the head of this batch's wave kernel: its few single-wave workgroups drain while the main tier pulls its work
 		// dynamically, which costs less than holding the wave kernel back for them (0.71 -> 0.66 ms per 1 M-read step).
 		HIP_TRY(hipEventRecord(sl.wave_begin, ix->stream));       // the wave kernel's own start
-		ix->cnt4_dirty = true;
+		ix->planes[sl.plane].dirty = true;
 		const unsigned wgrid = (unsigned)std::min<uint64_t>((n_reads + 64 * W1_WPB - 1) / (64 * W1_WPB), (uint64_t)ix->wave_grid / W1_WPB);
-		launch_wave<W1_ECAP, W1_NCAP, W1_WPB>(big, sdx, stats, wgrid, ix->stream, ix->d, sl.pk_kmer.p, sl.pk_meta.p, d_offsets, n_reads, nullptr, d_n_reads, sl.listA.p, &ctr[0], &ctr[4], ix->work_chunk, ix->d_stats, fin);
+		launch_wave<W1_ECAP, W1_NCAP, W1_WPB>(big, sdx, stats, wgrid, ix->stream, dv, sl.pk_kmer.p, sl.pk_meta.p, d_offsets, n_reads, nullptr, d_n_reads, sl.listA.p, &ctr[0], &ctr[4], ix->work_chunk, ix->d_stats, fin);
 		HIP_TRY(hipEventRecord(sl.wave_end, ix->stream));
 		ix->last_wave_end = sl.wave_end;
 		// tail stream, the deep tier: the same kernel with deeper tables over the spill list (single-wave workgroups of 42 KB of LDS).
@@ -2369,12 +2420,12 @@ static int enqueue_batch(vg_index *ix, Slot &sl, const bool stats, const uint8_t
 		// the waves pull their work from a counter and their pulls grow with the list -- just by fewer waves.
 		unsigned w2grid = (unsigned)std::min<uint64_t>((n_reads + 63) / 64, (uint64_t)ix->cus * ix->w2_wpc);
 		if (ix->spill_known && !ix->w2_full_grid) w2grid = std::min<unsigned>(w2grid, std::max<unsigned>(32u, (2u * ix->spill_hint + ix->w2_chunk - 1) / ix->w2_chunk + 16u));
-		launch_wave<W3_ECAP, W3_NCAP, 1>(big, sdx, stats, w2grid, ix->tail, ix->d, sl.pk_kmer.p, sl.pk_meta.p, d_offsets, 0, sl.listA.p, &ctr[0], sl.listB.p, &ctr[1], &ctr[5], ix->w2_chunk, ix->d_stats, nofuse);
+		launch_wave<W3_ECAP, W3_NCAP, 1>(big, sdx, stats, w2grid, ix->tail, dv, sl.pk_kmer.p, sl.pk_meta.p, d_offsets, 0, sl.listA.p, &ctr[0], sl.listB.p, &ctr[1], &ctr[5], ix->w2_chunk, ix->d_stats, nofuse);
 		// what the deep tier leaves behind goes to the handle's late store (the lane machine runs over it once, at the next
 		// synchronisation); the slot only keeps what the store cannot take (listA is free again: the deep tier has consumed it)
 		sl.lt_late = ix->late.state != nullptr;
 		if (sl.lt_late) {
-			vg_late_collect<<<4, 256, 0, ix->tail>>>(ix->late, sl.pk_kmer.p, sl.pk_meta.p, d_offsets, sl.listB.p, &ctr[1], sl.listA.p, &ctr[6]);
+			vg_late_collect<<<4, 256, 0, ix->tail>>>(ix->late, sl.pk_kmer.p, sl.pk_meta.p, d_offsets, sl.listB.p, &ctr[1], sl.listA.p, &ctr[6], sl.plane);
 			ix->late_dirty = true; ix->late_stats = stats;
 		}
 	} else {
@@ -2383,7 +2434,7 @@ static int enqueue_batch(vg_index *ix, Slot &sl, const bool stats, const uint8_t
 		if ((rc = begin_batch(sl, ix->stream, produced_on))) return rc;
 		HIP_TRY(hipEventRecord(sl.pack_end, ix->stream));
 		HIP_TRY(hipEventRecord(sl.wave_begin, ix->stream));
-		launch_lane(stats, g1, 256, ix->stream, ix->d, ix->mid.s, d_bases, d_quals, d_offsets, n_reads, nullptr, d_n_reads, sl.listB.p, &ctr[1], ix->d_stats, packed ? nullptr : &ctr[3], d_gate, sl.pk_kmer.p, sl.pk_meta.p, packed);
+		launch_lane(stats, g1, 256, ix->stream, dv, ix->mid.s, d_bases, d_quals, d_offsets, n_reads, nullptr, d_n_reads, sl.listB.p, &ctr[1], ix->d_stats, packed ? nullptr : &ctr[3], d_gate, sl.pk_kmer.p, sl.pk_meta.p, packed, nullptr, nullptr);
 		HIP_TRY(hipEventRecord(sl.wave_end, ix->stream));
 		HIP_TRY(hipStreamWaitEvent(ix->tail, sl.wave_end, 0));
 	}
@@ -2404,7 +2455,7 @@ static int enqueue_batch(vg_index *ix, Slot &sl, const bool stats, const uint8_t
 	if (sl.lt_enqueued) {
 		lt = ix->tail2;
 		HIP_TRY(hipStreamWaitEvent(lt, sl.deep_end, 0));
-		launch_lane(stats, ix->big.s.nlanes / 64, 64, lt, ix->d, ix->big.s, d_bases, d_quals, d_offsets, 0, sl.lt_late ? sl.listA.p : sl.listB.p, sl.lt_late ? &ctr[6] : &ctr[1], sl.listC.p, &ctr[2], ix->d_stats, nullptr, d_gate, sl.pk_kmer.p, sl.pk_meta.p, packed);
+		launch_lane(stats, ix->big.s.nlanes / 64, 64, lt, dv, ix->big.s, d_bases, d_quals, d_offsets, 0, sl.lt_late ? sl.listA.p : sl.listB.p, sl.lt_late ? &ctr[6] : &ctr[1], sl.listC.p, &ctr[2], ix->d_stats, nullptr, d_gate, sl.pk_kmer.p, sl.pk_meta.p, packed, nullptr, nullptr);
 	}
 	HIP_TRY(hipMemcpyAsync(sl.h_ctr.p, ctr, 32, hipMemcpyDeviceToHost, lt));
 	HIP_TRY(hipEventRecord(sl.batch_done, lt));
@@ -2413,12 +2464,14 @@ static int enqueue_batch(vg_index *ix, Slot &sl, const bool stats, const uint8_t
 	return VG_OK;
 }
 
-static int acquire_slot(vg_index *ix, Slot **out)
+// sample: the plane the slot's next batch counts into -- the selected sample, or the open FASTQ stream's
+static int acquire_slot(vg_index *ix, Slot **out, uint32_t sample)
 {
 	Slot &sl = ix->slot[ix->next_slot];
 	ix->next_slot = (ix->next_slot + 1) % NSLOT;
 	int rc = harvest(ix, sl);                             // blocks only when NSLOT batches are already in flight
 	if (rc) return rc;
+	sl.plane = sample;
 	*out = &sl;
 	return VG_OK;
 }
@@ -2457,7 +2510,7 @@ extern "C" int vg_reads_process_device(vg_index *ix, const uint8_t *d_bases, con
 	if (n_reads == 0) return VG_OK;
 	HIP_TRY(hipSetDevice(ix->device));
 	Slot *sl = nullptr;
-	int rc = acquire_slot(ix, &sl);
+	int rc = acquire_slot(ix, &sl, ix->cur_sample);
 	if (rc) return rc;
 	return launch_batch(ix, *sl, d_bases, d_quals, d_offsets, n_reads);
 }
@@ -2468,7 +2521,7 @@ extern "C" int vg_reads_process_device_gated(vg_index *ix, const uint8_t *d_base
 	if (n_reads == 0) return VG_OK;
 	HIP_TRY(hipSetDevice(ix->device));
 	Slot *sl = nullptr;
-	int rc = acquire_slot(ix, &sl);
+	int rc = acquire_slot(ix, &sl, ix->cur_sample);
 	if (rc) return rc;
 	return launch_batch(ix, *sl, d_bases, nullptr, d_offsets, n_reads, nullptr, nullptr, 0, d_gate_words);
 }
@@ -2526,14 +2579,14 @@ static int submit_packed_impl(vg_index *ix, const uint64_t *kmers, const uint64_
 	int rc = check_packed(kmers, meta, chunk_offsets, n_reads, n_chunks, invalid);
 	if (rc) return rc;
 	Slot *sl = nullptr;
-	if ((rc = acquire_slot(ix, &sl))) return rc;
+	if ((rc = acquire_slot(ix, &sl, ix->cur_sample))) return rc;
 	// the flat-batch offsets of the trimmed reads (32 x chunks before each), in the slot's page-locked staging
 	if (n_reads + 1 > sl->hp_offsets.cap && (rc = reserve_together({&sl->hp_meta, &sl->hp_offsets}, (n_reads + 1) * 5 / 4, "packed staging"))) return rc;
 	for (uint64_t i = 0; i <= n_reads; i++) sl->hp_offsets.p[i] = 32 * chunk_offsets[i];
 	hipStream_t is = ix->ingest_or_main();
 	rc = launch_packed(ix, *sl, kmers, meta, sl->hp_offsets.p, n_reads, n_chunks, is);
 	if (rc == VG_OK && !pinned) HIP_TRY(hipStreamSynchronize(is));          // the caller's arrays are free again
-	if (rc == VG_OK) ix->host_invalid += invalid;
+	if (rc == VG_OK) { ix->host_invalid += invalid; ix->planes[sl->plane].invalid += invalid; }
 	return rc;
 }
 extern "C" int vg_reads_submit_packed(vg_index *ix, const uint64_t *kmers, const uint64_t *meta, const uint64_t *chunk_offsets, uint64_t n_reads)
@@ -2642,12 +2695,12 @@ extern "C" int vg_reads_submit_store(vg_index *ix, vg_read_store *rs)
 		hipStream_t is = ix->ingest_or_main();
 		for (const StoredBatch &b : rs->batches) {
 			Slot *sl = nullptr;
-			int rc = acquire_slot(ix, &sl);
+			int rc = acquire_slot(ix, &sl, ix->cur_sample);
 			if (rc) return rc;
 			rc = launch_packed(ix, *sl, b.kmers, b.meta, b.offsets, b.n_reads, b.n_chunks, is);
 			if (rc) return rc;
 		}
-		ix->host_invalid += rs->invalid;
+		ix->host_invalid += rs->invalid; ix->planes[ix->cur_sample].invalid += rs->invalid;
 		return VG_OK;
 	});
 }
@@ -2669,7 +2722,7 @@ static int submit_impl(vg_index *ix, const uint8_t *bases, const uint8_t *quals,
 		if (offsets[i + 1] - offsets[i] > 1022) return fail(VG_EBADREAD, "read longer than 1022 bases (reference BUF_SIZE 1024, qv.cc:700)");
 	}
 	Slot *slp = nullptr;
-	int rc = acquire_slot(ix, &slp);
+	int rc = acquire_slot(ix, &slp, ix->cur_sample);
 	if (rc) return rc;
 	Slot &sl = *slp;
 	if ((rc = sl.st_bases.reserve(total + 64, "base text")) || (rc = sl.st_quals.reserve(total + 64, "quality strings")) || (rc = sl.st_offsets.reserve(n_reads + 1, "read offsets"))) return rc;
@@ -2726,6 +2779,7 @@ extern "C" int vg_fastq_stream_begin_packed(vg_index *ix, int host_threads)
 		if (!ix->packer || ix->packer->threads() != host_threads) { delete ix->packer; ix->packer = nullptr; ix->packer = new vgp::Packer(host_threads); }
 		ix->packer->begin();
 		ix->fq_open = true; ix->fq_packed = true; ix->fq_prev_slot = -1;
+		ix->fq_sample = ix->cur_sample;                          // the stream stays with the sample selected now
 		return VG_OK;
 	});
 }
@@ -2737,7 +2791,7 @@ static int push_packed(vg_index *ix, const uint8_t *text, uint64_t nbytes)
 	HIP_TRY(hipSetDevice(ix->device));
 	if (ix->packer->poisoned()) return VG_OK;                 // refused earlier: the rest of the stream is the host reader's
 	Slot *slp = nullptr;
-	int rc = acquire_slot(ix, &slp);                            // (its previous batch has finished: the staging is free)
+	int rc = acquire_slot(ix, &slp, ix->fq_sample);            // (its previous batch has finished: the staging is free)
 	if (rc) return rc;
 	Slot &sl = *slp;
 	const uint64_t need_r = vgp::Packer::reads_cap(nbytes) + 1, need_k = vgp::Packer::kmers_cap(nbytes);
@@ -2747,7 +2801,7 @@ static int push_packed(vg_index *ix, const uint8_t *text, uint64_t nbytes)
 	const vgp::ChunkResult r = ix->packer->push(text, nbytes, st);
 	if (r.n_reads == 0) return VG_OK;                            // (a refused block poisons the stream; the records framed before it are still this batch)
 	rc = launch_packed(ix, sl, sl.hp_kmers.p, sl.hp_meta.p, sl.hp_offsets.p, r.n_reads, r.n_chunks, ix->ingest_or_main());
-	if (rc == VG_OK) ix->host_invalid += r.n_invalid;
+	if (rc == VG_OK) { ix->host_invalid += r.n_invalid; ix->planes[sl.plane].invalid += r.n_invalid; }
 	return rc;
 }
 
@@ -2758,6 +2812,7 @@ extern "C" int vg_fastq_stream_begin(vg_index *ix)
 	HIP_TRY(hipSetDevice(ix->device));
 	HIP_TRY(hipMemsetAsync(ix->d_fq, 0, sizeof(FqStream), ix->ingest_or_main()));
 	ix->fq_open = true; ix->fq_prev_slot = -1;
+	ix->fq_sample = ix->cur_sample;                              // the stream stays with the sample selected now
 	return VG_OK;
 }
 
@@ -2773,7 +2828,7 @@ extern "C" int vg_fastq_stream_push(vg_index *ix, const uint8_t *text, uint64_t 
 	HIP_TRY(hipSetDevice(ix->device));
 	const int slot_no = ix->next_slot;
 	Slot *slp = nullptr;
-	int rc = acquire_slot(ix, &slp);
+	int rc = acquire_slot(ix, &slp, ix->fq_sample);
 	if (rc) return rc;
 	Slot &sl = *slp;
 	hipStream_t is = ix->ingest_or_main();
@@ -3009,13 +3064,16 @@ extern "C" int vg_sites_fetch(vg_index *ix, uint32_t *pos, uint8_t *ref_base, ui
 	return VG_OK;
 }
 
+// the exact sums of the selected sample (vg_sample_select): what fetch, device_ptr and the all-reduces act on
+static uint32_t *sel_cnt(const vg_index *ix) { return ix->planes[ix->cur_sample].p.cnt; }
+
 extern "C" int vg_counts_fetch(vg_index *ix, uint8_t *ref_cnt, uint8_t *alt_cnt)
 {
 	if (!ix || !ref_cnt || !alt_cnt) return fail(VG_EINVAL, "null argument");
 	int rc = vg_sync(ix);
 	if (rc) return rc;
 	if (ix->n_sites == 0) return VG_OK;
-	vg_clamp_counters<<<(unsigned)std::min<uint64_t>((ix->n_sites + 255) / 256, 4096), 256, 0, ix->stream>>>(ix->d.cnt, ix->n_sites, ix->d_clamped, ix->d_clamped + ix->n_sites);
+	vg_clamp_counters<<<(unsigned)std::min<uint64_t>((ix->n_sites + 255) / 256, 4096), 256, 0, ix->stream>>>(sel_cnt(ix), ix->n_sites, ix->d_clamped, ix->d_clamped + ix->n_sites);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipMemcpyAsync(ref_cnt, ix->d_clamped, ix->n_sites, hipMemcpyDeviceToHost, ix->stream));
 	HIP_TRY(hipMemcpyAsync(alt_cnt, ix->d_clamped + ix->n_sites, ix->n_sites, hipMemcpyDeviceToHost, ix->stream));
@@ -3028,6 +3086,8 @@ extern "C" int vg_counts_reset(vg_index *ix)
 	if (!ix) return fail(VG_EINVAL, "null argument");
 	{ int rc = finish_pending(ix); if (rc) return rc; }
 	HIP_TRY(hipMemsetAsync(ix->d.cnt, 0, (2 * ix->n_sites + 2) * 4, ix->stream));
+	for (size_t s = 1; s < ix->planes.size(); s++) HIP_TRY(hipMemsetAsync(ix->planes[s].p.cnt, 0, 2 * ix->n_sites * 4, ix->stream));
+	for (Plane &pl : ix->planes) pl.invalid = 0;
 	HIP_TRY(hipMemsetAsync(ix->d_stats, 0, S_COUNT * sizeof(unsigned long long), ix->stream));
 	for (auto &c : ix->cum) c = 0;
 	ix->host_invalid = 0;
@@ -3039,7 +3099,72 @@ extern "C" int vg_counts_device_ptr(vg_index *ix, void **d_counts, uint64_t *n_u
 {
 	if (!ix || !d_counts || !n_u32) return fail(VG_EINVAL, "null argument");
 	{ int rc = finish_pending(ix); if (rc) return rc; }         // the sums are only meaningful once the batches in flight have landed
-	*d_counts = ix->d.cnt; *n_u32 = 2 * ix->n_sites;
+	*d_counts = sel_cnt(ix); *n_u32 = 2 * ix->n_sites;
+	return VG_OK;
+}
+
+// ---- sample planes (include/vargeno_hip.h): several samples against one resident index --------------------------------------
+extern "C" uint32_t vg_num_samples(const vg_index *ix) { return ix ? (uint32_t)ix->planes.size() : 0; }
+extern "C" uint32_t vg_sample_selected(const vg_index *ix) { return ix ? ix->cur_sample : 0; }
+extern "C" int vg_sample_select(vg_index *ix, uint32_t sample)
+{
+	if (!ix) return fail(VG_EINVAL, "null argument");
+	if (sample >= ix->planes.size()) return fail(VG_EINVAL, "sample %s is out of range: the handle has %s plane(s) (vg_samples_reserve)", std::to_string(sample).c_str(), std::to_string(ix->planes.size()).c_str());
+	ix->cur_sample = sample;
+	return VG_OK;
+}
+extern "C" int vg_samples_reserve(vg_index *ix, uint32_t n_samples)
+{
+	if (!ix) return fail(VG_EINVAL, "null argument");
+	if (n_samples < 1 || n_samples > VG_MAX_SAMPLES) return fail(VG_EINVAL, "vg_samples_reserve: 1 to 65535 samples");
+	if (n_samples < ix->planes.size()) return fail(VG_EINVAL, "vg_samples_reserve: planes only grow (the handle has %s)", std::to_string(ix->planes.size()).c_str());
+	{ int rc = finish_pending(ix); if (rc) return rc; }
+	return guarded([&]() -> int {
+		// all new planes first, the handle only changes when every one of them could be had
+		const size_t have = ix->planes.size(), bytes = (size_t)(24 * ix->n_sites + 16);
+		std::vector<void *> blk;
+		for (size_t s = have; s < n_samples; s++) {
+			void *q = nullptr;
+			const hipError_t e = vg_malloc_patient(&q, bytes);
+			if (e != hipSuccess || hipMemsetAsync(q, 0, bytes, ix->stream) != hipSuccess) {
+				(void)hipGetLastError();
+				(void)hipStreamSynchronize(ix->stream);
+				if (e == hipSuccess) (void)hipFree(q);
+				for (void *b : blk) (void)hipFree(b);
+				return fail(VG_ENOMEM, "vg_samples_reserve: no device memory for plane %s of %s bytes", std::to_string(s).c_str(), std::to_string(bytes).c_str());
+			}
+			blk.push_back(q);
+		}
+		std::vector<PlanePtr> tab;
+		for (void *q : blk) tab.push_back(PlanePtr{(uint32_t *)q + 4 * ix->n_sites + 4, (uint32_t *)q});
+		if (!tab.empty()) {
+			const hipError_t e = hipMemcpy(ix->d_planes + have, tab.data(), tab.size() * sizeof(PlanePtr), hipMemcpyHostToDevice);
+			if (e != hipSuccess || hipStreamSynchronize(ix->stream) != hipSuccess) { for (void *b : blk) (void)hipFree(b); return fail(VG_ENODEV, "vg_samples_reserve: %s", hipGetErrorString(e)); }
+		}
+		for (size_t i = 0; i < blk.size(); i++) {
+			ix->owned.push_back(blk[i]); ix->owned_bytes[blk[i]] = bytes; ix->dev_bytes += bytes;
+			Plane pl; pl.p = tab[i];
+			ix->planes.push_back(pl);
+		}
+		return VG_OK;
+	});
+}
+extern "C" int vg_sample_reset(vg_index *ix, uint32_t sample)
+{
+	if (!ix) return fail(VG_EINVAL, "null argument");
+	if (sample >= ix->planes.size()) return fail(VG_EINVAL, "sample %s is out of range", std::to_string(sample).c_str());
+	{ int rc = finish_pending(ix); if (rc) return rc; }              // (the fold leaves cnt4 zeroed)
+	HIP_TRY(hipMemsetAsync(ix->planes[sample].p.cnt, 0, 2 * ix->n_sites * 4, ix->stream));
+	HIP_TRY(hipStreamSynchronize(ix->stream));
+	ix->planes[sample].invalid = 0;
+	return VG_OK;
+}
+extern "C" int vg_sample_invalid_reads(vg_index *ix, uint32_t sample, uint64_t *out)
+{
+	if (!ix || !out) return fail(VG_EINVAL, "null argument");
+	if (sample >= ix->planes.size()) return fail(VG_EINVAL, "sample %s is out of range", std::to_string(sample).c_str());
+	{ int rc = finish_pending(ix); if (rc) return rc; }
+	*out = ix->planes[sample].invalid;
 	return VG_OK;
 }
 
@@ -3083,7 +3208,7 @@ extern "C" int vg_counts_allreduce(vg_index *ix, void *nccl_comm)
 	if (!R.ok) return fail(VG_ENODEV, "cannot load librccl (or it lacks the collective entry points)");
 	{ int rc = finish_pending(ix); if (rc) return rc; }
 	if (ix->n_sites == 0) return VG_OK;
-	const ncclResult_t rc = R.all_reduce(ix->d.cnt, ix->d.cnt, (size_t)(2 * ix->n_sites), ncclUint32, ncclSum, (ncclComm_t)nccl_comm, ix->stream);
+	const ncclResult_t rc = R.all_reduce(sel_cnt(ix), sel_cnt(ix), (size_t)(2 * ix->n_sites), ncclUint32, ncclSum, (ncclComm_t)nccl_comm, ix->stream);
 	if (rc != ncclSuccess) return fail(VG_ENODEV, "ncclAllReduce: %s", R.error_string(rc));
 	HIP_TRY(hipStreamSynchronize(ix->stream));
 	return VG_OK;
@@ -3104,6 +3229,7 @@ extern "C" int vg_counts_allreduce_devices(vg_index **handles, int n)
 	for (int i = 0; i < n; i++) {
 		if (!handles[i]) return fail(VG_EINVAL, "null handle");
 		if (handles[i]->n_sites != handles[0]->n_sites) return fail(VG_EINVAL, "the handles do not hold replicas of one index");
+		if (handles[i]->cur_sample != handles[0]->cur_sample) return fail(VG_EINVAL, "the handles have different samples selected (vg_sample_select): the exchange sums ONE sample's counters");
 		for (int j = 0; j < i; j++) if (handles[j] == handles[i]) return fail(VG_EINVAL, "the same handle twice");
 	}
 	const Rccl &R = rccl();
@@ -3118,7 +3244,7 @@ extern "C" int vg_counts_allreduce_devices(vg_index **handles, int n)
 			int add_into(int dst, int src)
 			{
 				if (hipSetDevice(h[dst]->device) != hipSuccess) return VG_ENODEV;
-				vg_add_counters<<<(unsigned)std::min<uint64_t>((words + 255) / 256, 4096), 256, 0, h[dst]->stream>>>(h[dst]->d.cnt, h[src]->d.cnt, words);
+				vg_add_counters<<<(unsigned)std::min<uint64_t>((words + 255) / 256, 4096), 256, 0, h[dst]->stream>>>(sel_cnt(h[dst]), sel_cnt(h[src]), words);
 				return hipGetLastError() == hipSuccess ? 0 : VG_ENODEV;
 			}
 			int comm_init(const int *devs, int nr) { comms.assign((size_t)nr, nullptr); last = R.comm_init_all(comms.data(), nr, devs); return last == ncclSuccess ? 0 : VG_ENODEV; }
@@ -3127,12 +3253,12 @@ extern "C" int vg_counts_allreduce_devices(vg_index **handles, int n)
 			int all_reduce(int i, int rank)
 			{
 				if (hipSetDevice(h[i]->device) != hipSuccess) { last = ncclUnhandledCudaError; return VG_ENODEV; }
-				last = R.all_reduce(h[i]->d.cnt, h[i]->d.cnt, (size_t)words, ncclUint32, ncclSum, comms[(size_t)rank], h[i]->stream);
+				last = R.all_reduce(sel_cnt(h[i]), sel_cnt(h[i]), (size_t)words, ncclUint32, ncclSum, comms[(size_t)rank], h[i]->stream);
 				return last == ncclSuccess ? 0 : VG_ENODEV;
 			}
 			int copy_from(int dst, int src)
 			{
-				return hipSetDevice(h[src]->device) == hipSuccess && hipMemcpyAsync(h[dst]->d.cnt, h[src]->d.cnt, words * 4, hipMemcpyDeviceToDevice, h[src]->stream) == hipSuccess ? 0 : VG_ENODEV;
+				return hipSetDevice(h[src]->device) == hipSuccess && hipMemcpyAsync(sel_cnt(h[dst]), sel_cnt(h[src]), words * 4, hipMemcpyDeviceToDevice, h[src]->stream) == hipSuccess ? 0 : VG_ENODEV;
 			}
 			int sync(int i) { return hipSetDevice(h[i]->device) == hipSuccess && hipStreamSynchronize(h[i]->stream) == hipSuccess ? 0 : VG_ENODEV; }
 			void comm_destroy() { for (ncclComm_t c : comms) if (c) (void)R.comm_destroy(c); comms.clear(); }

@@ -603,15 +603,28 @@ __device__ inline void bump_site(const DevIndex &d, uint32_t p, uint32_t which)
 {
 	atomicAdd(&d.cnt[2ull * site_id(d.srank[p >> 6], p) + which], 1u);
 }
+// ... into the counters of a sample plane (PlanePtr below): the lane machine's run over the late store, whose reads belong to
+// several samples, takes the base from the read's plane; every other launch passes d.cnt
+__device__ inline void bump_site(const DevIndex &d, uint32_t *__restrict__ cnt, uint32_t p, uint32_t which)
+{
+	atomicAdd(&cnt[2ull * site_id(d.srank[p >> 6], p) + which], 1u);
+}
+
+// One sample's pile-up counters (the per-sample state of qv.cc:1573-1626): `cnt` and `cnt4` as DevIndex has them.  Plane 0 is
+// DevIndex::cnt / cnt4 itself; a handle keeps a device-resident table of its planes, indexed by the sample number.
+struct PlanePtr {
+	uint32_t *cnt;                 // [2 * n_sites]
+	uint32_t *cnt4;                // [4 * n_sites + 4]
+};
 
 template <class ST>
-__device__ inline void walk_ctx(const DevIndex &d, ST &st, uint64_t kk, uint32_t kpos, uint32_t mod)
+__device__ inline void walk_ctx(const DevIndex &d, uint32_t *__restrict__ cnt, ST &st, uint64_t kk, uint32_t kpos, uint32_t mod)
 {
 	st.add(S_WALKS, 1);
 	if ((uint64_t)kpos + 32 > d.pile_len) return;          // cannot happen: pile_len = max position + 64
 	uint4 w4[2];
 	load_pile_window(d, kpos, w4);
-	walk_matches(w4, kk, kpos, mod, [&](uint32_t p, uint32_t which) { bump_site(d, p, which); st.add(S_INCR, 1); });
+	walk_matches(w4, kk, kpos, mod, [&](uint32_t p, uint32_t which) { bump_site(d, cnt, p, which); st.add(S_INCR, 1); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -636,11 +649,12 @@ struct Lane {
 	const DevIndex &d;
 	const Scratch &s;
 	uint32_t lane;                 // scratch column
+	uint32_t *cnt;                 // the counters this read's walks bump: d.cnt, or the read's sample plane (late store)
 	uint32_t nctx, nkeys;
 	int best; bool amb; bool overflow;
 	LaneStats<STATS> st;
 
-	__device__ Lane(const DevIndex &d_, const Scratch &s_, uint32_t lane_) : d(d_), s(s_), lane(lane_), nctx(0), nkeys(0), best(-1), amb(false), overflow(false) {}
+	__device__ Lane(const DevIndex &d_, const Scratch &s_, uint32_t lane_) : d(d_), s(s_), lane(lane_), cnt(d_.cnt), nctx(0), nkeys(0), best(-1), amb(false), overflow(false) {}
 
 	__device__ inline void reset_pass() { nctx = 0; nkeys = 0; best = -1; amb = false; }
 
@@ -809,7 +823,7 @@ struct Lane {
 			const uint32_t kpos = s.ctx_kpos[at];
 			const uint32_t meta = s.ctx_meta[at];
 			if (kpos - 32u * (meta >> 16) != target) continue;
-			walk_ctx(d, st, s.ctx_kmer[at], kpos, meta & 0xFFFFu);
+			walk_ctx(d, cnt, st, s.ctx_kmer[at], kpos, meta & 0xFFFFu);
 		}
 		return true;
 	}
