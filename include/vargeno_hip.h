@@ -224,6 +224,38 @@ int  vg_fastq_stream_begin_packed(vg_index *ix, int host_threads);
 int  vg_fastq_stream_push(vg_index *ix, const uint8_t *text, uint64_t nbytes);
 int  vg_fastq_stream_end(vg_index *ix, uint64_t *n_records, uint64_t *consumed, uint64_t *last_record_start, int *refused);
 
+/* The same device-framed stream over BGZF, the blocked gzip that bgzip / htslib write (gzip members of at most 64 KiB, each with
+ * its compressed size in a `BC` extra subfield and CRC32 + ISIZE in its trailer; a BGZF file is also a valid .gz).  After
+ * vg_fastq_stream_begin_bgzf, vg_fastq_stream_push takes BGZF bytes cut anywhere -- mid-header, mid-block, one byte at a time: the
+ * library keeps an incomplete block (at most 64 KiB) for the next push, walks the block headers on the host, copies the COMPRESSED
+ * bytes up and inflates them on the device, one wave per block, straight into the chunk's text buffer; framing and the read loop are
+ * those of the text stream.  A push whose text would pass the text chunks' limit is split at block boundaries.
+ * vg_fastq_stream_end reports records, consumed and last_record_start as offsets in the UNCOMPRESSED stream.  Bytes that are no
+ * BGZF block header (1f 8b 08 04, XLEN subfields with BC of length 2, BSIZE + 1 >= header + 8, ISIZE <= 65536) make the push
+ * return VG_EIO.  A block that fails on the device (deflate error / size / CRC), or an incomplete block left at the end, makes
+ * vg_fastq_stream_end return VG_EIO: vg_last_error() names the compressed offset and the reason, the out-parameters hold what was
+ * framed before it -- nothing of the chunk with the bad block or of later ones is -- and the handle stays usable.  A missing
+ * end-of-file marker block is accepted; an empty block anywhere is a block of zero bytes. */
+int  vg_fastq_stream_begin_bgzf(vg_index *ix);
+/* Where an uncompressed offset of the handle's last BGZF stream lies: compressed offset of its block and the offset inside the
+ * block's text (a host reader that takes over at last_record_start / consumed inflates from there).  The library keeps 16 bytes
+ * per block, valid until the next vg_fastq_stream_begin*.  text_offset = the end of the text seen: the offset behind the last
+ * whole block, 0. */
+int  vg_fastq_stream_bgzf_locate(vg_index *ix, uint64_t text_offset, uint64_t *block_offset, uint32_t *within);
+
+/* BGZF without a handle: the whole blocks of bgzf[0, nbytes) inflated into text[0, text_cap) in host memory -- on `device` by the
+ * stream's kernel (compressed bytes up, text back), or on the host by the host build of the same decoder.  *text_len = bytes of text
+ * written, *consumed = compressed bytes used (trailing bytes of an incomplete block are not), *bad_block_offset = compressed offset
+ * of the first block that failed (header, deflate error, size or CRC; UINT64_MAX: none) -- the text of the blocks before it is
+ * there, *consumed stops at it, vg_last_error() has the reason, and the call still returns VG_OK.  VG_ETOOBIG: the text does not
+ * fit text_cap (nothing is written beyond it).  Buffers of less than 4 GiB.  With VG_VERBOSE set the device form prints the
+ * kernel's own time and rate. */
+int  vg_bgzf_inflate_device(int device, const uint8_t *bgzf, uint64_t nbytes, uint8_t *text, uint64_t text_cap, uint64_t *text_len, uint64_t *consumed, uint64_t *bad_block_offset);
+int  vg_bgzf_inflate_host(const uint8_t *bgzf, uint64_t nbytes, uint8_t *text, uint64_t text_cap, uint64_t *text_len, uint64_t *consumed, uint64_t *bad_block_offset);
+/* The header walk alone: every whole block of bgzf[0, nbytes) as six numbers in blocks[6 * i ..]: compressed offset, text offset,
+ * payload offset, payload length, ISIZE, CRC32.  *consumed / *bad_block_offset as above (header errors only). */
+int  vg_bgzf_scan_host(const uint8_t *bgzf, uint64_t nbytes, uint64_t *blocks, uint64_t blocks_cap, uint64_t *n_blocks, uint64_t *consumed, uint64_t *bad_block_offset);
+
 /* One self-contained chunk, synchronously: *consumed = bytes used (the rest, an incomplete last record, is the caller's to
  * resubmit with the next chunk); waits for the framing, not for the read loop.  VG_EBADREAD: the chunk was refused (see above);
  * nothing was processed. */

@@ -22,7 +22,8 @@ SYMBOLS = ["vg_last_error", "vg_build_id", "vg_device_count", "vg_device_memory"
            "vg_packer_create", "vg_packer_destroy", "vg_packer_begin", "vg_packer_reads_cap", "vg_packer_kmers_cap", "vg_packer_push", "vg_packer_end", "vg_sync", "vg_stats_get",
            "vg_set_stats", "vg_timing_get", "vg_num_sites", "vg_sites_fetch", "vg_counts_fetch", "vg_counts_reset",
            "vg_counts_device_ptr", "vg_counts_allreduce", "vg_counts_allreduce_devices",
-           "vg_samples_reserve", "vg_num_samples", "vg_sample_select", "vg_sample_selected", "vg_sample_reset", "vg_sample_invalid_reads"]
+           "vg_samples_reserve", "vg_num_samples", "vg_sample_select", "vg_sample_selected", "vg_sample_reset", "vg_sample_invalid_reads",
+           "vg_fastq_stream_begin_bgzf", "vg_fastq_stream_bgzf_locate", "vg_bgzf_inflate_device", "vg_bgzf_inflate_host", "vg_bgzf_scan_host"]
 
 
 class VgStats(C.Structure):
@@ -155,6 +156,11 @@ def lib():
         except AttributeError:
             if not os.environ.get("VARGENO_HIP_LIB"):                   # (an older build loaded for an A/B run has no sample planes)
                 raise
+        L.vg_fastq_stream_begin_bgzf.argtypes = [vp]
+        L.vg_fastq_stream_bgzf_locate.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+        L.vg_bgzf_inflate_device.argtypes = [C.c_int, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.vg_bgzf_inflate_host.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.vg_bgzf_scan_host.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         # The library is a build product that travels next to its sources (not in git): refuse a stale one.  Its build id is the
         # sha256 of the sources it was compiled from (csrc/Makefile); VARGENO_HIP_LIB (A/B variants) opts out.
         if not os.environ.get("VARGENO_HIP_LIB"):

@@ -150,12 +150,16 @@ class GenoIndex:
         check(lib().vg_reads_submit_store(self._h, store._h))
         self._stores.append(store)        # (released by sync / counts / stats / close: the batches read the store's memory until then)
 
-    def fastq_stream(self, chunks, host_threads=None):
+    def fastq_stream(self, chunks, host_threads=None, bgzf=False):
         """FASTQ text as a stream of byte chunks cut anywhere (numpy uint8 arrays / bytes; pinned host memory copies at link
         speed): records are framed across the cuts -- on the device (host_threads None or 0), or framed and 2-bit packed by
         that many host threads inside the library (-1: the library picks).  Returns (records, bytes consumed, start of the
-        last framed record, refused) once everything pushed has been processed."""
-        if host_threads is None:
+        last framed record, refused) once everything pushed has been processed.
+        bgzf=True: the chunks are BGZF bytes (cut anywhere too), inflated on the device; the offsets returned are offsets in the
+        uncompressed text.  A bad block raises VgError (VG_EIO) naming its compressed offset; what was framed before it counts."""
+        if bgzf:
+            check(lib().vg_fastq_stream_begin_bgzf(self._h))
+        elif host_threads is None:
             check(lib().vg_fastq_stream_begin(self._h))
         else:
             check(lib().vg_fastq_stream_begin_packed(self._h, int(host_threads)))
@@ -165,6 +169,12 @@ class GenoIndex:
         n, used, last, refused = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_int()
         check(lib().vg_fastq_stream_end(self._h, C.byref(n), C.byref(used), C.byref(last), C.byref(refused)))
         return int(n.value), int(used.value), int(last.value), bool(refused.value)
+
+    def bgzf_locate(self, text_offset):
+        """(compressed offset of the block, offset inside its text) of an uncompressed offset of the last BGZF stream."""
+        block, within = C.c_uint64(), C.c_uint32()
+        check(lib().vg_fastq_stream_bgzf_locate(self._h, int(text_offset), C.byref(block), C.byref(within)))
+        return int(block.value), int(within.value)
 
     def process_device(self, d_bases, d_quals, d_offsets, n_reads):
         """Device-resident batch: torch CUDA tensors (uint8, uint8, int64/uint64 offsets[n+1])."""
@@ -363,6 +373,40 @@ class ReadStore:
             self.close()
         except Exception:
             pass
+
+
+def _u8(data):
+    return np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+
+
+def bgzf_scan(data):
+    """The BGZF header walk (host): ([(compressed offset, text offset, payload offset, payload length, ISIZE, CRC32), ...] of the
+    whole blocks, bytes consumed, compressed offset of bytes that are no BGZF header or None)."""
+    a = _u8(data)
+    cap = len(a) // 20 + 1                                     # a block is at least 20 bytes
+    tab = np.zeros(6 * cap, dtype=np.uint64)
+    n, used, bad = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    check(lib().vg_bgzf_scan_host(_ptr(a), len(a), _ptr(tab), cap, C.byref(n), C.byref(used), C.byref(bad)))
+    blocks = [tuple(int(v) for v in tab[6 * i:6 * i + 6]) for i in range(int(n.value))]
+    return blocks, int(used.value), (None if bad.value == 2 ** 64 - 1 else int(bad.value))
+
+
+def bgzf_inflate(data, device=0, out=None, text_cap=None):
+    """The whole BGZF blocks of `data` inflated: on `device` by the stream's kernel, or (device=None) by the host build of the
+    same decoder.  Returns (text as bytes, compressed bytes consumed, compressed offset of the first bad block or None); the
+    text stops before a bad block.  out / text_cap: a caller's uint8 buffer and how much of it may be written (default: a new
+    buffer of the blocks' ISIZE sum)."""
+    a = _u8(data)
+    if text_cap is None:
+        text_cap = sum(b[4] for b in bgzf_scan(a)[0]) if out is None else len(out)
+    if out is None:
+        out = np.zeros(max(1, text_cap), dtype=np.uint8)
+    n, used, bad = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    if device is None:
+        check(lib().vg_bgzf_inflate_host(_ptr(a), len(a), _ptr(out), int(text_cap), C.byref(n), C.byref(used), C.byref(bad)))
+    else:
+        check(lib().vg_bgzf_inflate_device(int(device), _ptr(a), len(a), _ptr(out), int(text_cap), C.byref(n), C.byref(used), C.byref(bad)))
+    return out[:int(n.value)].tobytes(), int(used.value), (None if bad.value == 2 ** 64 - 1 else int(bad.value))
 
 
 def pinned_buffer(nbytes):

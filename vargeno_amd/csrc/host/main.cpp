@@ -71,6 +71,7 @@
 
 #include "../../../include/vargeno_hip.h"
 #include "vg_host.h"
+#include "bgzf.cpp"       // the host side of the BGZF routes, in this translation unit (csrc/Makefile: builds that list the four host files get it)
 
 static void print_help()
 {
@@ -125,6 +126,10 @@ struct GenoOptions {
 	const int cohort_inflight = std::max(1, env_int("VARGENO_COHORT_INFLIGHT", 4));      // cohort: samples in flight together = sample planes per replica
 	const bool force_rccl = env_int("VARGENO_FORCE_RCCL", 0) != 0, orderly_exit = env_int("VARGENO_ORDERLY_EXIT", 0) != 0, fqpipe_quiet = env_int("VARGENO_FQPIPE_QUIET", 0) != 0;
 	const char *const dump_counts = getenv("VARGENO_DUMP_COUNTS");
+	// BGZF input: host threads that inflate (BgzfTextPipe), and the route of one replica -- `device`: compressed bytes cross the link
+	// and are inflated there; `host` (the default until profiles/bgzf_ingest.txt says otherwise): inflated here, then the once-only route
+	const int bgzf_threads = std::max(1, std::min(env_int("VARGENO_BGZF_THREADS", vgh::bgzf_threads_default(hw)), 256));
+	const bool bgzf_device = std::string(env_str("VARGENO_BGZF")) == "device";
 	explicit GenoOptions(int devices) : have(devices)
 	{
 		if (ngpu > have && !share) ngpu = have;
@@ -208,7 +213,8 @@ struct StreamResult {
 	int refused = 0;
 	std::string error;                                               // empty: fine
 };
-static StreamResult stream_range(vg_index *ix, int fd, uint64_t lo, uint64_t hi, uint64_t chunk, int n_readers, int pack_threads)
+// bgzf: the bytes are BGZF (vg_fastq_stream_begin_bgzf) -- the same ring over the compressed file; the result's offsets are text offsets.
+static StreamResult stream_range(vg_index *ix, int fd, uint64_t lo, uint64_t hi, uint64_t chunk, int n_readers, int pack_threads, bool bgzf = false)
 {
 	StreamResult res;
 	const int NBUF = 4;
@@ -219,7 +225,7 @@ static StreamResult stream_range(vg_index *ix, int fd, uint64_t lo, uint64_t hi,
 		if (!ring[(size_t)i]) { pageable[(size_t)i].resize((size_t)chunk); ring[(size_t)i] = pageable[(size_t)i].data(); }
 	}
 	RangeReader rr(fd, lo, hi, chunk, n_readers, ring);
-	int rc = pack_threads > 0 ? vg_fastq_stream_begin_packed(ix, pack_threads) : vg_fastq_stream_begin(ix);
+	int rc = bgzf ? vg_fastq_stream_begin_bgzf(ix) : pack_threads > 0 ? vg_fastq_stream_begin_packed(ix, pack_threads) : vg_fastq_stream_begin(ix);
 	for (uint64_t i = 0; i < rr.n_chunks() && rc == VG_OK; i++) {
 		if (!rr.wait(i)) break;
 		rc = vg_fastq_stream_push(ix, rr.buf(i), rr.chunk_len(i));
@@ -616,6 +622,14 @@ struct FastqInput {
 	bool once_only = false;                    // a FIFO, /dev/stdin, <(...): one descriptor, read once, no ranges (PipeIngest)
 	bool cuts_ok = false;                      // a regular file, and cut[] holds a record-aligned range per replica
 	std::vector<uint64_t> cut;
+	bool bgzf_device = false;                  // a BGZF file, one replica, VARGENO_BGZF=device: the compressed bytes are streamed to the device
+	std::unique_ptr<vgh::BgzfTextPipe> bz_pipe;   // a BGZF file on every other route: inflated by host threads; fd is the pipe's read end
+	int file_fd = -1;                          // ... and the file itself
+};
+// Bytes of a once-only stream that are still in memory, for the host reader: [base, base + the spans); the descriptor continues behind them
+struct HostSpans {
+	uint64_t base = 0;
+	std::vector<std::pair<const uint8_t *, size_t>> spans;
 };
 // What an ingest route hands to the host reader that runs behind it
 struct HostHandover {
@@ -636,13 +650,23 @@ static uint64_t read_store_bytes(const GenoOptions &o, int g, uint64_t bound)
 // false: the path cannot be opened (said on stderr)
 static bool open_fastq(const std::string &fastq, const GenoOptions &o, FastqInput &in)
 {
-	if (o.host_framing) return true;
+	struct stat sb;
+	if (o.host_framing && (stat(fastq.c_str(), &sb) != 0 || !S_ISREG(sb.st_mode))) return true;     // (the host reader opens the path itself, once)
 	in.fd = open(fastq.c_str(), O_RDONLY);
 	if (in.fd < 0) { fprintf(stderr, "vargeno: cannot open %s\n", fastq.c_str()); return false; }
-	struct stat sb;
 	if (fstat(in.fd, &sb) != 0) { close(in.fd); fprintf(stderr, "vargeno: cannot stat %s\n", fastq.c_str()); return false; }
 	in.fsize = (uint64_t)sb.st_size;
 	in.once_only = !S_ISREG(sb.st_mode);
+	// a regular file says what it is (a FIFO or /dev/stdin cannot be looked at without taking its bytes: it is text, as before)
+	if (!in.once_only && vgh::sniff_fastq(in.fd) == vgh::FastqKind::Bgzf) {
+		if (o.bgzf_device && o.ngpu == 1 && !o.host_framing) { in.bgzf_device = true; return true; }
+		in.file_fd = in.fd;
+		in.bz_pipe.reset(new vgh::BgzfTextPipe(in.file_fd, 0, 0, o.bgzf_threads));
+		if (in.bz_pipe->read_fd() < 0) { fprintf(stderr, "vargeno: %s\n", in.bz_pipe->error.c_str()); return false; }
+		in.fd = in.bz_pipe->read_fd();
+		in.once_only = true;
+	}
+	if (o.host_framing) { if (!in.bz_pipe) { close(in.fd); in.fd = -1; } return true; }
 	if (in.once_only) (void)fcntl(in.fd, F_SETPIPE_SZ, 1 << 20);        // (a pipe: the largest buffer an unprivileged process may ask for; fails harmlessly on anything else)
 	else in.cuts_ok = range_cuts(in.fd, in.fsize, o.ngpu, in.cut);
 	return true;
@@ -806,16 +830,56 @@ static HostHandover once_only_route(const GenoOptions &o, PipeIngest &pipe_in, c
 	return HostHandover{pipe_in.records, pipe_in.consumed, pipe_in.records ? pipe_in.last : UINT64_MAX, 0};
 }
 
+// One replica, a BGZF file, VARGENO_BGZF=device: the compressed file goes to the device through the text route's reader ring
+// (vg_fastq_stream_begin_bgzf); no pre-packers, no read store -- reading the file ahead while the index opens is all the overlap.
+// The host take-over behind it (a framing refusal, a truncated final record) needs TEXT from the last framed record on:
+// vg_fastq_stream_bgzf_locate says which block holds it, the blocks up to the hand-over point are inflated here into a memory
+// span, and a BgzfTextPipe inflates the rest of the file into a pipe -- the span plus a descriptor, what the host reader takes.
+struct BgzfTakeover {
+	std::vector<uint8_t> text;
+	std::unique_ptr<vgh::BgzfTextPipe> rest;
+	HostSpans mem;
+};
+static HostHandover bgzf_device_route(const GenoOptions &o, const FastqInput &in, vg_index *ix, BgzfTakeover &tk)
+{
+	struct timespec a, b; clock_gettime(CLOCK_MONOTONIC, &a);
+	const StreamResult r = stream_range(ix, in.fd, 0, in.fsize, o.chunk(16), o.range_readers(), 0, true);
+	if (!r.error.empty()) { fprintf(stderr, "vargeno: %s\n", r.error.c_str()); exit(EXIT_FAILURE); }
+	clock_gettime(CLOCK_MONOTONIC, &b);
+	const uint64_t from = r.nrec ? r.last : r.used;                      // the span starts with the last framed record (it primes the stale buffers)
+	uint64_t block = 0, comp_next = 0;
+	uint32_t within = 0;
+	VG_CHECK(vg_fastq_stream_bgzf_locate(ix, from, &block, &within));
+	std::string err;
+	if (!vgh::bgzf_inflate_span(in.fd, block, within + (r.used - from), tk.text, &comp_next, err)) { fprintf(stderr, "vargeno: %s\n", err.c_str()); exit(EXIT_FAILURE); }
+	tk.mem.base = from - within;
+	tk.mem.spans.assign(1, std::make_pair((const uint8_t *)tk.text.data(), tk.text.size()));
+	tk.rest.reset(new vgh::BgzfTextPipe(in.fd, comp_next, 0, o.bgzf_threads));
+	if (tk.rest->read_fd() < 0) { fprintf(stderr, "vargeno: %s\n", tk.rest->error.c_str()); exit(EXIT_FAILURE); }
+	if (o.verbose) fprintf(stderr, "ingest, replica 0: BGZF inflated on the device: %lu reads framed, %.3f GB compressed (%.2f GB/s), %.3f GB of text (%.2f GB/s) in %.2f s%s\n", (unsigned long)r.nrec,
+	                       (double)in.fsize / 1e9, (double)in.fsize / 1e9 / secs(a, b), (double)r.used / 1e9, (double)r.used / 1e9 / secs(a, b), secs(a, b), r.refused ? "; the stream framing refused a chunk: the host reader takes the rest" : "");
+	return HostHandover{r.nrec, r.used, r.nrec ? r.last : UINT64_MAX, 0};
+}
+// a BgzfTextPipe has met the end of its text: what it has to say (false: a bad block, said on stderr)
+static bool bgzf_pipe_verdict(const GenoOptions &o, vgh::BgzfTextPipe &bp, const char *what)
+{
+	bp.finish();
+	if (!bp.error.empty()) { fprintf(stderr, "vargeno: %s\n", bp.error.c_str()); return false; }
+	if (o.verbose) fprintf(stderr, "ingest, %s: BGZF inflated by %d host threads: %.3f GB compressed (%.2f GB/s), %.3f GB of text (%.2f GB/s) in %.2f s\n", what, o.bgzf_threads,
+	                       (double)bp.comp_bytes / 1e9, bp.seconds > 0 ? (double)bp.comp_bytes / 1e9 / bp.seconds : 0.0, (double)bp.text_bytes / 1e9, bp.seconds > 0 ? (double)bp.text_bytes / 1e9 / bp.seconds : 0.0, bp.seconds);
+	return true;
+}
+
 // The host reader: the file from hand.host_from on -- or, for a stream that is read once, the bytes still in memory and then the
 // descriptor (never a second open: a FIFO has lost its writer by then).  Returns the job's reads: the route's and its own.
 // submit(replica, batch, n): hands a host-framed batch to a replica's read loop (`geno`: vg_reads_submit; `cohort`: the same after
 // selecting the sample's plane, under the replica's mutex).  whole_file: VARGENO_HOST_FASTQ=1, no route ran before.
 typedef std::function<void(int, const vgh::ReadBatch &, uint64_t)> BatchSubmit;
-static uint64_t host_reader_tail(const GenoOptions &o, const std::string &fastq, int fd, const PipeIngest *pipe_in, const HostHandover &hand, bool whole_file, const BatchSubmit &submit)
+static uint64_t host_reader_tail(const GenoOptions &o, const std::string &fastq, int fd, const HostSpans *mem, const HostHandover &hand, bool whole_file, const BatchSubmit &submit)
 {
 	uint64_t total = hand.total;
 	int next_gpu = hand.next_gpu;
-	std::unique_ptr<vgh::FastqReader> rdp(pipe_in ? new vgh::FastqReader(fd, pipe_in->span_base, pipe_in->spans) : new vgh::FastqReader(fastq));
+	std::unique_ptr<vgh::FastqReader> rdp(mem ? new vgh::FastqReader(fd, mem->base, mem->spans) : new vgh::FastqReader(fastq));
 	vgh::FastqReader &rd = *rdp;
 	vgh::ReadBatch rb;
 	if (!whole_file && hand.prime_from != UINT64_MAX) {       // re-read the last framed record: it only fills the line buffers
@@ -892,10 +956,24 @@ static void verbose_report(uint64_t total, int ngpu, const struct timespec t[4])
 	}
 }
 
+// A regular file with gzip magic but no BGZF header: refused by name (framed as text it would yield garbage).  Said on stderr.
+static bool plain_gzip(const std::string &fastq)
+{
+	struct stat sb;
+	if (stat(fastq.c_str(), &sb) != 0 || !S_ISREG(sb.st_mode)) return false;      // (a FIFO is opened once, by its reader)
+	const int fd = open(fastq.c_str(), O_RDONLY);
+	if (fd < 0) return false;                                          // (open_fastq says so)
+	const bool plain = vgh::sniff_fastq(fd) == vgh::FastqKind::PlainGzip;
+	close(fd);
+	if (plain) fprintf(stderr, "vargeno: %s is gzip but not BGZF: only BGZF (bgzip) is inflated here -- recompress with bgzip, or pass <(zcat %s)\n", fastq.c_str(), fastq.c_str());
+	return plain;
+}
+
 static int run_geno(const std::string &prefix, const std::string &fastq, const std::string &vcf_in, const std::string &vcf_out)
 {
 	const clock_t begin = clock();
 	struct timespec t[4]; clock_gettime(CLOCK_MONOTONIC, &t[0]);       // the start; then: index loaded, reads counted, VCF written
+	if (plain_gzip(fastq)) return EXIT_FAILURE;                        // (before the index or a device is asked for)
 	std::vector<vgh::ChrLen> chrlens = vgh::read_chrlens(prefix + ".chrlens");
 	const int have = vg_device_count();
 	if (have <= 0) { fprintf(stderr, "vargeno: no HIP device found (this build has no CPU path)\n"); return EXIT_FAILURE; }
@@ -910,8 +988,8 @@ static int run_geno(const std::string &prefix, const std::string &fastq, const s
 	std::vector<vg_index *> ix((size_t)o.ngpu, nullptr);
 	std::unique_ptr<PipeIngest> pipe_in;
 	std::vector<std::unique_ptr<PrePacker>> pre;
-	if (in.once_only) pipe_in = start_pipe_ingest(o, in.fd, store, ix);
-	else pre = start_prepackers(o, in, store);
+	if (in.once_only && !o.host_framing) pipe_in = start_pipe_ingest(o, in.fd, store, ix);
+	else if (!in.bgzf_device && !o.host_framing) pre = start_prepackers(o, in, store);
 	// the SNP list is read now, beside the index open (the VCF pass at the end of the job starts from its bytes)
 	std::string vcf_text;
 	bool vcf_ok = false;
@@ -925,15 +1003,23 @@ static int run_geno(const std::string &prefix, const std::string &fastq, const s
 	clock_gettime(CLOCK_MONOTONIC, &t[1]);
 	// ---- one ingest route (ranged_route has the long story), then the host reader for whatever the route left
 	HostHandover hand;
-	if (pipe_in) hand = once_only_route(o, *pipe_in, ix, store);
+	HostSpans mem;
+	const HostSpans *reader_mem = nullptr;                              // what the host reader starts from (null: it opens the path)
+	int reader_fd = in.fd;
+	BgzfTakeover tk;
+	if (pipe_in) { hand = once_only_route(o, *pipe_in, ix, store); mem.base = pipe_in->span_base; mem.spans = pipe_in->spans; reader_mem = &mem; }
+	else if (in.bgzf_device) { hand = bgzf_device_route(o, in, ix[0], tk); reader_mem = &tk.mem; reader_fd = tk.rest->read_fd(); }
 	else if (!o.host_framing) {
 		hand = ranged_route(o, in, ix, store, pre);
 		pre.clear();
 		close(in.fd);
-	}
-	const uint64_t total = host_reader_tail(o, fastq, in.fd, pipe_in.get(), hand, o.host_framing, [&ix](int g, const vgh::ReadBatch &rb, uint64_t n) {
+	} else if (in.bz_pipe) reader_mem = &mem;                           // VARGENO_HOST_FASTQ=1 on a BGZF file: the host reader reads the inflated text from its start
+	const uint64_t total = host_reader_tail(o, fastq, reader_fd, reader_mem, hand, o.host_framing, [&ix](int g, const vgh::ReadBatch &rb, uint64_t n) {
 		VG_CHECK(vg_reads_submit(ix[(size_t)g], rb.bases.data(), rb.quals.data(), rb.offsets.data(), n));
 	});
+	// a bad block ends a BgzfTextPipe's text early: no VCF from half a file
+	if (in.bz_pipe && !bgzf_pipe_verdict(o, *in.bz_pipe, "all replicas")) return EXIT_FAILURE;
+	if (tk.rest && !bgzf_pipe_verdict(o, *tk.rest, "the host reader's tail")) return EXIT_FAILURE;
 	for (auto *h : ix) VG_CHECK(vg_sync(h));
 	clock_gettime(CLOCK_MONOTONIC, &t[2]);
 	vgh::SiteCounts sc;
@@ -1024,10 +1110,17 @@ static int run_cohort(const std::string &prefix, const std::string &manifest, co
 			if (at >= samples.size()) return;
 			const CohortSample &s = samples[at];
 			struct timespec a; clock_gettime(CLOCK_MONOTONIC, &a);
-			const int fd = open(s.fastq.c_str(), O_RDONLY);
-			if (fd < 0) { fprintf(stderr, "vargeno: %s line %d: cannot open %s\n", manifest.c_str(), s.line, s.fastq.c_str()); failed.store(1); continue; }
+			if (plain_gzip(s.fastq)) { failed.store(1); continue; }
+			const int file_fd = open(s.fastq.c_str(), O_RDONLY);
+			if (file_fd < 0) { fprintf(stderr, "vargeno: %s line %d: cannot open %s\n", manifest.c_str(), s.line, s.fastq.c_str()); failed.store(1); continue; }
+			// a BGZF sample is inflated by host threads into a pipe: the once-only route below takes the pipe's descriptor in place of the file's
+			std::unique_ptr<vgh::BgzfTextPipe> bz;
+			struct stat sb;
+			if (fstat(file_fd, &sb) == 0 && S_ISREG(sb.st_mode) && vgh::sniff_fastq(file_fd) == vgh::FastqKind::Bgzf) bz.reset(new vgh::BgzfTextPipe(file_fd, 0, 0, std::max(1, o.bgzf_threads / K)));
+			const int fd = bz ? bz->read_fd() : file_fd;
 			(void)fcntl(fd, F_SETPIPE_SZ, 1 << 20);
 			uint64_t total = 0;
+			bool bz_ok = true;
 			{
 				PipeIngest pin(fd, o.pipe_chunk(), std::max(1, o.pack_threads / K), o.pipe_copiers, no_store,
 				               [&](size_t g, const uint64_t *k, const uint64_t *m, const uint64_t *off, uint64_t n) -> std::string {
@@ -1040,13 +1133,16 @@ static int run_cohort(const std::string &prefix, const std::string &manifest, co
 				if (!pin.error.empty()) { fprintf(stderr, "vargeno: %s line %d: %s\n", manifest.c_str(), s.line, pin.error.c_str()); exit(EXIT_FAILURE); }
 				// what the packer refused, and the possibly truncated tail: the host reader, into the same plane
 				const HostHandover hand{pin.records, pin.consumed, pin.records ? pin.last : UINT64_MAX, 0};
-				total = host_reader_tail(o, s.fastq, fd, &pin, hand, false, [&](int g, const vgh::ReadBatch &rb, uint64_t n) {
+				const HostSpans mem{pin.span_base, pin.spans};
+				total = host_reader_tail(o, s.fastq, fd, &mem, hand, false, [&](int g, const vgh::ReadBatch &rb, uint64_t n) {
 					std::lock_guard<std::mutex> lock(mu[(size_t)g]);
 					VG_CHECK(vg_sample_select(ix[(size_t)g], plane));
 					VG_CHECK(vg_reads_submit(ix[(size_t)g], rb.bases.data(), rb.quals.data(), rb.offsets.data(), n));
 				});
+				if (bz) { bz->finish(); if (!bz->error.empty()) { fprintf(stderr, "vargeno: %s line %d: %s: no VCF written\n", manifest.c_str(), s.line, bz->error.c_str()); bz_ok = false; } }
 			}
-			close(fd);
+			bz.reset();
+			close(file_fd);
 			// the sample is complete: its plane summed over the replicas, fetched and zeroed for the worker's next sample
 			vgh::SiteCounts sc;
 			uint64_t invalid = 0;
@@ -1054,10 +1150,11 @@ static int run_cohort(const std::string &prefix, const std::string &manifest, co
 				for (auto &m : mu) m.lock();
 				for (auto *h : ix) VG_CHECK(vg_sample_select(h, plane));
 				for (auto *h : ix) { uint64_t bad = 0; VG_CHECK(vg_sample_invalid_reads(h, plane, &bad)); invalid += bad; }
-				if (!invalid) fetch_selected_counts(o, ix, sc);
+				if (!invalid && bz_ok) fetch_selected_counts(o, ix, sc);
 				for (auto *h : ix) VG_CHECK(vg_sample_reset(h, plane));
 				for (auto &m : mu) m.unlock();
 			}
+			if (!bz_ok) { failed.store(1); continue; }
 			if (invalid) {
 				// util.c:103: the reference aborts on such a read and writes no VCF; the other samples go on
 				fprintf(stderr, "vargeno: %s line %d: %lu reads of %s contain a character other than ACGTN (the reference aborts on these): no VCF written\n", manifest.c_str(), s.line, (unsigned long)invalid, s.fastq.c_str());
@@ -1099,6 +1196,24 @@ int main(int argc, const char *argv[])
 		} else if (opt == "cohort") {
 			arg_check(argc, 3);
 			return run_cohort(argv[2], argv[3], argv[4]);
+		} else if (opt == "bgzfcat") {
+			// hidden: a BGZF file's text on stdout, inflated by the host threads of the BgzfTextPipe (no device needed; tests/test_bgzf_cpu.py)
+			arg_check(argc, 1);
+			if (plain_gzip(argv[2])) return EXIT_FAILURE;
+			const int fd = open(argv[2], O_RDONLY);
+			if (fd < 0) throw vgh::Error{std::string("cannot open ") + argv[2]};
+			vgh::BgzfTextPipe bp(fd, 0, 0, std::max(1, std::min(env_int("VARGENO_BGZF_THREADS", vgh::bgzf_threads_default(usable_cpus())), 256)));
+			if (bp.read_fd() < 0) throw vgh::Error{bp.error};
+			std::vector<uint8_t> buf(1 << 20);
+			for (;;) {
+				const ssize_t n = read(bp.read_fd(), buf.data(), buf.size());
+				if (n < 0 && errno == EINTR) continue;
+				if (n <= 0) break;
+				if (fwrite(buf.data(), 1, (size_t)n, stdout) != (size_t)n) throw vgh::Error{"cannot write to stdout"};
+			}
+			bp.finish();
+			if (!bp.error.empty()) throw vgh::Error{bp.error};
+			return EXIT_SUCCESS;
 		} else if (opt == "fqcheck") {
 			// hidden: the host FASTQ framing alone -- one line per record: read length, then the read and the quality
 			// characters the path can see (no device needed; tests/test_host_tools.py)

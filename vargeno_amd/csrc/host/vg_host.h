@@ -47,6 +47,36 @@ private:
 	Impl *p;
 };
 
+// ---- BGZF-compressed FASTQ on the host (bgzf.cpp; the decoder is ../vg_inflate.h, shared with the device kernel) ----
+enum class FastqKind { Text, Bgzf, PlainGzip };
+// what a regular file's first bytes say: BGZF (gzip magic with the `BC` subfield), some other gzip, or anything else (text)
+FastqKind sniff_fastq(int fd);
+// VARGENO_BGZF_THREADS' default: min(usable CPUs, 8)
+int bgzf_threads_default(int usable_cpus);
+// A BGZF file as a once-only text descriptor: from compressed offset comp_from (a block start) on, `threads` host threads inflate
+// the blocks, in order, into a pipe; the first `skip` bytes of text are dropped.  read_fd() is an ordinary FASTQ descriptor (owned
+// by the object: it must outlive its reader).  After the reader has met the end of the text, finish() and look at `error`: a bad or
+// incomplete block ends the text early and is named there, with its compressed offset.
+// read_fd() < 0: no pipe could be made (error says so).
+class BgzfTextPipe {
+public:
+	BgzfTextPipe(int fd, uint64_t comp_from, uint32_t skip, int threads);
+	~BgzfTextPipe();
+	BgzfTextPipe(const BgzfTextPipe &) = delete;
+	BgzfTextPipe &operator=(const BgzfTextPipe &) = delete;
+	int read_fd() const;
+	void finish();
+	std::string error;
+	uint64_t comp_bytes = 0, text_bytes = 0;       // valid after finish()
+	double seconds = 0.0;                          // from construction to the end of the text
+private:
+	struct Impl;
+	Impl *p;
+};
+// The blocks from compressed offset comp_from on, inflated on this thread until they hold more than want_text bytes (or the file
+// ends); *comp_next = offset of the block after them.  false: err says which block is bad.
+bool bgzf_inflate_span(int fd, uint64_t comp_from, uint64_t want_text, std::vector<uint8_t> &text, uint64_t *comp_next, std::string &err);
+
 // ---- caller + VCF writer (behaviour of reference src/qv.cc:1573-1747, 1789-1848) ---------------
 enum : uint8_t { GT_NONE = 0, GT_HOM_REF = 1, GT_HOM_ALT = 2, GT_HET = 3 };     // numbering of the reference's GTYPE_* (vartype.h)
 struct Genotype {

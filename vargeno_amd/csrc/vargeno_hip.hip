@@ -12,6 +12,7 @@
 #include "vg_hostpack.h"
 #include "vg_allreduce_plan.h"
 #include "vg_arena.h"
+#include "vg_inflate.h"
 
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -736,12 +737,14 @@ struct FqChunk {                                     // one per batch slot, devi
 	unsigned long long total;                        // bases of the batch
 };
 
-// carried bytes in front of the new text; start / length of the chunk's text
-__global__ __launch_bounds__(256) void vg_fqs_prepare(const FqStream *__restrict__ st, FqChunk *__restrict__ ck, const uint8_t *__restrict__ prev_end, uint8_t *__restrict__ buf, uint32_t nbytes)
+// carried bytes in front of the new text; start / length of the chunk's text.  bad_key (BGZF streams, else null): the inflate kernel's
+// verdict on this chunk's blocks and all before them -- a bad block makes the chunk a refused one: nothing of it or behind it is framed
+__global__ __launch_bounds__(256) void vg_fqs_prepare(const FqStream *__restrict__ st, FqChunk *__restrict__ ck, const uint8_t *__restrict__ prev_end, uint8_t *__restrict__ buf, uint32_t nbytes,
+                                                      const unsigned long long *__restrict__ bad_key)
 {
 	const uint32_t c = prev_end ? st->carry : 0u;
 	for (uint32_t i = threadIdx.x; i < c; i += 256) buf[FQ_CARRY - c + i] = prev_end[(int64_t)i - (int64_t)c];
-	if (threadIdx.x == 0) { ck->start = FQ_CARRY - c; ck->len = c + nbytes; ck->n_reads = 0; ck->bad = st->poisoned; ck->total = 0; }
+	if (threadIdx.x == 0) { ck->start = FQ_CARRY - c; ck->len = c + nbytes; ck->n_reads = 0; ck->bad = st->poisoned | (bad_key && *bad_key != ~0ull ? 1u : 0u); ck->total = 0; }
 }
 
 // newlines per 4 KiB tile of the buffer (bytes outside the chunk's text do not count)
@@ -854,6 +857,176 @@ __global__ __launch_bounds__(256) void vg_fq_gather(const uint8_t *__restrict__ 
 		if (lane < n && lane < 32u) { const uint8_t q = lane < qlen ? text[s3 + lane] : (uint8_t)0; open = (int)(int8_t)q - '8' < 0; }
 		const uint64_t m = __ballot(open);
 		if (lane == 0) gate[r] = (uint32_t)m;
+	}
+}
+
+// ------------------------------------------------------------------------------------------------
+// kernel: BGZF blocks inflated on the device (vg_inflate.h is the decoder; this is its wave policy)
+//
+// ONE WAVE PER BGZF BLOCK, one-wave workgroups.  Symbol decoding inside a block is serial -- the position of a code is known only
+// when the code before it has been read -- so the 64 lanes of the wave hold ONE decode state (bit buffer, positions: formed
+// through readfirstlane, they live in SGPRs and the decode loop is scalar code with broadcast LDS look-ups) and share what is
+// parallel: code tables, ring refills, match / stored copies, the CRC, the write-out.  A chunk holds some thousand blocks; they
+// are independent (no shared window), and their output offsets are known from the ISIZE fields before a byte is decoded.
+//
+// LDS per workgroup (BzShared, 74 320 B: two blocks per CU of 160 KiB):
+//   out   65 536 + 16   the block's output is assembled here: back-references never read global memory another lane has just
+//                       written, and the text leaves in one coalesced pass at the end
+//   ring   1 024        compressed input, refilled by one 16-byte load per lane; the next KiB waits in a register meanwhile
+//   crc    4 096        slicing-by-4 table (second pass over the finished output: each lane a slice, combined by x^(8n) mod P)
+//   t      3 648        code tables (vg_inflate.h)
+// ------------------------------------------------------------------------------------------------
+struct BzShared {
+	uint32_t out32[VG_BGZF_MAX_ISIZE / 4 + 4];
+	uint4 ring[64];
+	VgCrcTab crc;
+	VgInfTables t;
+};
+
+struct BzWaveIO {
+	uint8_t *outp;                 // LDS: the block's output
+	uint32_t *ring32;              // LDS: 256 words of input
+	uint4 *ring16;
+	const uint4 *src;              // global: the 16-byte aligned address at or below the payload
+	const uint8_t *in;             // global: the payload
+	uint32_t in_len, skew;         // payload bytes; in - (const uint8_t *)src
+	uint32_t n_vec;                // 16-byte vectors of src that hold payload bytes: nothing beyond them is loaded
+	uint32_t g0;                   // vector index of ring16[0]
+	uint4 pre;                     // this lane's vector of the NEXT KiB (loaded while the ring's KiB is decoded)
+	uint32_t wpos;                 // next word of the ring
+	uint64_t bitbuf; uint32_t bitcnt;
+	int32_t bits_left;             // payload bits not yet consumed; negative: the decoder ran past the end
+	uint32_t ln;
+
+	__device__ __forceinline__ uint32_t lane() const { return ln; }
+	__device__ __forceinline__ static uint32_t lanes() { return 64; }
+	__device__ __forceinline__ static void sync() { __syncthreads(); }            // (one wave: a wait for its own LDS traffic, no s_barrier)
+	__device__ __forceinline__ static uint32_t u(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
+	__device__ __forceinline__ uint4 load(uint32_t v) const { return v < n_vec ? src[v] : make_uint4(0, 0, 0, 0); }
+	// the reader at payload byte `at` (<= in_len): ring and bit buffer start over
+	__device__ __forceinline__ void seek(uint32_t at)
+	{
+		const uint32_t a = skew + at;
+		g0 = a >> 4;
+		sync();                                                              // (nobody still reads the ring's old contents)
+		ring16[ln] = load(g0 + ln);
+		pre = load(g0 + 64 + ln);
+		sync();
+		wpos = (a & 15u) >> 2;
+		bitbuf = 0; bitcnt = 0;
+		need();
+		const uint32_t lead = (a & 3u) * 8u;                                 // bytes of the first word in front of `at`
+		bitbuf >>= lead; bitcnt -= lead;
+		bits_left = (int32_t)((in_len - at) * 8u);
+	}
+	__device__ __forceinline__ void need()
+	{
+		if (bitcnt <= 32) {
+			if (wpos == 256) {                                               // the ring's KiB is used up: the waiting one takes its place
+				sync();
+				ring16[ln] = pre;
+				g0 += 64;
+				pre = load(g0 + 64 + ln);
+				sync();
+				wpos = 0;
+			}
+			const uint32_t w = u(ring32[wpos]);
+			bitbuf |= (uint64_t)w << bitcnt;
+			bitcnt += 32; wpos++;
+		}
+	}
+	__device__ __forceinline__ uint32_t peek() const { return (uint32_t)bitbuf; }
+	__device__ __forceinline__ void drop(uint32_t n) { bitbuf >>= n; bitcnt -= n; bits_left -= (int32_t)n; }
+	__device__ __forceinline__ uint32_t bits(uint32_t n) { const uint32_t v = (uint32_t)bitbuf & ((1u << n) - 1u); drop(n); return v; }
+	__device__ __forceinline__ void align_byte() { drop(bitcnt & 7u); }
+	__device__ __forceinline__ bool overrun() const { return bits_left < 0; }
+	__device__ __forceinline__ void put(uint32_t o, uint8_t b) { if (ln == 0) outp[o] = b; }
+	// len bytes from `dist` back.  dist >= 64: a round of 64 lanes reads what earlier rounds (or earlier symbols) wrote.  dist < 64:
+	// the copy replicates a period; every lane reads below o only -- bytes that were there before the copy began.
+	__device__ __forceinline__ void copy(uint32_t o, uint32_t dist, uint32_t len)
+	{
+		sync();
+		if (dist >= 64) {
+			for (uint32_t base = 0; base < len; base += 64) {                // at most 5 rounds (len <= 258), 64 output bytes each
+				const uint32_t j = base + ln;
+				if (j < len) outp[o + j] = outp[o + j - dist];
+				if (base + 64 < len) sync();
+			}
+		} else {
+			for (uint32_t base = 0; base < len; base += 64) {
+				const uint32_t j = base + ln;
+				if (j < len) outp[o + j] = outp[o - dist + j % dist];
+			}
+		}
+	}
+	// a stored block's bytes straight from global memory; then the reader starts over behind them
+	__device__ __forceinline__ bool stored_copy(uint32_t o, uint32_t n)
+	{
+		const uint32_t at = in_len - ((uint32_t)bits_left >> 3);             // byte-aligned here, and not past the end (the caller checked)
+		if (n > in_len - at) return false;
+		const uint8_t *s = in + at;
+		for (uint32_t base = 0; base < n; base += 64 * 8) {                  // 512 output bytes per round
+			uint8_t v[8];
+#pragma unroll
+			for (uint32_t k = 0; k < 8; k++) { const uint32_t j = base + k * 64 + ln; v[k] = j < n ? s[j] : (uint8_t)0; }
+#pragma unroll
+			for (uint32_t k = 0; k < 8; k++) { const uint32_t j = base + k * 64 + ln; if (j < n) outp[o + j] = v[k]; }
+		}
+		seek(at + n);
+		return true;
+	}
+};
+
+// grid = blocks of the chunk.  status[b] = the block's VG_INF_* result; a failing block writes no text and enters
+// (its compressed offset << 4 | result) into *bad_key with atomicMin: the lowest failing block of the chunk / the stream.
+__global__ __launch_bounds__(64) void vg_bgzf_inflate_kernel(const uint8_t *__restrict__ comp, const vg_bgzf_block *__restrict__ tab, uint32_t n_blocks,
+                                                            uint8_t *__restrict__ text, uint32_t *__restrict__ status, unsigned long long *__restrict__ bad_key)
+{
+	__shared__ BzShared sh;
+	const uint32_t b = blockIdx.x;
+	if (b >= n_blocks) return;
+	const vg_bgzf_block blk = tab[b];
+	const uint32_t isize = blk.isize;
+	BzWaveIO io;
+	io.ln = threadIdx.x;
+	io.outp = (uint8_t *)sh.out32;
+	io.ring16 = sh.ring;
+	io.ring32 = (uint32_t *)sh.ring;
+	io.in = comp + blk.in_off;
+	io.in_len = blk.in_len;
+	io.skew = (uint32_t)((uintptr_t)io.in & 15u);
+	io.src = (const uint4 *)(io.in - io.skew);
+	io.n_vec = (io.skew + io.in_len + 15u) >> 4;
+	int rc = VG_INF_ESIZE;
+	if (isize <= VG_BGZF_MAX_ISIZE) {
+		vg_crc_tab_build(io, sh.crc);
+		io.seek(0);
+		rc = vg_inflate_raw(io, sh.t, isize);
+		if (rc == VG_INF_OK) {
+			__syncthreads();
+			uint32_t x = vg_crc32_share(sh.crc, io.outp, isize, io.ln, 64);
+			for (int o = 32; o > 0; o >>= 1) x ^= __shfl_xor(x, o);
+			if (x != blk.crc) rc = VG_INF_ECRC;
+		}
+	}
+	rc = __builtin_amdgcn_readfirstlane(rc);
+	if (rc == VG_INF_OK) {
+		// the text leaves coalesced: bytes up to the destination's next word boundary, whole words (two LDS words funnelled), tail bytes
+		uint8_t *dst = text + blk.text_off;
+		const uint32_t head = min(isize, (4u - (uint32_t)((uintptr_t)dst & 3u)) & 3u);
+		if (io.ln < head) dst[io.ln] = io.outp[io.ln];
+		const uint32_t n_w = (isize - head) >> 2;
+		uint32_t *dw = (uint32_t *)(dst + head);
+		for (uint32_t w = io.ln; w < n_w; w += 64) {
+			const uint32_t i = head + 4u * w, sft = (i & 3u) * 8u;
+			const uint32_t lo = sh.out32[i >> 2], hi = sh.out32[(i >> 2) + 1];
+			dw[w] = sft ? (lo >> sft) | (hi << (32u - sft)) : lo;
+		}
+		for (uint32_t i = head + 4u * n_w + io.ln; i < isize; i += 64) dst[i] = io.outp[i];
+	}
+	if (io.ln == 0) {
+		status[b] = (uint32_t)rc;
+		if (rc != VG_INF_OK) atomicMin(bad_key, (unsigned long long)blk.comp_off << 4 | (unsigned long long)rc);
 	}
 }
 
@@ -971,6 +1144,7 @@ struct Slot {
 	DevBuf<uint8_t> fq_tmp;                                           // scan scratch, bytes (grow-only: no allocation per chunk)
 	DevBuf<FqChunk> fq_chunk;                                         // this chunk's framing results (one FqChunk), device resident
 	uint64_t fq_text_len = 0;                                        // bytes of text copied into fq_text (after the FQ_CARRY gap)
+	DevBuf<uint8_t> bz_comp; DevBuf<vg_bgzf_block> bz_tab; DevBuf<uint32_t> bz_status;   // a BGZF chunk: compressed bytes, block table, per-block results
 	SlotEvent e_in;                                                  // the batch's buffers are complete (when another stream produced them)
 	SlotEvent e_fq; bool fq_tail_wanted = false;                     // the NEXT chunk's prepare kernel reads this text's tail: recorded after it
 	// the batch's timeline (harvest reads the times between them): the pack kernel on its stream; the wave kernel (main tier) on the main
@@ -986,6 +1160,19 @@ struct Plane {
 	PlanePtr p{nullptr, nullptr};
 	bool dirty = false;                   // cnt4 holds increments not yet folded into cnt
 	uint64_t invalid = 0;                 // reads of this sample the reference would have aborted on, since open / vg_counts_reset / vg_sample_reset
+};
+
+// Host state of a BGZF stream (vg_fastq_stream_begin_bgzf): pushes are cut anywhere, so the bytes of an incomplete block wait here
+// for the next push; the block index (16 bytes per block) is what vg_fastq_stream_bgzf_locate answers from, until the next begin.
+struct BgzfStream {
+	std::vector<uint8_t> carry;                                   // an incomplete block's bytes (at most 64 KiB once a header is whole)
+	uint64_t comp_pos = 0, text_pos = 0;                          // stream offsets of the first byte not yet handed to a slot: compressed, text
+	std::vector<std::pair<uint64_t, uint64_t>> index;             // (text offset, compressed offset) of every block so far
+	unsigned long long *d_key = nullptr;                          // device: lowest (compressed offset << 4 | VG_INF_*) of a failed block, ~0: none
+	unsigned long long host_key = ~0ull;                          // the same for blocks checked on the host (chunks without text)
+	uint64_t slot_text = 0;                                       // most text one slot takes: a longer push is split at block boundaries
+	bool header_bad = false;                                      // a push met bytes that are no BGZF block: the stream is over
+	std::vector<vg_bgzf_block> blocks, tab;                       // scratch of a push
 };
 
 struct vg_index {
@@ -1049,6 +1236,8 @@ struct vg_index {
 	bool w2_full_grid = false;            // ... and that grid for every batch, whatever the lists before were like (VG_W2_FULL_GRID)
 	FqStream *d_fq = nullptr;             // FASTQ stream state (vg_fastq_stream_*)
 	bool fq_open = false; int fq_prev_slot = -1;
+	BgzfStream bz;                        // the BGZF side of a stream opened with vg_fastq_stream_begin_bgzf
+	bool fq_bgzf = false;                 // the open FASTQ stream takes BGZF bytes
 	uint64_t max_device_bytes = 0;        // the caller's budget for this replica (vg_index_open_ex; 0: the whole device)
 	std::string plan_text;                // what the budget bought: views kept / left out (vg_index_plan)
 	std::string aux_note;                 // ... and what the loader found in the auxiliary rows, if anything
@@ -1876,6 +2065,7 @@ static int build_on_device(vg_index *ix, DevCols &c, const ViewPlan &plan, uint6
 	for (Slot &sl : ix->slot) if ((rc = dev_alloc(ix, &sl.ctr, 16, true, true))) return rc;       // [0..2] spill counts, [3] invalid reads, [4],[5] work counters of the two wave tiers, [6] reads left for the per-batch lane tier
 	if ((rc = dev_alloc(ix, &ix->d_clamped, 2 * ix->n_sites + 2, false, true))) return rc;
 	if ((rc = dev_alloc(ix, &ix->d_fq, 1, true, true))) return rc;
+	if ((rc = dev_alloc(ix, &ix->bz.d_key, 1, true, true))) return rc;
 	if ((rc = dev_alloc(ix, &ix->d_stats, S_COUNT, true, true))) return rc;
 	HIP_TRY(hipStreamSynchronize(st));
 #ifdef VG_VIEW_COUNTERS
@@ -2778,7 +2968,7 @@ extern "C" int vg_fastq_stream_begin_packed(vg_index *ix, int host_threads)
 		HIP_TRY(hipSetDevice(ix->device));
 		if (!ix->packer || ix->packer->threads() != host_threads) { delete ix->packer; ix->packer = nullptr; ix->packer = new vgp::Packer(host_threads); }
 		ix->packer->begin();
-		ix->fq_open = true; ix->fq_packed = true; ix->fq_prev_slot = -1;
+		ix->fq_open = true; ix->fq_packed = true; ix->fq_bgzf = false; ix->fq_prev_slot = -1;
 		ix->fq_sample = ix->cur_sample;                          // the stream stays with the sample selected now
 		return VG_OK;
 	});
@@ -2808,7 +2998,7 @@ static int push_packed(vg_index *ix, const uint8_t *text, uint64_t nbytes)
 extern "C" int vg_fastq_stream_begin(vg_index *ix)
 {
 	if (!ix) return fail(VG_EINVAL, "null argument");
-	ix->fq_packed = false;
+	ix->fq_packed = false; ix->fq_bgzf = false;
 	HIP_TRY(hipSetDevice(ix->device));
 	HIP_TRY(hipMemsetAsync(ix->d_fq, 0, sizeof(FqStream), ix->ingest_or_main()));
 	ix->fq_open = true; ix->fq_prev_slot = -1;
@@ -2816,29 +3006,17 @@ extern "C" int vg_fastq_stream_begin(vg_index *ix)
 	return VG_OK;
 }
 
-// One chunk of the stream: a blocking host-to-device copy (the caller's buffer is free when the call returns), then framing
-// and the read loop are only ENQUEUED -- record counts stay on the device until vg_fastq_stream_end.
-extern "C" int vg_fastq_stream_push(vg_index *ix, const uint8_t *text, uint64_t nbytes)
+// What a chunk of `nbytes` of text needs in its slot.  Capacities follow from the chunk's size alone: lines average at least 8 bytes
+// (or the chunk is refused), a record has four.
+static int fq_reserve(Slot &sl, uint64_t nbytes)
 {
-	if (!ix || (!text && nbytes)) return fail(VG_EINVAL, "null argument");
-	if (!ix->fq_open) return fail(VG_EINVAL, "vg_fastq_stream_push without vg_fastq_stream_begin");
-	if (nbytes == 0) return VG_OK;
-	if (nbytes >= (1ull << 31)) return fail(VG_EINVAL, "FASTQ chunk of 2 GiB or more");
-	if (ix->fq_packed) return guarded([&] { return push_packed(ix, text, nbytes); });
-	HIP_TRY(hipSetDevice(ix->device));
-	const int slot_no = ix->next_slot;
-	Slot *slp = nullptr;
-	int rc = acquire_slot(ix, &slp, ix->fq_sample);
-	if (rc) return rc;
-	Slot &sl = *slp;
-	hipStream_t is = ix->ingest_or_main();
-	// the chunk after this slot's last one copied the tail of its text on the ingest stream: that must have happened before
-	// the text is overwritten (the slot's own batch being finished does not imply it)
-	if (sl.fq_tail_wanted) { HIP_TRY(hipEventSynchronize(sl.e_fq)); sl.fq_tail_wanted = false; }
-	// capacities follow from the chunk's size alone: lines average at least 8 bytes (or the chunk is refused), a record has four
+	int rc;
 	const uint64_t span = (uint64_t)FQ_CARRY + nbytes;
 	const uint64_t n_tiles = (span + FQ_TILE - 1) / FQ_TILE;
 	const uint64_t cap_lines = span / 8 + 16, cap_rec = cap_lines / 4 + 1;
+	// the chunk after this slot's last one copied the tail of its text on the ingest stream: that must have happened before
+	// the text is overwritten (the slot's own batch being finished does not imply it)
+	if (sl.fq_tail_wanted) { HIP_TRY(hipEventSynchronize(sl.e_fq)); sl.fq_tail_wanted = false; }
 	if ((rc = sl.fq_text.reserve(n_tiles * FQ_TILE + 64, "FASTQ text"))) return rc;
 	if ((rc = sl.fq_tiles.reserve(n_tiles + 2, "FASTQ tiles"))) return rc;
 	if ((rc = sl.fq_lines.reserve(cap_lines + 2, "FASTQ lines"))) return rc;
@@ -2847,11 +3025,22 @@ extern "C" int vg_fastq_stream_push(vg_index *ix, const uint8_t *text, uint64_t 
 	if ((rc = sl.st_bases.reserve(span + 64, "base text"))) return rc;              // the bases of a chunk are shorter than its text
 	if ((rc = sl.st_gate.reserve(cap_rec + 2, "gate words"))) return rc;
 	if ((rc = sl.fq_tmp.reserve(vg_dev_scan_temp_bytes(n_tiles + 1, cap_rec + 1), "scan scratch"))) return rc;
-	HIP_TRY(hipMemcpy(sl.fq_text.p + FQ_CARRY, text, nbytes, hipMemcpyHostToDevice));
+	return VG_OK;
+}
+
+// The framing sequence of one chunk whose `nbytes` of text are (or will be, by work already enqueued on the ingest stream) at
+// sl.fq_text.p + FQ_CARRY: carry, newline counts, line starts, record lengths, verdict, gather -- and the read loop behind them.
+// Text chunks and inflated BGZF chunks (bad_key: see vg_fqs_prepare) both come through here.
+static int fq_frame_and_launch(vg_index *ix, Slot &sl, int slot_no, uint64_t nbytes, const unsigned long long *bad_key)
+{
+	hipStream_t is = ix->ingest_or_main();
+	const uint64_t span = (uint64_t)FQ_CARRY + nbytes;
+	const uint64_t n_tiles = (span + FQ_TILE - 1) / FQ_TILE;
+	const uint64_t cap_lines = span / 8 + 16, cap_rec = cap_lines / 4 + 1;
 	sl.fq_text_len = nbytes;
 	const uint8_t *prev_end = nullptr;
 	if (ix->fq_prev_slot >= 0) { const Slot &pv = ix->slot[ix->fq_prev_slot]; prev_end = pv.fq_text.p + FQ_CARRY + pv.fq_text_len; }
-	vg_fqs_prepare<<<1, 256, 0, is>>>(ix->d_fq, sl.fq_chunk.p, prev_end, sl.fq_text.p, (uint32_t)nbytes);
+	vg_fqs_prepare<<<1, 256, 0, is>>>(ix->d_fq, sl.fq_chunk.p, prev_end, sl.fq_text.p, (uint32_t)nbytes, bad_key);
 	if (ix->fq_prev_slot >= 0) { Slot &pv = ix->slot[ix->fq_prev_slot]; HIP_TRY(hipEventRecord(pv.e_fq, is)); pv.fq_tail_wanted = true; }
 	vg_fq_count_newlines<<<(unsigned)n_tiles, 256, 0, is>>>(sl.fq_text.p, sl.fq_chunk.p, sl.fq_tiles.p);
 	HIP_TRY(hipMemsetAsync(sl.fq_tiles.p + n_tiles, 0, 4, is));
@@ -2869,6 +3058,235 @@ extern "C" int vg_fastq_stream_push(vg_index *ix, const uint8_t *text, uint64_t 
 	HIP_TRY(hipGetLastError());
 	ix->fq_prev_slot = slot_no;
 	return launch_batch(ix, sl, sl.st_bases.p, nullptr, sl.st_offsets.p, cap_rec, is, &sl.fq_chunk.p->n_reads, span, sl.st_gate.p);
+}
+
+static int push_bgzf(vg_index *ix, const uint8_t *data, uint64_t nbytes);
+
+// One chunk of the stream: a blocking host-to-device copy (the caller's buffer is free when the call returns), then framing
+// and the read loop are only ENQUEUED -- record counts stay on the device until vg_fastq_stream_end.
+extern "C" int vg_fastq_stream_push(vg_index *ix, const uint8_t *text, uint64_t nbytes)
+{
+	if (!ix || (!text && nbytes)) return fail(VG_EINVAL, "null argument");
+	if (!ix->fq_open) return fail(VG_EINVAL, "vg_fastq_stream_push without vg_fastq_stream_begin");
+	if (nbytes == 0) return VG_OK;
+	if (nbytes >= (1ull << 31)) return fail(VG_EINVAL, "FASTQ chunk of 2 GiB or more");
+	if (ix->fq_packed) return guarded([&] { return push_packed(ix, text, nbytes); });
+	if (ix->fq_bgzf) return guarded([&] { return push_bgzf(ix, text, nbytes); });
+	HIP_TRY(hipSetDevice(ix->device));
+	const int slot_no = ix->next_slot;
+	Slot *slp = nullptr;
+	int rc = acquire_slot(ix, &slp, ix->fq_sample);
+	if (rc) return rc;
+	Slot &sl = *slp;
+	if ((rc = fq_reserve(sl, nbytes))) return rc;
+	HIP_TRY(hipMemcpy(sl.fq_text.p + FQ_CARRY, text, nbytes, hipMemcpyHostToDevice));
+	return fq_frame_and_launch(ix, sl, slot_no, nbytes, nullptr);
+}
+
+// ---- BGZF streams: compressed bytes cross the link, the inflate kernel writes the slot's text, the framing above takes it from there
+constexpr uint64_t BZ_SLOT_TEXT_MAX = (1ull << 31) - 1;               // the text chunks' own limit
+
+static std::string bz_describe(unsigned long long key)
+{
+	return "BGZF block at compressed offset " + std::to_string(key >> 4) + ": " + vg_inflate_strerror((int)(key & 15u));
+}
+
+extern "C" int vg_fastq_stream_begin_bgzf(vg_index *ix)
+{
+	if (!ix) return fail(VG_EINVAL, "null argument");
+	return guarded([&]() -> int {
+		int rc = vg_fastq_stream_begin(ix);
+		if (rc) return rc;
+		BgzfStream &bz = ix->bz;
+		HIP_TRY(hipMemsetAsync(bz.d_key, 0xff, sizeof *bz.d_key, ix->ingest_or_main()));
+		bz.carry.clear(); bz.index.clear();
+		bz.comp_pos = 0; bz.text_pos = 0; bz.host_key = ~0ull; bz.header_bad = false;
+		bz.slot_text = BZ_SLOT_TEXT_MAX;
+		if (const char *e = getenv("VG_BGZF_SLOT_TEXT")) bz.slot_text = std::min<uint64_t>(BZ_SLOT_TEXT_MAX, std::max<uint64_t>(VG_BGZF_MAX_ISIZE, strtoull(e, nullptr, 10)));   // (tests: the split path with small inputs)
+		ix->fq_bgzf = true;
+		return VG_OK;
+	});
+}
+
+// blocks [i0, i1) of a push (bz.blocks; their bytes are in p, in_off relative to it) -> one slot: copy the compressed bytes and the
+// table up, inflate into the slot's text, frame
+static int bgzf_slot(vg_index *ix, const uint8_t *p, size_t i0, size_t i1, uint64_t text_n)
+{
+	BgzfStream &bz = ix->bz;
+	const vg_bgzf_block &first = bz.blocks[i0], &last = bz.blocks[i1 - 1];
+	const uint64_t c0 = first.comp_off - bz.comp_pos, c1 = (uint64_t)last.in_off + last.in_len + 8;
+	bz.tab.assign(bz.blocks.begin() + (long)i0, bz.blocks.begin() + (long)i1);
+	for (vg_bgzf_block &b : bz.tab) { b.in_off -= (uint32_t)c0; b.text_off -= first.text_off; }
+	if (text_n == 0) {
+		// nothing to frame (empty blocks, the end-of-file marker): their payloads and CRCs are checked here
+		for (const vg_bgzf_block &b : bz.tab) {
+			uint8_t none;
+			const int rc = vg_inflate_block_host(p + c0 + b.in_off, b.in_len, &none, 0, b.crc);
+			if (rc) bz.host_key = std::min(bz.host_key, (unsigned long long)b.comp_off << 4 | (unsigned)rc);
+		}
+		return VG_OK;
+	}
+	HIP_TRY(hipSetDevice(ix->device));
+	const int slot_no = ix->next_slot;
+	Slot *slp = nullptr;
+	int rc = acquire_slot(ix, &slp, ix->fq_sample);
+	if (rc) return rc;
+	Slot &sl = *slp;
+	if ((rc = fq_reserve(sl, text_n))) return rc;
+	if ((rc = sl.bz_comp.reserve(c1 - c0 + 64, "BGZF bytes"))) return rc;   // (the kernel loads whole aligned 16-byte vectors around a payload)
+	if ((rc = sl.bz_tab.reserve(bz.tab.size(), "BGZF block table"))) return rc;
+	if ((rc = sl.bz_status.reserve(bz.tab.size(), "BGZF block results"))) return rc;
+	HIP_TRY(hipMemcpy(sl.bz_comp.p, p + c0, c1 - c0, hipMemcpyHostToDevice));
+	HIP_TRY(hipMemcpy(sl.bz_tab.p, bz.tab.data(), bz.tab.size() * sizeof(vg_bgzf_block), hipMemcpyHostToDevice));
+	vg_bgzf_inflate_kernel<<<(unsigned)bz.tab.size(), 64, 0, ix->ingest_or_main()>>>(sl.bz_comp.p, sl.bz_tab.p, (uint32_t)bz.tab.size(), sl.fq_text.p + FQ_CARRY, sl.bz_status.p, bz.d_key);
+	HIP_TRY(hipGetLastError());
+	return fq_frame_and_launch(ix, sl, slot_no, text_n, bz.d_key);
+}
+
+static int push_bgzf(vg_index *ix, const uint8_t *data, uint64_t nbytes)
+{
+	BgzfStream &bz = ix->bz;
+	if (bz.header_bad) return fail(VG_EIO, "the BGZF stream ended at bytes that are no BGZF block (an earlier push said where)");
+	const uint8_t *p = data;
+	uint64_t len = nbytes;
+	if (!bz.carry.empty()) { bz.carry.insert(bz.carry.end(), data, data + nbytes); p = bz.carry.data(); len = bz.carry.size(); }
+	bz.blocks.clear();
+	uint64_t tail = 0, bad_off = 0;
+	const int hdr_rc = vg_bgzf_scan(p, len, bz.comp_pos, bz.text_pos, bz.blocks, &tail, &bad_off);
+	for (size_t i0 = 0; i0 < bz.blocks.size();) {                     // slots of at most slot_text bytes of text, cut at block boundaries
+		size_t i1 = i0;
+		uint64_t text_n = 0;
+		while (i1 < bz.blocks.size() && (i1 == i0 || text_n + bz.blocks[i1].isize <= bz.slot_text)) text_n += bz.blocks[i1++].isize;
+		const int rc = bgzf_slot(ix, p, i0, i1, text_n);
+		if (rc) return rc;
+		i0 = i1;
+	}
+	uint64_t used = 0;                                                  // bytes of p that whole blocks took
+	for (const vg_bgzf_block &b : bz.blocks) bz.index.emplace_back(b.text_off, b.comp_off);
+	if (!bz.blocks.empty()) { const vg_bgzf_block &b = bz.blocks.back(); bz.text_pos = b.text_off + b.isize; used = (uint64_t)b.in_off + b.in_len + 8; }
+	if (hdr_rc) {
+		bz.header_bad = true;
+		bz.comp_pos += used;
+		bz.carry.clear();
+		return fail(VG_EIO, "BGZF block at compressed offset %s: not a BGZF block header (1f 8b 08 04, a BC subfield, BSIZE and ISIZE in range)", std::to_string(bad_off).c_str());
+	}
+	std::vector<uint8_t> rest(p + used, p + len);                       // the incomplete block, if any, waits for the next push
+	bz.carry.swap(rest);
+	bz.comp_pos += used;
+	return VG_OK;
+}
+
+extern "C" int vg_fastq_stream_bgzf_locate(vg_index *ix, uint64_t text_offset, uint64_t *block_offset, uint32_t *within)
+{
+	if (!ix || !block_offset || !within) return fail(VG_EINVAL, "null argument");
+	const BgzfStream &bz = ix->bz;
+	if (text_offset > bz.text_pos) return fail(VG_EINVAL, "text offset beyond what the BGZF stream has seen");
+	// the last block that starts at or before the offset (empty blocks in front of it are passed over)
+	auto it = std::upper_bound(bz.index.begin(), bz.index.end(), std::pair<uint64_t, uint64_t>(text_offset, UINT64_MAX));
+	if (text_offset == bz.text_pos || it == bz.index.begin()) { *block_offset = bz.comp_pos; *within = 0; return VG_OK; }   // the end of the blocks seen: whatever comes next
+	--it;
+	*block_offset = it->second; *within = (uint32_t)(text_offset - it->first);
+	return VG_OK;
+}
+
+// ---- BGZF without a handle: whole blocks of a buffer -> text in host memory (the tests see every inflated byte through these)
+static int bz_buffer_args(const uint8_t *bgzf, uint64_t nbytes, uint8_t *text, uint64_t *text_len, uint64_t *consumed, uint64_t *bad_block_offset)
+{
+	if ((!bgzf && nbytes) || !text_len || !consumed || !bad_block_offset || !text) return fail(VG_EINVAL, "null argument");
+	if (nbytes >= (1ull << 32)) return fail(VG_EINVAL, "BGZF buffer of 4 GiB or more");
+	*text_len = 0; *consumed = 0; *bad_block_offset = UINT64_MAX;
+	return VG_OK;
+}
+
+extern "C" int vg_bgzf_scan_host(const uint8_t *bgzf, uint64_t nbytes, uint64_t *blocks, uint64_t blocks_cap, uint64_t *n_blocks, uint64_t *consumed, uint64_t *bad_block_offset)
+{
+	if ((!bgzf && nbytes) || (!blocks && blocks_cap) || !n_blocks || !consumed || !bad_block_offset) return fail(VG_EINVAL, "null argument");
+	if (nbytes >= (1ull << 32)) return fail(VG_EINVAL, "BGZF buffer of 4 GiB or more");
+	return guarded([&]() -> int {
+		std::vector<vg_bgzf_block> bl;
+		uint64_t tail = 0, bad = UINT64_MAX;
+		const int rc = vg_bgzf_scan(bgzf, nbytes, 0, 0, bl, &tail, &bad);
+		*n_blocks = bl.size();
+		*consumed = bl.empty() ? 0 : (uint64_t)bl.back().in_off + bl.back().in_len + 8;
+		*bad_block_offset = rc ? bad : UINT64_MAX;
+		if (bl.size() > blocks_cap) return fail(VG_ETOOBIG, "more BGZF blocks than the caller's table holds");
+		for (size_t i = 0; i < bl.size(); i++) { const vg_bgzf_block &b = bl[i]; uint64_t *o = blocks + 6 * i; o[0] = b.comp_off; o[1] = b.text_off; o[2] = b.in_off; o[3] = b.in_len; o[4] = b.isize; o[5] = b.crc; }
+		if (rc) (void)fail(VG_EIO, "BGZF block at compressed offset %s: not a BGZF block header", std::to_string(bad).c_str());
+		return VG_OK;
+	});
+}
+
+extern "C" int vg_bgzf_inflate_host(const uint8_t *bgzf, uint64_t nbytes, uint8_t *text, uint64_t text_cap, uint64_t *text_len, uint64_t *consumed, uint64_t *bad_block_offset)
+{
+	int rc = bz_buffer_args(bgzf, nbytes, text, text_len, consumed, bad_block_offset);
+	if (rc) return rc;
+	return guarded([&]() -> int {
+		std::vector<vg_bgzf_block> bl;
+		uint64_t tail = 0, bad = UINT64_MAX;
+		const int hdr_rc = vg_bgzf_scan(bgzf, nbytes, 0, 0, bl, &tail, &bad);
+		for (const vg_bgzf_block &b : bl) {
+			if (b.text_off + b.isize > text_cap) return fail(VG_ETOOBIG, "the text of the BGZF blocks does not fit the caller's buffer");
+			const int brc = vg_inflate_block_host(bgzf + b.in_off, b.in_len, text + b.text_off, b.isize, b.crc);
+			if (brc) {
+				*bad_block_offset = b.comp_off; *consumed = b.comp_off;
+				(void)fail(VG_EIO, "%s", bz_describe((unsigned long long)b.comp_off << 4 | (unsigned)brc).c_str());
+				return VG_OK;
+			}
+			*text_len = b.text_off + b.isize;
+			*consumed = (uint64_t)b.in_off + b.in_len + 8;
+		}
+		if (hdr_rc) { *bad_block_offset = bad; (void)fail(VG_EIO, "BGZF block at compressed offset %s: not a BGZF block header", std::to_string(bad).c_str()); }
+		return VG_OK;
+	});
+}
+
+extern "C" int vg_bgzf_inflate_device(int device, const uint8_t *bgzf, uint64_t nbytes, uint8_t *text, uint64_t text_cap, uint64_t *text_len, uint64_t *consumed, uint64_t *bad_block_offset)
+{
+	int rc = bz_buffer_args(bgzf, nbytes, text, text_len, consumed, bad_block_offset);
+	if (rc) return rc;
+	return guarded([&]() -> int {
+		std::vector<vg_bgzf_block> bl;
+		uint64_t tail = 0, bad = UINT64_MAX;
+		const int hdr_rc = vg_bgzf_scan(bgzf, nbytes, 0, 0, bl, &tail, &bad);
+		const uint64_t comp_n = bl.empty() ? 0 : (uint64_t)bl.back().in_off + bl.back().in_len + 8;
+		const uint64_t text_n = bl.empty() ? 0 : bl.back().text_off + bl.back().isize;
+		if (text_n > text_cap) return fail(VG_ETOOBIG, "the text of the BGZF blocks does not fit the caller's buffer");
+		unsigned long long key = ~0ull;
+		if (!bl.empty()) {
+			HIP_TRY(hipSetDevice(device));
+			DevBuf<uint8_t> d_comp, d_text; DevBuf<vg_bgzf_block> d_tab; DevBuf<uint32_t> d_status; DevBuf<unsigned long long> d_key;
+			if ((rc = d_comp.reserve(comp_n + 64, "BGZF bytes")) || (rc = d_text.reserve(text_n + 64, "inflated text")) || (rc = d_tab.reserve(bl.size(), "BGZF block table"))
+			    || (rc = d_status.reserve(bl.size(), "BGZF block results")) || (rc = d_key.reserve(1, "BGZF verdict"))) return rc;
+			HIP_TRY(hipMemcpy(d_comp.p, bgzf, comp_n, hipMemcpyHostToDevice));
+			HIP_TRY(hipMemcpy(d_tab.p, bl.data(), bl.size() * sizeof(vg_bgzf_block), hipMemcpyHostToDevice));
+			HIP_TRY(hipMemset(d_key.p, 0xff, sizeof key));
+			const bool timed = getenv("VG_VERBOSE") != nullptr;
+			const int rounds = timed ? 3 : 1;                          // (verbose: the kernel's own rate, warmed -- the same text is written again)
+			hipEvent_t e0 = nullptr, e1 = nullptr;
+			if (timed) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); }
+			float ms = 0;
+			for (int r = 0; r < rounds; r++) {
+				if (timed) HIP_TRY(hipEventRecord(e0, nullptr));
+				vg_bgzf_inflate_kernel<<<(unsigned)bl.size(), 64>>>(d_comp.p, d_tab.p, (uint32_t)bl.size(), d_text.p, d_status.p, d_key.p);
+				HIP_TRY(hipGetLastError());
+				if (timed) { HIP_TRY(hipEventRecord(e1, nullptr)); HIP_TRY(hipEventSynchronize(e1)); HIP_TRY(hipEventElapsedTime(&ms, e0, e1)); }
+			}
+			HIP_TRY(hipDeviceSynchronize());
+			if (timed) {
+				fprintf(stderr, "[vargeno_hip] bgzf inflate kernel: %zu blocks, %.3f ms, %.2f GB/s text, %.2f GB/s compressed\n", bl.size(), ms, text_n / 1e6 / ms, comp_n / 1e6 / ms);
+				(void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+			}
+			HIP_TRY(hipMemcpy(&key, d_key.p, sizeof key, hipMemcpyDeviceToHost));
+			uint64_t good_text = text_n;
+			if (key != ~0ull) for (const vg_bgzf_block &b : bl) if (b.comp_off == key >> 4) good_text = b.text_off;
+			if (good_text) HIP_TRY(hipMemcpy(text, d_text.p, good_text, hipMemcpyDeviceToHost));
+			*text_len = good_text;
+		}
+		*consumed = comp_n;
+		if (key != ~0ull) { *bad_block_offset = key >> 4; *consumed = key >> 4; (void)fail(VG_EIO, "%s", bz_describe(key).c_str()); }
+		else if (hdr_rc) { *bad_block_offset = bad; (void)fail(VG_EIO, "BGZF block at compressed offset %s: not a BGZF block header", std::to_string(bad).c_str()); }
+		return VG_OK;
+	});
 }
 
 static int fq_collect(vg_index *ix, bool drain, uint64_t *n_records, uint64_t *consumed, uint64_t *last_record_start, int *refused)
@@ -2900,7 +3318,19 @@ extern "C" int vg_fastq_stream_end(vg_index *ix, uint64_t *n_records, uint64_t *
 		if (refused) *refused = ix->packer->poisoned() ? 1 : 0;
 		return VG_OK;
 	}
-	return fq_collect(ix, true, n_records, consumed, last_record_start, refused);
+	int rc = fq_collect(ix, true, n_records, consumed, last_record_start, refused);
+	if (rc || !ix->fq_bgzf) return rc;
+	ix->fq_bgzf = false;
+	return guarded([&]() -> int {
+		BgzfStream &bz = ix->bz;
+		unsigned long long key = ~0ull;
+		HIP_TRY(hipMemcpy(&key, bz.d_key, sizeof key, hipMemcpyDeviceToHost));
+		key = std::min(key, bz.host_key);
+		if (key != ~0ull) return fail(VG_EIO, "%s", bz_describe(key).c_str());
+		if (bz.header_bad) return fail(VG_EIO, "BGZF block at compressed offset %s: not a BGZF block header", std::to_string(bz.comp_pos).c_str());
+		if (!bz.carry.empty()) return fail(VG_EIO, "BGZF block at compressed offset %s: incomplete (the stream ends %s bytes into it)", std::to_string(bz.comp_pos).c_str(), std::to_string(bz.carry.size()).c_str());
+		return VG_OK;
+	});
 }
 
 // One self-contained chunk (a stream of one push): the older, synchronous form of the above -- the caller learns what was

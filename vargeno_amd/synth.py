@@ -376,6 +376,50 @@ def write_fastq(path, reads):
         f.write(b"".join(chunk))
 
 
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+
+
+def bgzf_block(payload, crc, isize, extra_before=b"", extra_after=b""):
+    """One BGZF block around a raw-DEFLATE payload: gzip member with FLG.FEXTRA and the `BC` subfield (BSIZE = block size - 1).
+    extra_before / extra_after: further, well-formed subfields around `BC`."""
+    import struct
+
+    xlen = len(extra_before) + 6 + len(extra_after)
+    bsize = 12 + xlen + len(payload) + 8 - 1
+    return (b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff" + struct.pack("<H", xlen) + extra_before + b"BC" + struct.pack("<HH", 2, bsize)
+            + extra_after + payload + struct.pack("<II", crc & 0xFFFFFFFF, isize))
+
+
+def bgzf_bytes(text, block=65280, level=6, strategy=None, flush_at=None, eof=True, extra_before=b"", rng=None):
+    """`text` as a BGZF file (what bgzip / htslib write; also a valid .gz), on Python's zlib: raw deflate (wbits=-15) per block.
+    block: uncompressed bytes per block -- an int, or a sequence of sizes to draw from per block with `rng` (0 gives an empty
+    block in the middle).  strategy: a zlib strategy (Z_FIXED, Z_HUFFMAN_ONLY, ...).  flush_at: a fraction in (0, 1): one
+    Z_FULL_FLUSH at that point of every block -- several DEFLATE blocks, an empty stored one among them.  eof=False leaves
+    the 28-byte end-of-file marker out."""
+    import zlib
+
+    text = bytes(text)
+    sizes = None if isinstance(block, int) else list(block)
+    out, at = [], 0
+    while True:
+        n = block if sizes is None else int(sizes[int(rng.integers(0, len(sizes)))])
+        piece = text[at:at + n]
+        at += len(piece)
+        co = zlib.compressobj(level, zlib.DEFLATED, -15, 9, zlib.Z_DEFAULT_STRATEGY if strategy is None else strategy)
+        if flush_at is not None and piece:
+            cut = int(len(piece) * flush_at)
+            payload = co.compress(piece[:cut]) + co.flush(zlib.Z_FULL_FLUSH) + co.compress(piece[cut:]) + co.flush()
+        else:
+            payload = co.compress(piece) + co.flush()
+        assert 12 + 6 + len(extra_before) + len(payload) + 8 <= 65536, "block does not fit BSIZE: lower `block`"
+        out.append(bgzf_block(payload, zlib.crc32(piece), len(piece), extra_before=extra_before))
+        if at >= len(text):
+            break
+    if eof:
+        out.append(BGZF_EOF)
+    return b"".join(out)
+
+
 # ----------------------------------------------------------------------------- named data sets
 
 def f_small(seed=20261002):
