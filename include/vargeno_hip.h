@@ -293,6 +293,27 @@ int  vg_sites_fetch(vg_index *ix, uint32_t *pos, uint8_t *ref_base, uint8_t *alt
 int  vg_counts_fetch(vg_index *ix, uint8_t *ref_cnt, uint8_t *alt_cnt);    /* clamped at 63     */
 int  vg_counts_reset(vg_index *ix);
 
+/* Replaces the caller, qv.cc:1789-1848 (posterior) and :1681 (the GQ column): the step that turns the counters into an answer.
+ * Per site gt = 0 not called (no reads, or both counters saturated), 1 hom-ref, 2 hom-alt, 3 het -- the reference's GTYPE_*
+ * numbering -- and gq = (int)(-10 ln(confidence)) exactly as the reference prints it (0 where gt is 0; -2147483648 where allele
+ * frequencies whose squares sum above 1 make the confidence negative, as there).
+ * A kernel computes the call where the counters live, one lane per site, and 2 bytes per site cross the link (gt << 14 | gq).  The
+ * arithmetic up to the confidence is the host caller's own, bit for bit (csrc/vg_caller.h: one function for both, contraction
+ * off, the per-count factor tables computed once on the host with libm and uploaded).  The logarithm is not: the kernel settles a
+ * site only when its -10 ln(confidence) lies farther than a guard (1e-6) from the nearest integer, the confidence is inside (0, 1)
+ * and the result is below 16383; every other site leaves the device with an escape code and is recomputed on the host with libm
+ * before the call returns.  The values handed out are final.
+ *   vg_sample_calls_fetch   the selected sample (vg_sample_select), like vg_counts_fetch: implies vg_sync; with several replicas
+ *                           the all-reduce comes first.  gt, gq: vg_num_sites entries each.  *n_escaped (may be NULL): the sites
+ *                           the host recomputed.  The first call takes 4 bytes of device memory per site (the sites' frequency
+ *                           columns and the staging) plus ~5 KiB, outside the plan, counted by vg_index_device_bytes; VG_ENOMEM
+ *                           for it leaves the handle usable (and the caller with vg_counts_fetch and a host loop)
+ *   vg_call_device          the same kernel without a handle, over n quadruples in host memory (counters are clamped at 63 first):
+ *                           what drives it over the caller's whole domain.  guard <= 0: the default; a guard must be below 0.5 */
+int  vg_sample_calls_fetch(vg_index *ix, uint8_t *gt, int32_t *gq, uint64_t *n_escaped);
+int  vg_call_device(int device, const uint8_t *ref_cnt, const uint8_t *alt_cnt, const uint8_t *ref_freq, const uint8_t *alt_freq,
+                    uint64_t n, double guard, uint8_t *gt, int32_t *gq, uint64_t *n_escaped);
+
 /* Sample planes: several samples against ONE resident index.  The reference genotypes one sample per process: the counters it hands
  * to the caller (qv.cc:1573-1626) are the only per-sample state of its read loop, the dictionaries are read-only.  A PLANE is that
  * state for one sample on the device: the exact sums (8 bytes per SNP site) and the wave kernel's base-indexed counters (16 bytes

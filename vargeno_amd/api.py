@@ -277,6 +277,23 @@ class GenoIndex:
         check(lib().vg_counts_fetch(self._h, _ptr(buf[:n]), _ptr(buf[n:])))
         return buf[:n], buf[n:2 * n]
 
+    def calls(self, sample=None):
+        """The genotype calls (gt, gq) of the selected sample, or of `sample` (the selection is restored), computed on the device
+        from its counters: gt uint8 in the reference's numbering (0 not called, 1 hom-ref, 2 hom-alt, 3 het), gq int32 as the
+        reference prints it (0 where gt is 0).  `last_escaped` is the number of sites the host had to recompute."""
+        if sample is not None:
+            before = self.selected
+            self.select(sample)
+            try:
+                return self.calls()
+            finally:
+                self.select(before)
+        n = self.num_sites
+        gt, gq, esc = np.empty(n, np.uint8), np.empty(n, np.int32), C.c_uint64()
+        check(lib().vg_sample_calls_fetch(self._h, _ptr(gt), _ptr(gq), C.byref(esc)))
+        self.last_escaped = int(esc.value)
+        return gt, gq
+
     def reset(self):
         check(lib().vg_counts_reset(self._h))
 
@@ -407,6 +424,23 @@ def bgzf_inflate(data, device=0, out=None, text_cap=None):
     else:
         check(lib().vg_bgzf_inflate_device(int(device), _ptr(a), len(a), _ptr(out), int(text_cap), C.byref(n), C.byref(used), C.byref(bad)))
     return out[:int(n.value)].tobytes(), int(used.value), (None if bad.value == 2 ** 64 - 1 else int(bad.value))
+
+
+# the caller kernel's launch: lanes per block, and the most blocks of a grid (a longer array wraps round the grid-stride loop)
+CALL_BLOCK, CALL_MAX_GRID = 256, 4096
+
+
+def call_device(ref_cnt, alt_cnt, ref_freq, alt_freq, device=0, guard=0.0):
+    """The caller kernel over flat arrays (no index): (gt, gq, n_escaped) for the quadruples (counters are clamped at 63, frequencies
+    are the dictionary's n/255 bytes).  gt / gq are final, as GenoIndex.calls() returns them; n_escaped counts the entries the
+    kernel left to the host (guard: how close to an integer -10 ln(confidence) may lie before it does; <= 0: the default, 1e-6)."""
+    cols = [np.ascontiguousarray(a, dtype=np.uint8) for a in (ref_cnt, alt_cnt, ref_freq, alt_freq)]
+    n = len(cols[0])
+    if any(len(c) != n for c in cols):
+        raise ValueError("call_device: four arrays of one length")
+    gt, gq, esc = np.empty(n, np.uint8), np.empty(n, np.int32), C.c_uint64()
+    check(lib().vg_call_device(int(device), _ptr(cols[0]), _ptr(cols[1]), _ptr(cols[2]), _ptr(cols[3]), n, float(guard), _ptr(gt), _ptr(gq), C.byref(esc)))
+    return gt, gq, int(esc.value)
 
 
 def pinned_buffer(nbytes):

@@ -25,64 +25,28 @@
 #include <vector>
 
 #include "vg_host.h"
+#include "../vg_caller.h"
 
 namespace vgh {
 
 // ------------------------------------------------------------------------------------------------
-// posterior
+// posterior: ../vg_caller.h, shared with the device's caller kernel
 // ------------------------------------------------------------------------------------------------
 namespace {
-
-constexpr unsigned kCap = 63;            // counter saturation, src/vartype.h:27
-constexpr double kErr = 0.01;            // src/vartype.h:13
-constexpr double kMeanDepth = 7.1;       // src/vartype.h:14
-
-// Per-count factors.  The reference tabulates the three likelihoods per (ref_cnt, alt_cnt) pair; a product of two
-// tabulated powers is the same pair of libm calls and the same multiply, so 3 x 64 numbers replace 3 x 4096.
-struct Factors {
-	double keep[kCap + 1];               // (1 - e)^k
-	double flip[kCap + 1];               // e^k
-	double half[2 * kCap + 1];           // 0.5^k
-	double depth[2 * kCap + 1];          // Poisson(7.1) mass at k
-	Factors()
-	{
-		for (unsigned k = 0; k <= kCap; k++) { keep[k] = pow(1.0 - kErr, (int)k); flip[k] = pow(kErr, (int)k); }
-		const double m = exp(-kMeanDepth);
-		for (unsigned k = 0; k <= 2 * kCap; k++) {
-			half[k] = pow(0.5, (int)k);
-			depth[k] = (m * pow(kMeanDepth, (int)k)) / exp(lgamma(k + 1.0));
-		}
-	}
-};
-const Factors &factors() { static const Factors f; return f; }
-
+const vg_caller_tables &caller_tables()
+{
+	static const vg_caller_tables t = [] { vg_caller_tables x; vg_caller_tables_fill(x); return x; }();
+	return t;
+}
 }  // namespace
 
 Genotype call_genotype(unsigned ref_cnt, unsigned alt_cnt, uint8_t ref_freq, uint8_t alt_freq)
 {
-	Genotype out{GT_NONE, 0.0};
-	if (ref_cnt > kCap) ref_cnt = kCap;
-	if (alt_cnt > kCap) alt_cnt = kCap;
-	if ((ref_cnt | alt_cnt) == 0 || (ref_cnt == kCap && alt_cnt == kCap)) return out;
-	const Factors &f = factors();
-	const double pr = ref_freq / 255.0, pa = alt_freq / 255.0;
-	const double rr = pr * pr, aa = pa * pa;
-	const double w[3] = {
-		rr * (f.keep[ref_cnt] * f.flip[alt_cnt]),            // hom-ref
-		(1.0 - rr - aa) * f.half[ref_cnt + alt_cnt],         // het
-		aa * (f.flip[ref_cnt] * f.keep[alt_cnt]),            // hom-alt
-	};
-	const double sum = w[0] + w[1] + w[2];
-	// strict maximum wins, hom-ref tested before het; anything else (ties included) is hom-alt
-	int best = 2;
-	if (w[0] > w[1] && w[0] > w[2]) best = 0;
-	else if (w[1] > w[0] && w[1] > w[2]) best = 1;
-	out.gt = best == 0 ? GT_HOM_REF : best == 1 ? GT_HET : GT_HOM_ALT;
-	out.confidence = (w[best] / sum) * f.depth[ref_cnt + alt_cnt];
-	return out;
+	const vg_site_call c = vg_call_site(caller_tables(), ref_cnt, alt_cnt, ref_freq, alt_freq);
+	return Genotype{c.gt, c.confidence};
 }
 
-int genotype_quality(double confidence) { return (int)(-10 * log(confidence)); }
+int genotype_quality(double confidence) { return vg_genotype_quality(confidence); }
 
 // ------------------------------------------------------------------------------------------------
 // chromosome table (<prefix>.chrlens: "name length" per line; a name is at most 32 non-space characters)
@@ -105,6 +69,25 @@ std::vector<ChrLen> read_chrlens(const std::string &path)
 	return table;
 }
 
+// the calls themselves are independent of one another: threads, a slice of the sites each (r05: 10 M sites at 30-fold coverage
+// are all genotyped; one thread took 0.3 s of the job's tail for them)
+void call_sites(const SiteCounts &s, SiteCalls &out)
+{
+	const size_t ns = s.pos.size();
+	out.gt.resize(ns); out.gq.resize(ns);
+	unsigned nt = std::max(1u, std::min(std::thread::hardware_concurrency(), 16u));
+	if (ns < (1u << 16)) nt = 1;
+	auto work = [&](unsigned t) {
+		for (size_t i = ns * t / nt; i < ns * (t + 1) / nt; i++) {
+			const Genotype k = call_genotype(s.ref_cnt[i], s.alt_cnt[i], s.ref_freq[i], s.alt_freq[i]);
+			out.gt[i] = k.gt;
+			out.gq[i] = k.gt == GT_NONE ? 0 : genotype_quality(k.confidence);
+		}
+	};
+	if (nt == 1) work(0);
+	else { std::vector<std::thread> th; for (unsigned t = 0; t < nt; t++) th.emplace_back(work, t); for (auto &x : th) x.join(); }
+}
+
 // ------------------------------------------------------------------------------------------------
 // called sites, addressable the way the reference's "name$position" keys are
 // ------------------------------------------------------------------------------------------------
@@ -119,53 +102,55 @@ struct CalledSite {
 
 class CallBook {
 public:
+	// the host call loop, then the book of its calls
 	CallBook(const SiteCounts &s, const std::vector<ChrLen> &chrs, CallSummary &sum)
 	{
-		// the calls themselves are independent of one another: threads, a slice of the sites each (r05: 10 M sites at 30-fold coverage
-		// are all genotyped; one thread took 0.3 s of the job's tail for them)
-		const size_t ns = s.pos.size();
-		std::vector<uint8_t> gts(ns);
-		std::vector<int> gqs(ns);
-		{
-			unsigned nt = std::max(1u, std::min(std::thread::hardware_concurrency(), 16u));
-			if (ns < (1u << 16)) nt = 1;
-			auto work = [&](unsigned t) {
-				for (size_t i = ns * t / nt; i < ns * (t + 1) / nt; i++) {
-					const Genotype k = call_genotype(s.ref_cnt[i], s.alt_cnt[i], s.ref_freq[i], s.alt_freq[i]);
-					gts[i] = k.gt;
-					gqs[i] = k.gt == GT_NONE ? 0 : genotype_quality(k.confidence);
-				}
-			};
-			if (nt == 1) work(0);
-			else { std::vector<std::thread> th; for (unsigned t = 0; t < nt; t++) th.emplace_back(work, t); for (auto &x : th) x.join(); }
-		}
+		SiteCalls calls;
+		call_sites(s, calls);
+		build(s.pos, chrs, calls.gt.data(), calls.gq.data(), &sum);
+	}
+	// from precomputed calls, one per site (the device caller's: vg_sample_calls_fetch)
+	CallBook(const std::vector<uint32_t> &pos, const std::vector<ChrLen> &chrs, const SiteCalls &calls, CallSummary &sum) { build(pos, chrs, calls.gt.data(), calls.gq.data(), &sum); }
+	// EVERY site under its key, called or not, sites of one key in genome order: the key -> sites structure of a joint file, built once
+	// for all samples (find() returns the first site of a key, the others follow it)
+	CallBook(const std::vector<uint32_t> &pos, const std::vector<ChrLen> &chrs) { build(pos, chrs, nullptr, nullptr, nullptr); }
+
+private:
+	void build(const std::vector<uint32_t> &pos, const std::vector<ChrLen> &chrs, const uint8_t *gts, const int32_t *gqs, CallSummary *sum)
+	{
+		const size_t ns = pos.size();
 		// sites ascend over the concatenated genome: walk the chromosome table alongside them
 		size_t c = 0, c_of_list = SIZE_MAX;
 		std::vector<CalledSite> *list = nullptr;                 // by_name_[chrs[c].name], looked up once per chromosome
 		uint64_t before = 0;                                     // bases in chromosomes 0 .. c-1
 		for (size_t i = 0; i < ns; i++) {
-			const uint64_t g = s.pos[i];
+			const uint64_t g = pos[i];
 			while (c < chrs.size() && g - before > chrs[c].len) before += chrs[c++].len;
-			struct { uint8_t gt; } k{gts[i]};
-			if (k.gt == GT_NONE) continue;
-			(k.gt == GT_HOM_REF ? sum.ref : k.gt == GT_HOM_ALT ? sum.alt : sum.het)++;
+			const uint8_t gt = gts ? gts[i] : (uint8_t)GT_NONE;
+			if (gts) {
+				if (gt == GT_NONE) continue;
+				(gt == GT_HOM_REF ? sum->ref : gt == GT_HOM_ALT ? sum->alt : sum->het)++;
+			}
 			if (c == chrs.size()) continue;                      // beyond the last chromosome: no name to print it under
-			if (c != c_of_list) { list = &by_name_[chrs[c].name]; c_of_list = c; list->reserve(list->size() + (ns - i) / 4); }
-			list->push_back(CalledSite{g - before, (uint32_t)i, (uint8_t)k.gt, gqs[i]});
+			if (c != c_of_list) { list = &by_name_[chrs[c].name]; c_of_list = c; list->reserve(list->size() + (gts ? (ns - i) / 4 : 0)); }
+			list->push_back(CalledSite{g - before, (uint32_t)i, gt, gts ? (int)gqs[i] : 0});
 		}
-		// two chromosomes with one name share a key space; keep, per position, the site that comes last in genome order
+		// two chromosomes with one name share a key space; keep, per position, the site that comes last in genome order (a book of
+		// every site keeps them all: which of them is a sample's last CALLED one differs from sample to sample)
 		for (auto &kv : by_name_) {
 			std::vector<CalledSite> &v = kv.second;
 			if (std::is_sorted(v.begin(), v.end(), [](const CalledSite &a, const CalledSite &b) { return a.local < b.local; }) &&
 			    std::adjacent_find(v.begin(), v.end(), [](const CalledSite &a, const CalledSite &b) { return a.local == b.local; }) == v.end())
 				continue;
 			std::stable_sort(v.begin(), v.end(), [](const CalledSite &a, const CalledSite &b) { return a.local != b.local ? a.local < b.local : a.order < b.order; });
+			if (!gts) continue;
 			size_t w = 0;
 			for (size_t r = 0; r < v.size(); r++) { if (w && v[w - 1].local == v[r].local) v[w - 1] = v[r]; else v[w++] = v[r]; }
 			v.resize(w);
 		}
 	}
 
+public:
 	// The reference compares the strings  name + "$" + decimal(position)  and  chrom + "$" + POS-column.  A decimal number
 	// holds no '$', so the two are equal exactly when the text after the LAST '$' of the right-hand side is the canonical
 	// decimal form of the position and the text before it is the name.
@@ -201,6 +186,9 @@ public:
 		h.at = (size_t)(at - list.begin());
 		return &*at;
 	}
+
+	// one past the last site of the list the hint's last find() looked in
+	static const CalledSite *list_end(const Hint &h) { return h.list->data() + h.list->size(); }
 
 private:
 	std::map<std::string, std::vector<CalledSite>> by_name_;
@@ -370,31 +358,27 @@ bool read_whole_file(const std::string &path, std::string &text)
 	return ok;
 }
 
-CallSummary write_genotyped_vcf(const SiteCounts &s, const std::vector<ChrLen> &chrlens, const std::string &vcf_in, const std::string &vcf_out, const std::string *vcf_text)
+namespace {
+
+unsigned vcf_threads()
 {
-	CallSummary sum;
-	const bool clocks = getenv("VARGENO_VCF_CLOCKS") != nullptr;
-	struct timespec c0, c1, c2; clock_gettime(CLOCK_MONOTONIC, &c0);
-	double t_annot = 0, t_write = 0;
-	auto lap = [](const timespec &a, const timespec &b) { return (double)(b.tv_sec - a.tv_sec) + 1e-9 * (double)(b.tv_nsec - a.tv_nsec); };
-	const CallBook book(s, chrlens, sum);
-	clock_gettime(CLOCK_MONOTONIC, &c1);
-	bool ok = vcf_text != nullptr;
-	std::string own;
-	if (!vcf_text) own = slurp(vcf_in, ok);
-	const std::string &text = vcf_text ? *vcf_text : own;
-	struct timespec c1b; clock_gettime(CLOCK_MONOTONIC, &c1b);
-	if (!ok) { fprintf(stderr, "Error opening: %s . You have failed.\n", vcf_in.c_str()); return sum; }
-	FILE *out = fopen(vcf_out.c_str(), "wb");
-	if (!out) throw Error{"cannot write " + vcf_out};
 	unsigned threads = std::max(1u, std::min(std::thread::hardware_concurrency(), 32u));
 	if (const char *e = getenv("VARGENO_THREADS")) if (atoi(e) > 0) threads = (unsigned)atoi(e);
+	return threads;
+}
 
-	Layout lay;
+// The pass over the SNP list's bytes, shared by the single-sample and the joint writer.  header(p, end, dst) takes the lines that
+// one thread reads in file order and stops in front of the first data line that can be annotated independently of its
+// neighbours; line(ln, dst, scratch) annotates one such line.  Returns the seconds spent in fwrite.
+template <class Header, class Line>
+double vcf_pass(const std::string &text, FILE *out, unsigned threads, Header header, Line line)
+{
+	double t_write = 0;
+	auto lap = [](const timespec &a, const timespec &b) { return (double)(b.tv_sec - a.tv_sec) + 1e-9 * (double)(b.tv_nsec - a.tv_nsec); };
 	const char *p = text.data(), *const end = p + text.size();
 	while (p < end) {
 		std::string seq;
-		ordered_lines(p, end, lay, book, seq);
+		header(p, end, seq);
 		fwrite(seq.data(), 1, seq.size(), out);
 		// a run of data lines: up to the next line that starts with '#' (the reference re-reads header lines wherever they
 		// stand, so they fence the run), cut at line starts into one piece per thread
@@ -420,7 +404,7 @@ CallSummary write_genotyped_vcf(const SiteCounts &s, const std::vector<ChrLen> &
 			piece[t].reserve((size_t)(e - q) + (size_t)(e - q) / 4 + 4096);          // (a line grows by ~":GT:GQ" + the two values)
 			Scratch sc;
 			try {
-				while (q < e) { const Span ln = next_line(q, e); if (ln.size()) annotate(ln, book, lay, false, nullptr, piece[t], sc); }
+				while (q < e) { const Span ln = next_line(q, e); if (ln.size()) line(ln, piece[t], sc); }
 			} catch (const Error &x) { err[t] = x.msg; }
 		};
 		if (nt == 1) work(0);
@@ -430,15 +414,122 @@ CallSummary write_genotyped_vcf(const SiteCounts &s, const std::vector<ChrLen> &
 			for (auto &x : th) x.join();
 		}
 		for (unsigned t = 0; t < nt; t++) if (!err[t].empty()) { fclose(out); throw Error{err[t]}; }
-		clock_gettime(CLOCK_MONOTONIC, &c2);
+		struct timespec c2, c3; clock_gettime(CLOCK_MONOTONIC, &c2);
 		for (unsigned t = 0; t < nt; t++) fwrite(piece[t].data(), 1, piece[t].size(), out);          // (positioned writes by several threads are slower: one inode lock)
-		struct timespec c3; clock_gettime(CLOCK_MONOTONIC, &c3);
+		clock_gettime(CLOCK_MONOTONIC, &c3);
 		t_write += lap(c2, c3);
 		p = stop;
 	}
+	return t_write;
+}
+
+}  // namespace
+
+CallSummary write_genotyped_vcf(const SiteCounts &s, const std::vector<ChrLen> &chrlens, const std::string &vcf_in, const std::string &vcf_out, const std::string *vcf_text, const SiteCalls *calls)
+{
+	CallSummary sum;
+	const bool clocks = getenv("VARGENO_VCF_CLOCKS") != nullptr;
+	struct timespec c0, c1; clock_gettime(CLOCK_MONOTONIC, &c0);
+	auto lap = [](const timespec &a, const timespec &b) { return (double)(b.tv_sec - a.tv_sec) + 1e-9 * (double)(b.tv_nsec - a.tv_nsec); };
+	const CallBook book = calls ? CallBook(s.pos, chrlens, *calls, sum) : CallBook(s, chrlens, sum);
+	clock_gettime(CLOCK_MONOTONIC, &c1);
+	bool ok = vcf_text != nullptr;
+	std::string own;
+	if (!vcf_text) own = slurp(vcf_in, ok);
+	const std::string &text = vcf_text ? *vcf_text : own;
+	struct timespec c1b; clock_gettime(CLOCK_MONOTONIC, &c1b);
+	if (!ok) { fprintf(stderr, "Error opening: %s . You have failed.\n", vcf_in.c_str()); return sum; }
+	FILE *out = fopen(vcf_out.c_str(), "wb");
+	if (!out) throw Error{"cannot write " + vcf_out};
+
+	Layout lay;
+	const double t_write = vcf_pass(text, out, vcf_threads(),
+	                                [&](const char *&p, const char *end, std::string &dst) { ordered_lines(p, end, lay, book, dst); },
+	                                [&](Span ln, std::string &dst, Scratch &sc) { annotate(ln, book, lay, false, nullptr, dst, sc); });
 	if (fclose(out) != 0) throw Error{"cannot write " + vcf_out};
-	if (clocks) { struct timespec c4; clock_gettime(CLOCK_MONOTONIC, &c4); t_annot = lap(c1b, c4) - t_write; fprintf(stderr, "vcf: calls + book %.3f s, SNP list read %.3f s, lines %.3f s, write %.3f s\n", lap(c0, c1), lap(c1, c1b), t_annot, t_write); }
+	if (clocks) { struct timespec c4; clock_gettime(CLOCK_MONOTONIC, &c4); fprintf(stderr, "vcf: calls + book %.3f s, SNP list read %.3f s, lines %.3f s, write %.3f s\n", lap(c0, c1), lap(c1, c1b), lap(c1b, c4) - t_write, t_write); }
 	return sum;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the joint file: one line per site, one column per sample (no reference counterpart; README "Cohorts")
+// ------------------------------------------------------------------------------------------------
+// A data line is written iff at least one sample's own VCF would contain it: its first eight fields, GT:GQ, then per sample what
+// that sample's own VCF shows for the record -- the call of the LAST site of the record's key, in genome order, that the sample
+// has called -- or ./.:. if its VCF drops the record.
+void write_joint_vcf(const std::vector<uint32_t> &pos, const std::vector<ChrLen> &chrlens, const std::vector<JointSample> &samples, const std::string &vcf_in, const std::string &vcf_out, const std::string *vcf_text)
+{
+	for (const JointSample &js : samples)
+		if (js.calls.gt.size() != pos.size() || js.calls.gq.size() != pos.size()) throw Error{"sample " + js.name + " has calls for another number of sites than the index has"};
+	const CallBook book(pos, chrlens);
+	bool ok = vcf_text != nullptr;
+	std::string own;
+	if (!vcf_text) own = slurp(vcf_in, ok);
+	const std::string &text = vcf_text ? *vcf_text : own;
+	if (!ok) throw Error{"Error opening: " + vcf_in + " . You have failed."};
+	FILE *out = fopen(vcf_out.c_str(), "wb");
+	if (!out) throw Error{"cannot write " + vcf_out};
+
+	const size_t n = samples.size();
+	bool declares_gt = false, declares_gq = false;
+	auto first_eight = [](Span ln) {
+		const char *q = ln.b;
+		for (int k = 0; k < 8 && q; k++) { q = (const char *)memchr(q, '\t', (size_t)(ln.e - q)); if (q && k < 7) q++; }
+		return Span{ln.b, q ? q : ln.e};
+	};
+	auto header = [&](const char *&p, const char *end, std::string &dst) {
+		while (p < end) {
+			const char *at = p;
+			const Span ln = next_line(p, end);
+			if (ln.size() == 0) continue;
+			if (ln.b[0] != '#') { p = at; return; }
+			if (ln.size() > 1 && ln.b[1] == '#') {
+				dst.append(ln.b, ln.e).push_back('\n');
+				const std::string meta(ln.b, ln.e);
+				if (meta.find("ID=GT,") != std::string::npos) declares_gt = true;
+				else if (meta.find("ID=GQ,") != std::string::npos) declares_gq = true;
+			} else {
+				if (!declares_gt) dst += kGtDecl;
+				if (!declares_gq) dst += kGqDecl;
+				const Span cols = first_eight(ln);
+				dst.append(cols.b, cols.e) += "\tFORMAT";
+				for (const JointSample &js : samples) { dst.push_back('\t'); dst += js.name; }
+				dst.push_back('\n');
+			}
+		}
+	};
+	auto line = [&](Span ln, std::string &dst, Scratch &sc) {
+		if (count_fields(ln, '\t') < 2) return;
+		const Span chrom = field(ln, '\t', 0), ps = field(ln, '\t', 1);
+		std::string &key = sc.key;
+		key.clear();
+		if (chrom.size() == 0 || chrom.b[0] != 'c') key = "chr";
+		key.append(chrom.b, chrom.e).push_back('$');
+		key.append(ps.b, ps.e);
+		const CalledSite *first = book.find(key, sc.hint);
+		if (!first) return;
+		const CalledSite *last = first + 1;                        // [first, last): the sites of this key, in genome order
+		for (const CalledSite *e = CallBook::list_end(sc.hint); last < e && last->local == first->local; last++) {}
+		std::string &cols = sc.smp;
+		cols.clear();
+		bool any = false;
+		for (size_t j = 0; j < n; j++) {
+			const SiteCalls &c = samples[j].calls;
+			const CalledSite *hit = nullptr;
+			for (const CalledSite *q = last; q > first && !hit;) { q--; if (c.gt[q->order] != GT_NONE) hit = q; }
+			if (!hit) { cols += "\t./.:."; continue; }
+			any = true;
+			char buf[24];
+			snprintf(buf, sizeof buf, "\t%s:%d", gt_text(c.gt[hit->order]), (int)c.gq[hit->order]);
+			cols += buf;
+		}
+		if (!any) return;
+		const Span head = first_eight(ln);
+		dst.append(head.b, head.e) += "\tGT:GQ";
+		dst.append(cols).push_back('\n');
+	};
+	vcf_pass(text, out, vcf_threads(), header, line);
+	if (fclose(out) != 0) throw Error{"cannot write " + vcf_out};
 }
 
 }  // namespace vgh

@@ -2,6 +2,7 @@
 //   vargeno index <ref.fa> <snps.vcf> <prefix>
 //   vargeno geno  <prefix> <reads.fq> <snps.vcf> <out.vcf>
 //   vargeno cohort <prefix> <manifest> <snps.vcf>     many samples against ONE resident index (no reference counterpart; run_cohort)
+//   vargeno joint  <prefix> <manifest> <snps.vcf> <joint.vcf>   the same cohort as ONE multi-sample VCF: a line per site, a column per sample
 // Same positional arguments, file names, messages and exit codes as upstream.  `geno` drives the
 // HIP library through the C-ABI of include/vargeno_hip.h only.  Extra knobs come from the
 // environment so that the argument list stays the reference's:
@@ -29,6 +30,9 @@
 //   VARGENO_PIPE_COPIERS=n  a FASTQ that is not a regular file: copier threads the one reader deals the pipe's pages to (default 4, at most 16;
 //                         0: the plain read() loop; see PipeIngest)
 //   VARGENO_COHORT_INFLIGHT=n  cohort: samples genotyped at the same time, each in a sample plane of its own (default 4)
+//   VARGENO_CALLER=device|host  geno, cohort: where the genotypes are called -- `device`: by the caller kernel, where the counters live
+//                         (vg_sample_calls_fetch: 2 bytes per site cross the link; no device memory for it: the host loop after all, one
+//                         line under VARGENO_VERBOSE); `host` (the default): the host loop over the fetched counters.  `joint` always asks the device
 //   VARGENO_VERBOSE=1     stderr: the index plan and start-up report, one "ingest, replica g:" line per route taken, the "reads:" line with
 //                         the wall time phase by phase; index: the "cuts:" line
 //   VARGENO_STATS=1       the kernel's counting build: events per read (vg_set_stats; off by default here, it carries ~50 more registers per lane)
@@ -48,6 +52,7 @@
 //   VARGENO_DENSE_BF=0|1    reference bit vectors populated up front (1) or lazily zeroed (0) (default: 1 for a FASTA > 256 MB)
 //   VARGENO_WRITE_MODE=pwrite|stream|mmap  how the dictionary files are written (default pwrite)
 //   VARGENO_STREAM_QUEUE=n  stream mode: bytes queued for the writer thread before producers wait (default 2 GiB)
+#include <ctype.h>
 #include <errno.h>
 #include <fcntl.h>
 #include <limits.h>
@@ -81,6 +86,7 @@ static void print_help()
 	fprintf(stderr, "index   Generate index            <input FASTA> <input SNPs in VCF> <index_prefix>\n");
 	fprintf(stderr, "geno    Perform genotyping        <index_prefix> <input FASTQ> <input SNPs in VCF> <output file in VCF>\n");
 	fprintf(stderr, "cohort  Genotype many samples     <index_prefix> <manifest: one <input FASTQ><TAB><output file in VCF> per line> <input SNPs in VCF>\n");
+	fprintf(stderr, "joint   ... into one VCF          <index_prefix> <manifest: one <input FASTQ><TAB><sample name> per line> <input SNPs in VCF> <output file in VCF>\n");
 }
 static void arg_check(int argc, int expected)
 {
@@ -130,6 +136,7 @@ struct GenoOptions {
 	// and are inflated there; `host` (the default until profiles/bgzf_ingest.txt says otherwise): inflated here, then the once-only route
 	const int bgzf_threads = std::max(1, std::min(env_int("VARGENO_BGZF_THREADS", vgh::bgzf_threads_default(hw)), 256));
 	const bool bgzf_device = std::string(env_str("VARGENO_BGZF")) == "device";
+	const bool caller_device = std::string(env_str("VARGENO_CALLER")) == "device";      // genotypes from the caller kernel (default: the host loop)
 	explicit GenoOptions(int devices) : have(devices)
 	{
 		if (ngpu > have && !share) ngpu = have;
@@ -908,16 +915,36 @@ static void fetch_sites(vg_index *ix, vgh::SiteCounts &sc)
 }
 // The counters of the sample selected on every replica, summed over the replicas.  One process, n devices: one RCCL all-reduce of
 // the per-site counters over xGMI (VARGENO_FORCE_RCCL=1 also sends a single device through it, which is the identity)
-static void fetch_selected_counts(const GenoOptions &o, std::vector<vg_index *> &ix, vgh::SiteCounts &sc)
+static void reduce_selected_counts(const GenoOptions &o, std::vector<vg_index *> &ix)
 {
 	if (o.ngpu > 1 || o.force_rccl) VG_CHECK(vg_counts_allreduce_devices(ix.data(), o.ngpu));
-	const uint64_t ns = vg_num_sites(ix[0]);
+}
+static void fetch_reduced_counts(vg_index *ix, vgh::SiteCounts &sc)
+{
+	const uint64_t ns = vg_num_sites(ix);
 	sc.ref_cnt.resize(ns); sc.alt_cnt.resize(ns);
-	VG_CHECK(vg_counts_fetch(ix[0], sc.ref_cnt.data(), sc.alt_cnt.data()));
+	VG_CHECK(vg_counts_fetch(ix, sc.ref_cnt.data(), sc.alt_cnt.data()));
+}
+// The calls of the selected sample from the caller kernel, its counters already summed over the replicas.  false: the device had no
+// memory for the caller's buffers (VG_ENOMEM; the handle stays usable) -- the host loop over the fetched counters takes its place
+static bool fetch_reduced_calls(const GenoOptions &o, vg_index *ix, vgh::SiteCalls &calls)
+{
+	const uint64_t ns = vg_num_sites(ix);
+	calls.gt.resize(ns); calls.gq.resize(ns);
+	uint64_t escaped = 0;
+	const int rc = vg_sample_calls_fetch(ix, calls.gt.data(), calls.gq.data(), &escaped);
+	if (rc == VG_ENOMEM) {
+		if (o.verbose) fprintf(stderr, "caller: no device memory for the caller kernel (%s): genotypes are called on the host\n", vg_last_error());
+		calls.gt.clear(); calls.gq.clear();
+		return false;
+	}
+	if (rc != VG_OK) { fprintf(stderr, "vargeno: vg_sample_calls_fetch failed (%d): %s\n", rc, vg_last_error()); exit(EXIT_FAILURE); }
+	if (o.verbose) fprintf(stderr, "caller: device, %lu sites, %lu recomputed on the host\n", (unsigned long)ns, (unsigned long)escaped);
+	return true;
 }
 
-// The per-site counters of the whole job, as the caller wants them.  false: said on stderr
-static bool fetch_counts(const GenoOptions &o, std::vector<vg_index *> &ix, vgh::SiteCounts &sc)
+// The per-site counters of the whole job, as the caller wants them -- or, with VARGENO_CALLER=device, the calls.  false: said on stderr
+static bool fetch_counts(const GenoOptions &o, std::vector<vg_index *> &ix, vgh::SiteCounts &sc, vgh::SiteCalls &calls, bool &have_calls)
 {
 	{
 		// util.c:103: the reference aborts on a read with a character other than ACGTN (and writes no VCF); the library counts
@@ -928,7 +955,9 @@ static bool fetch_counts(const GenoOptions &o, std::vector<vg_index *> &ix, vgh:
 		if (invalid) { fprintf(stderr, "vargeno: %lu reads contain a character other than ACGTN (the reference aborts on these)\n", (unsigned long)invalid); return false; }
 	}
 	fetch_sites(ix[0], sc);
-	fetch_selected_counts(o, ix, sc);
+	reduce_selected_counts(o, ix);
+	have_calls = o.caller_device && fetch_reduced_calls(o, ix[0], calls);      // VARGENO_CALLER=device: the calls instead of the counters
+	if (!have_calls || o.dump_counts) fetch_reduced_counts(ix[0], sc);
 	const uint64_t ns = sc.pos.size();
 	if (const char *dump = o.dump_counts) {                              // the saturated counters as the caller gets them: ref counts, then alt counts, one byte per site
 		FILE *f = fopen(dump, "wb");
@@ -1023,9 +1052,11 @@ static int run_geno(const std::string &prefix, const std::string &fastq, const s
 	for (auto *h : ix) VG_CHECK(vg_sync(h));
 	clock_gettime(CLOCK_MONOTONIC, &t[2]);
 	vgh::SiteCounts sc;
-	if (!fetch_counts(o, ix, sc)) return EXIT_FAILURE;
+	vgh::SiteCalls calls;
+	bool have_calls = false;
+	if (!fetch_counts(o, ix, sc, calls, have_calls)) return EXIT_FAILURE;
 	if (vcf_reader.joinable()) vcf_reader.join();
-	vgh::write_genotyped_vcf(sc, chrlens, vcf_in, vcf_out, vcf_ok ? &vcf_text : nullptr);
+	vgh::write_genotyped_vcf(sc, chrlens, vcf_in, vcf_out, vcf_ok ? &vcf_text : nullptr, have_calls ? &calls : nullptr);
 	clock_gettime(CLOCK_MONOTONIC, &t[3]);
 	// The output is complete and closed.  What is left is giving back ~240 GB of device memory and the page-locked buffers, which the
 	// operating system does for a process that ends anyway: an orderly vg_index_close + runtime shut-down took 0.7 + 0.9 s of an
@@ -1048,7 +1079,8 @@ static int run_geno(const std::string &prefix, const std::string &fastq, const s
 struct CohortSample { std::string fastq, out; int line = 0; };
 
 // The manifest: one "<reads.fq><TAB><out.vcf>" per line; blank lines and lines that start with '#' are skipped.  false: said on stderr
-static bool read_manifest(const std::string &path, std::vector<CohortSample> &samples)
+// joint: the second field is the sample's NAME, the header of its column (`out` holds it): unique, and without whitespace
+static bool read_manifest(const std::string &path, std::vector<CohortSample> &samples, bool joint = false)
 {
 	std::string text;
 	if (!vgh::read_whole_file(path, text)) { fprintf(stderr, "vargeno: cannot open the manifest %s\n", path.c_str()); return false; }
@@ -1062,22 +1094,30 @@ static bool read_manifest(const std::string &path, std::vector<CohortSample> &sa
 		if (!ln.empty() && ln.back() == '\r') ln.pop_back();
 		if (ln.empty() || ln[0] == '#') continue;
 		const size_t tab = ln.find('\t');
-		if (tab == std::string::npos || tab == 0 || tab + 1 >= ln.size()) { fprintf(stderr, "vargeno: %s line %d: expected <input FASTQ><TAB><output file in VCF>\n", path.c_str(), line); return false; }
+		if (tab == std::string::npos || tab == 0 || tab + 1 >= ln.size()) { fprintf(stderr, "vargeno: %s line %d: expected <input FASTQ><TAB>%s\n", path.c_str(), line, joint ? "<sample name>" : "<output file in VCF>"); return false; }
 		CohortSample s;
 		s.fastq = ln.substr(0, tab); s.out = ln.substr(tab + 1); s.line = line;
+		if (joint && std::any_of(s.out.begin(), s.out.end(), [](char c) { return isspace((unsigned char)c) != 0; })) { fprintf(stderr, "vargeno: %s line %d: the sample name \"%s\" contains whitespace\n", path.c_str(), line, s.out.c_str()); return false; }
 		for (const CohortSample &before : samples)
-			if (before.out == s.out) { fprintf(stderr, "vargeno: %s line %d: output file %s is already the output of line %d\n", path.c_str(), line, s.out.c_str(), before.line); return false; }
+			if (before.out == s.out) {
+				if (joint) fprintf(stderr, "vargeno: %s line %d: sample name %s is already the name of line %d\n", path.c_str(), line, s.out.c_str(), before.line);
+				else fprintf(stderr, "vargeno: %s line %d: output file %s is already the output of line %d\n", path.c_str(), line, s.out.c_str(), before.line);
+				return false;
+			}
 		samples.push_back(s);
 	}
 	if (samples.empty()) { fprintf(stderr, "vargeno: the manifest %s names no sample\n", path.c_str()); return false; }
 	return true;
 }
 
-static int run_cohort(const std::string &prefix, const std::string &manifest, const std::string &vcf_in)
+// joint_out: `vargeno joint` -- the same workers, but a finished sample's calls are kept as a column (from the caller kernel; the
+// host loop when the device has no memory for it) and ONE file is written after the last sample, if every sample succeeded.
+static int run_cohort(const std::string &prefix, const std::string &manifest, const std::string &vcf_in, const std::string *joint_out = nullptr)
 {
 	struct timespec t0; clock_gettime(CLOCK_MONOTONIC, &t0);
+	const bool joint = joint_out != nullptr;
 	std::vector<CohortSample> samples;
-	if (!read_manifest(manifest, samples)) return EXIT_FAILURE;      // (before any device is touched)
+	if (!read_manifest(manifest, samples, joint)) return EXIT_FAILURE;      // (before any device is touched)
 	std::vector<vgh::ChrLen> chrlens = vgh::read_chrlens(prefix + ".chrlens");
 	const int have = vg_device_count();
 	if (have <= 0) { fprintf(stderr, "vargeno: no HIP device found (this build has no CPU path)\n"); return EXIT_FAILURE; }
@@ -1104,10 +1144,27 @@ static int run_cohort(const std::string &prefix, const std::string &manifest, co
 	std::vector<std::mutex> mu((size_t)o.ngpu);                       // one caller at a time per handle
 	std::atomic<size_t> next{0};
 	std::atomic<int> failed{0};
+	std::vector<vgh::JointSample> columns(joint ? samples.size() : 0);      // joint: the samples' calls, in manifest order
+	const char *const nothing = joint ? "no joint file written" : "no VCF written";
+	// what happens to a finished sample: its own VCF, or its column of the joint file.  false: said on stderr
+	auto deliver = [&](size_t at, vgh::SiteCounts &sc, vgh::SiteCalls &calls, bool have_calls) -> bool {
+		const CohortSample &s = samples[at];
+		if (joint) {
+			if (!have_calls) { sc.pos = sites.pos; sc.ref_freq = sites.ref_freq; sc.alt_freq = sites.alt_freq; vgh::call_sites(sc, calls); }
+			columns[at].name = s.out;
+			columns[at].calls = std::move(calls);
+			return true;
+		}
+		sc.pos = sites.pos; sc.ref_freq = sites.ref_freq; sc.alt_freq = sites.alt_freq;
+		try { vgh::write_genotyped_vcf(sc, chrlens, vcf_in, s.out, &vcf_text, have_calls ? &calls : nullptr); }
+		catch (const vgh::Error &e) { fprintf(stderr, "vargeno: %s line %d: %s\n", manifest.c_str(), s.line, e.msg.c_str()); return false; }
+		return true;
+	};
 	auto worker = [&](uint32_t plane) {
 		for (;;) {
 			const size_t at = next.fetch_add(1);
 			if (at >= samples.size()) return;
+			if (joint && failed.load()) return;                           // (no joint file any more: the samples left are not read)
 			const CohortSample &s = samples[at];
 			struct timespec a; clock_gettime(CLOCK_MONOTONIC, &a);
 			if (plain_gzip(s.fastq)) { failed.store(1); continue; }
@@ -1139,43 +1196,64 @@ static int run_cohort(const std::string &prefix, const std::string &manifest, co
 					VG_CHECK(vg_sample_select(ix[(size_t)g], plane));
 					VG_CHECK(vg_reads_submit(ix[(size_t)g], rb.bases.data(), rb.quals.data(), rb.offsets.data(), n));
 				});
-				if (bz) { bz->finish(); if (!bz->error.empty()) { fprintf(stderr, "vargeno: %s line %d: %s: no VCF written\n", manifest.c_str(), s.line, bz->error.c_str()); bz_ok = false; } }
+				if (bz) { bz->finish(); if (!bz->error.empty()) { fprintf(stderr, "vargeno: %s line %d: %s: %s\n", manifest.c_str(), s.line, bz->error.c_str(), nothing); bz_ok = false; } }
 			}
 			bz.reset();
 			close(file_fd);
 			// the sample is complete: its plane summed over the replicas, fetched and zeroed for the worker's next sample
 			vgh::SiteCounts sc;
+			vgh::SiteCalls calls;
+			bool have_calls = false;
 			uint64_t invalid = 0;
 			{
 				for (auto &m : mu) m.lock();
 				for (auto *h : ix) VG_CHECK(vg_sample_select(h, plane));
 				for (auto *h : ix) { uint64_t bad = 0; VG_CHECK(vg_sample_invalid_reads(h, plane, &bad)); invalid += bad; }
-				if (!invalid && bz_ok) fetch_selected_counts(o, ix, sc);
+				if (!invalid && bz_ok) {
+					reduce_selected_counts(o, ix);
+					have_calls = (joint || o.caller_device) && fetch_reduced_calls(o, ix[0], calls);
+					if (!have_calls) fetch_reduced_counts(ix[0], sc);
+				}
 				for (auto *h : ix) VG_CHECK(vg_sample_reset(h, plane));
 				for (auto &m : mu) m.unlock();
 			}
 			if (!bz_ok) { failed.store(1); continue; }
 			if (invalid) {
 				// util.c:103: the reference aborts on such a read and writes no VCF; the other samples go on
-				fprintf(stderr, "vargeno: %s line %d: %lu reads of %s contain a character other than ACGTN (the reference aborts on these): no VCF written\n", manifest.c_str(), s.line, (unsigned long)invalid, s.fastq.c_str());
+				fprintf(stderr, "vargeno: %s line %d: %lu reads of %s contain a character other than ACGTN (the reference aborts on these): %s\n", manifest.c_str(), s.line, (unsigned long)invalid, s.fastq.c_str(), nothing);
 				failed.store(1);
 				continue;
 			}
-			sc.pos = sites.pos; sc.ref_freq = sites.ref_freq; sc.alt_freq = sites.alt_freq;
-			try { vgh::write_genotyped_vcf(sc, chrlens, vcf_in, s.out, &vcf_text); }
-			catch (const vgh::Error &e) { fprintf(stderr, "vargeno: %s line %d: %s\n", manifest.c_str(), s.line, e.msg.c_str()); failed.store(1); continue; }
-			if (o.verbose) { struct timespec b; clock_gettime(CLOCK_MONOTONIC, &b); fprintf(stderr, "sample, line %d: reads: %lu  plane: %u  open -> VCF: %.3f s\n", s.line, (unsigned long)total, plane, secs(a, b)); }
+			if (!deliver(at, sc, calls, have_calls)) { failed.store(1); continue; }
+			if (o.verbose) { struct timespec b; clock_gettime(CLOCK_MONOTONIC, &b); fprintf(stderr, "sample, line %d: reads: %lu  plane: %u  open -> %s: %.3f s\n", s.line, (unsigned long)total, plane, joint ? "calls" : "VCF", secs(a, b)); }
 		}
 	};
 	std::vector<std::thread> th;
 	for (int w = 0; w < K; w++) th.emplace_back(worker, (uint32_t)w);
 	for (auto &t : th) t.join();
+	if (joint && !failed.load()) {
+		try { vgh::write_joint_vcf(sites.pos, chrlens, columns, vcf_in, *joint_out, &vcf_text); }
+		catch (const vgh::Error &e) { fprintf(stderr, "vargeno: %s\n", e.msg.c_str()); failed.store(1); }
+	}
 	struct timespec t2; clock_gettime(CLOCK_MONOTONIC, &t2);
 	if (o.verbose) fprintf(stderr, "cohort: samples: %lu  in flight: %d  gpus: %d  index load %.3f s  wall: %.3f s\n", (unsigned long)samples.size(), K, o.ngpu, secs(t0, t1), secs(t0, t2));
 	const int status = failed.load() ? EXIT_FAILURE : EXIT_SUCCESS;
 	if (o.orderly_exit) { for (auto *h : ix) vg_index_close(h); return status; }
 	fflush(stdout); fflush(stderr);
 	_exit(status);                                                    // (as `geno`: the outputs are closed, the operating system takes the memory back)
+}
+
+// a counts table of the hidden `callvcf` / `jointvcf` commands: "pos ref_freq alt_freq ref_cnt alt_cnt" per line
+static void read_counts_table(const std::string &path, vgh::SiteCounts &sc)
+{
+	FILE *f = fopen(path.c_str(), "r");
+	if (!f) throw vgh::Error{"cannot open " + path};
+	unsigned long p; unsigned rf, af, rc, ac;
+	while (fscanf(f, "%lu %u %u %u %u", &p, &rf, &af, &rc, &ac) == 5) {
+		sc.pos.push_back((uint32_t)p); sc.ref_freq.push_back((uint8_t)rf); sc.alt_freq.push_back((uint8_t)af);
+		sc.ref_cnt.push_back((uint8_t)rc); sc.alt_cnt.push_back((uint8_t)ac);
+	}
+	fclose(f);
 }
 
 int main(int argc, const char *argv[])
@@ -1196,6 +1274,10 @@ int main(int argc, const char *argv[])
 		} else if (opt == "cohort") {
 			arg_check(argc, 3);
 			return run_cohort(argv[2], argv[3], argv[4]);
+		} else if (opt == "joint") {
+			arg_check(argc, 4);
+			const std::string out = argv[5];
+			return run_cohort(argv[2], argv[3], argv[4], &out);
 		} else if (opt == "bgzfcat") {
 			// hidden: a BGZF file's text on stdout, inflated by the host threads of the BgzfTextPipe (no device needed; tests/test_bgzf_cpu.py)
 			arg_check(argc, 1);
@@ -1306,15 +1388,29 @@ int main(int argc, const char *argv[])
 			// "pos ref_freq alt_freq ref_cnt alt_cnt" per line: <chrlens> <counts.txt> <snps.vcf> <out.vcf>
 			arg_check(argc, 4);
 			vgh::SiteCounts sc;
-			FILE *f = fopen(argv[3], "r");
-			if (!f) throw vgh::Error{std::string("cannot open ") + argv[3]};
-			unsigned long p; unsigned rf, af, rc, ac;
-			while (fscanf(f, "%lu %u %u %u %u", &p, &rf, &af, &rc, &ac) == 5) {
-				sc.pos.push_back((uint32_t)p); sc.ref_freq.push_back((uint8_t)rf); sc.alt_freq.push_back((uint8_t)af);
-				sc.ref_cnt.push_back((uint8_t)rc); sc.alt_cnt.push_back((uint8_t)ac);
-			}
-			fclose(f);
+			read_counts_table(argv[3], sc);
 			vgh::write_genotyped_vcf(sc, vgh::read_chrlens(argv[2]), argv[4], argv[5]);
+			return EXIT_SUCCESS;
+		} else if (opt == "jointvcf") {
+			// hidden: the joint writer alone, with the host caller, from one counts table per sample (callvcf's format; all list the same
+			// sites): <chrlens> <snps.vcf> <out.vcf> <name>=<counts.txt> ...  (no device needed; tests/test_joint_vcf_cpu.py)
+			if (argc < 6) { print_help(); return EXIT_FAILURE; }
+			std::vector<vgh::JointSample> columns;
+			std::vector<uint32_t> pos;
+			for (int a = 5; a < argc; a++) {
+				const std::string arg = argv[a];
+				const size_t eq = arg.find('=');
+				if (eq == std::string::npos || eq == 0 || eq + 1 >= arg.size()) { print_help(); return EXIT_FAILURE; }
+				vgh::SiteCounts sc;
+				read_counts_table(arg.substr(eq + 1), sc);
+				if (a == 5) pos = sc.pos;
+				else if (sc.pos != pos) throw vgh::Error{arg.substr(eq + 1) + " lists other sites than " + std::string(argv[5]).substr(std::string(argv[5]).find('=') + 1)};
+				vgh::JointSample js;
+				js.name = arg.substr(0, eq);
+				vgh::call_sites(sc, js.calls);
+				columns.push_back(std::move(js));
+			}
+			vgh::write_joint_vcf(pos, vgh::read_chrlens(argv[2]), columns, argv[3], argv[4]);
 			return EXIT_SUCCESS;
 		} else if (opt == "version") {
 			// hidden: the build ids (sha256 prefixes of the sources) of this binary and of the HIP library it loaded

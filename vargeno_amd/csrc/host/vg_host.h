@@ -77,7 +77,7 @@ private:
 // ends); *comp_next = offset of the block after them.  false: err says which block is bad.
 bool bgzf_inflate_span(int fd, uint64_t comp_from, uint64_t want_text, std::vector<uint8_t> &text, uint64_t *comp_next, std::string &err);
 
-// ---- caller + VCF writer (behaviour of reference src/qv.cc:1573-1747, 1789-1848) ---------------
+// ---- caller + VCF writer (behaviour of reference src/qv.cc:1573-1747, 1789-1848; the arithmetic is ../vg_caller.h) ----
 enum : uint8_t { GT_NONE = 0, GT_HOM_REF = 1, GT_HOM_ALT = 2, GT_HET = 3 };     // numbering of the reference's GTYPE_* (vartype.h)
 struct Genotype {
 	uint8_t gt;            // GT_*
@@ -96,9 +96,18 @@ struct SiteCounts {
 };
 // returns {ref calls, alt calls, het calls}
 struct CallSummary { uint64_t ref = 0, alt = 0, het = 0; };
+// one call per site: gt = GT_*, gq as the reference prints it (0 where gt is GT_NONE)
+struct SiteCalls { std::vector<uint8_t> gt; std::vector<int32_t> gq; };
+void call_sites(const SiteCounts &s, SiteCalls &out);                           // the host call loop
 // vcf_text: the SNP list's bytes if the caller has read them already (the command line reads them while the index is being opened)
+// calls: the sites' calls if the caller has them already (vg_sample_calls_fetch); the counters of `s` are not looked at then
 CallSummary write_genotyped_vcf(const SiteCounts &s, const std::vector<ChrLen> &chrlens,
-                                const std::string &vcf_in, const std::string &vcf_out, const std::string *vcf_text = nullptr);
+                                const std::string &vcf_in, const std::string &vcf_out, const std::string *vcf_text = nullptr, const SiteCalls *calls = nullptr);
+// One multi-sample VCF: a line per record that at least one sample's own VCF would contain, a column per sample in the given order.
+// Throws when the SNP list cannot be read or the file cannot be written.
+struct JointSample { std::string name; SiteCalls calls; };
+void write_joint_vcf(const std::vector<uint32_t> &pos, const std::vector<ChrLen> &chrlens, const std::vector<JointSample> &samples,
+                     const std::string &vcf_in, const std::string &vcf_out, const std::string *vcf_text = nullptr);
 bool read_whole_file(const std::string &path, std::string &text);
 
 }  // namespace vgh

@@ -13,6 +13,7 @@
 #include "vg_allreduce_plan.h"
 #include "vg_arena.h"
 #include "vg_inflate.h"
+#include "vg_caller.h"
 
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -1225,6 +1226,13 @@ struct vg_index {
 	uint32_t spill_hint = 0;              // the deep tier's list of the last harvested batches (reads): sizes the next batch's deep-tier grid
 	uint64_t cum[4] = {0, 0, 0, 0};       // since reset: [0] wave-tier overflow, [1] lane-tier overflow, [2] lost, [3] reads with a character other than ACGTN
 	uint8_t *d_clamped = nullptr;         // [2 * n_sites] staging of vg_counts_fetch: min(63, sum), ref counts then alt counts
+	// the caller kernel's buffers (vg_sample_calls_fetch): ONE block outside the plan, taken at the first call -- the sites' two
+	// frequency columns, the u16 staging of the calls (4 bytes per site in all), the factor tables and the escape count
+	void *d_call_block = nullptr;
+	const uint8_t *d_site_rf = nullptr, *d_site_af = nullptr;
+	uint16_t *d_calls = nullptr;
+	const vg_caller_tables *d_call_tab = nullptr;
+	unsigned long long *d_call_esc = nullptr;
 	unsigned long long *d_stats = nullptr;
 	bool stats_enabled = true;
 	bool force_generic = false;           // VG_FORCE_GENERIC=1: skip the wave tier (tests compare the tiers)
@@ -3509,6 +3517,149 @@ extern "C" int vg_counts_fetch(vg_index *ix, uint8_t *ref_cnt, uint8_t *alt_cnt)
 	HIP_TRY(hipMemcpyAsync(alt_cnt, ix->d_clamped + ix->n_sites, ix->n_sites, hipMemcpyDeviceToHost, ix->stream));
 	HIP_TRY(hipStreamSynchronize(ix->stream));
 	return VG_OK;
+}
+
+// ---- the genotype caller on the device (vg_caller.h; reference qv.cc:1789-1848, GQ at :1681) ------------------------------------
+// One lane per site: the exact sums clamped as vg_clamp_counters does, the site's two frequency bytes, the shared caller over the
+// HOST's factor tables (staged in LDS once per block), one u16 out: gt << 14 | gq.  The device's log is not libm's, so a site
+// whose -10 ln(confidence) is within `guard` of an integer -- or whose confidence is not inside (0, 1) at all -- gets the escape
+// code and is counted: the host recomputes those.
+constexpr unsigned VG_CALL_BLOCK = 256, VG_CALL_MAX_GRID = 4096;
+__global__ __launch_bounds__(VG_CALL_BLOCK) void vg_call_kernel(const uint32_t *__restrict__ cnt, const uint8_t *__restrict__ ref_freq, const uint8_t *__restrict__ alt_freq,
+                                                                const vg_caller_tables *__restrict__ tab, uint64_t n_sites, double guard,
+                                                                uint16_t *__restrict__ calls, unsigned long long *__restrict__ n_escaped)
+{
+	__shared__ vg_caller_tables t;
+	{
+		constexpr unsigned words = sizeof(vg_caller_tables) / sizeof(double);
+		const double *src = (const double *)tab;
+		double *dst = (double *)&t;
+		for (unsigned k = threadIdx.x; k < words; k += VG_CALL_BLOCK) dst[k] = src[k];
+	}
+	__syncthreads();
+	uint32_t escaped = 0;
+	for (uint64_t s = (uint64_t)blockIdx.x * VG_CALL_BLOCK + threadIdx.x; s < n_sites; s += (uint64_t)gridDim.x * VG_CALL_BLOCK) {
+		const uint2 v = ((const uint2 *)cnt)[s];
+		const vg_site_call c = vg_call_site(t, v.x < 63u ? v.x : 63u, v.y < 63u ? v.y : 63u, ref_freq[s], alt_freq[s]);
+		uint32_t gq = 0;
+		if (c.gt != VGC_NONE) {
+			const double y = -10 * log(c.confidence);
+			if (vg_gq_settled(c.confidence, y, guard)) gq = (uint32_t)(int)y;
+			else { gq = VG_CALL_ESCAPE; escaped++; }
+		}
+		calls[s] = (uint16_t)((uint32_t)c.gt << 14 | gq);
+	}
+	for (int o = 32; o > 0; o >>= 1) escaped += __shfl_xor(escaped, o);
+	if ((threadIdx.x & 63) == 0 && escaped) atomicAdd(n_escaped, (unsigned long long)escaped);
+}
+
+static unsigned call_grid(uint64_t n) { return (unsigned)std::min<uint64_t>((n + VG_CALL_BLOCK - 1) / VG_CALL_BLOCK, VG_CALL_MAX_GRID); }
+static const vg_caller_tables &host_call_tables()
+{
+	static const vg_caller_tables t = [] { vg_caller_tables x; vg_caller_tables_fill(x); return x; }();
+	return t;
+}
+// u16 codes -> final values; a site with the escape code is recomputed here, with libm's logarithm
+static void resolve_calls(const uint16_t *code, const uint8_t *ref_cnt, const uint8_t *alt_cnt, const uint8_t *ref_freq, const uint8_t *alt_freq, uint64_t n, uint8_t *gt, int32_t *gq)
+{
+	const vg_caller_tables &t = host_call_tables();
+	for (uint64_t s = 0; s < n; s++) {
+		gt[s] = (uint8_t)(code[s] >> 14);
+		gq[s] = code[s] & VG_CALL_ESCAPE;
+		if (gq[s] == VG_CALL_ESCAPE) {
+			const vg_site_call c = vg_call_site(t, ref_cnt[s], alt_cnt[s], ref_freq[s], alt_freq[s]);
+			gt[s] = c.gt;
+			gq[s] = c.gt == VGC_NONE ? 0 : vg_genotype_quality(c.confidence);
+		}
+	}
+}
+
+// the handle's caller buffers, at first use.  VG_ENOMEM leaves the handle as it was
+static int call_buffers(vg_index *ix)
+{
+	if (ix->d_call_block) return VG_OK;
+	const uint64_t n = ix->n_sites, col = (n + 255) & ~255ull;
+	const size_t bytes = (size_t)(2 * col + ((2 * n + 255) & ~255ull) + ((sizeof(vg_caller_tables) + 255) & ~255ull) + 256);
+	void *q = nullptr;
+	if (vg_malloc_patient(&q, bytes) != hipSuccess) { (void)hipGetLastError(); return fail(VG_ENOMEM, "vg_sample_calls_fetch: no device memory for the caller's %s bytes", std::to_string(bytes).c_str()); }
+	uint8_t *b = (uint8_t *)q;
+	uint8_t *rf = b, *af = b + col;
+	uint16_t *calls = (uint16_t *)(b + 2 * col);
+	vg_caller_tables *tab = (vg_caller_tables *)(b + 2 * col + ((2 * n + 255) & ~255ull));
+	unsigned long long *esc = (unsigned long long *)((uint8_t *)tab + ((sizeof(vg_caller_tables) + 255) & ~255ull));
+	hipError_t e = hipSuccess;
+	if (n) { e = hipMemcpy(rf, ix->site_rf.data(), n, hipMemcpyHostToDevice); if (e == hipSuccess) e = hipMemcpy(af, ix->site_af.data(), n, hipMemcpyHostToDevice); }
+	if (e == hipSuccess) e = hipMemcpy(tab, &host_call_tables(), sizeof(vg_caller_tables), hipMemcpyHostToDevice);
+	if (e != hipSuccess) { (void)hipFree(q); return fail(VG_ENODEV, "vg_sample_calls_fetch: %s", hipGetErrorString(e)); }
+	ix->owned.push_back(q); ix->owned_bytes[q] = bytes; ix->dev_bytes += bytes;
+	ix->d_call_block = q; ix->d_site_rf = rf; ix->d_site_af = af; ix->d_calls = calls; ix->d_call_tab = tab; ix->d_call_esc = esc;
+	return VG_OK;
+}
+
+extern "C" int vg_sample_calls_fetch(vg_index *ix, uint8_t *gt, int32_t *gq, uint64_t *n_escaped)
+{
+	if (!ix || !gt || !gq) return fail(VG_EINVAL, "null argument");
+	int rc = vg_sync(ix);
+	if (rc) return rc;
+	if (n_escaped) *n_escaped = 0;
+	const uint64_t n = ix->n_sites;
+	if (n == 0) return VG_OK;
+	return guarded([&]() -> int {
+		HIP_TRY(hipSetDevice(ix->device));
+		std::vector<uint16_t> code((size_t)n);                    // (host memory first: bad_alloc is VG_ENOMEM too, before the device is asked)
+		if ((rc = call_buffers(ix))) return rc;
+		HIP_TRY(hipMemsetAsync(ix->d_call_esc, 0, sizeof(unsigned long long), ix->stream));
+		vg_call_kernel<<<call_grid(n), VG_CALL_BLOCK, 0, ix->stream>>>(sel_cnt(ix), ix->d_site_rf, ix->d_site_af, ix->d_call_tab, n, VG_CALL_GUARD_DEFAULT, ix->d_calls, ix->d_call_esc);
+		HIP_TRY(hipGetLastError());
+		unsigned long long esc = 0;
+		HIP_TRY(hipMemcpyAsync(code.data(), ix->d_calls, n * sizeof(uint16_t), hipMemcpyDeviceToHost, ix->stream));
+		HIP_TRY(hipMemcpyAsync(&esc, ix->d_call_esc, sizeof esc, hipMemcpyDeviceToHost, ix->stream));
+		HIP_TRY(hipStreamSynchronize(ix->stream));
+		std::vector<uint8_t> cnt;
+		if (esc) {                                                // the escaped sites' counters: the two clamped columns, as vg_counts_fetch takes them
+			cnt.resize((size_t)(2 * n));
+			vg_clamp_counters<<<(unsigned)std::min<uint64_t>((n + 255) / 256, 4096), 256, 0, ix->stream>>>(sel_cnt(ix), n, ix->d_clamped, ix->d_clamped + n);
+			HIP_TRY(hipGetLastError());
+			HIP_TRY(hipMemcpyAsync(cnt.data(), ix->d_clamped, 2 * n, hipMemcpyDeviceToHost, ix->stream));
+			HIP_TRY(hipStreamSynchronize(ix->stream));
+		}
+		resolve_calls(code.data(), cnt.data(), cnt.data() + (esc ? n : 0), ix->site_rf.data(), ix->site_af.data(), n, gt, gq);
+		if (n_escaped) *n_escaped = esc;
+		return VG_OK;
+	});
+}
+
+extern "C" int vg_call_device(int device, const uint8_t *ref_cnt, const uint8_t *alt_cnt, const uint8_t *ref_freq, const uint8_t *alt_freq, uint64_t n, double guard, uint8_t *gt, int32_t *gq, uint64_t *n_escaped)
+{
+	if (n_escaped) *n_escaped = 0;
+	if (n == 0) return VG_OK;
+	if (!ref_cnt || !alt_cnt || !ref_freq || !alt_freq || !gt || !gq) return fail(VG_EINVAL, "null argument");
+	if (!(guard > 0)) guard = VG_CALL_GUARD_DEFAULT;
+	if (!(guard < 0.5)) return fail(VG_EINVAL, "vg_call_device: a guard of 0.5 or more settles nothing");
+	return guarded([&]() -> int {
+		HIP_TRY(hipSetDevice(device));
+		std::vector<uint32_t> cnt((size_t)(2 * n));               // the kernel's input form: the counter array of a sample plane
+		for (uint64_t s = 0; s < n; s++) { cnt[2 * s] = ref_cnt[s]; cnt[2 * s + 1] = alt_cnt[s]; }
+		std::vector<uint16_t> code((size_t)n);
+		DevBuf<uint32_t> d_cnt; DevBuf<uint8_t> d_rf, d_af; DevBuf<uint16_t> d_code; DevBuf<vg_caller_tables> d_tab; DevBuf<unsigned long long> d_esc;
+		int rc;
+		if ((rc = d_cnt.reserve(2 * n, "site counters")) || (rc = d_rf.reserve(n, "reference frequencies")) || (rc = d_af.reserve(n, "alternative frequencies"))
+		    || (rc = d_code.reserve(n, "calls")) || (rc = d_tab.reserve(1, "caller tables")) || (rc = d_esc.reserve(1, "escape count"))) return rc;
+		HIP_TRY(hipMemcpy(d_cnt.p, cnt.data(), 2 * n * sizeof(uint32_t), hipMemcpyHostToDevice));
+		HIP_TRY(hipMemcpy(d_rf.p, ref_freq, n, hipMemcpyHostToDevice));
+		HIP_TRY(hipMemcpy(d_af.p, alt_freq, n, hipMemcpyHostToDevice));
+		HIP_TRY(hipMemcpy(d_tab.p, &host_call_tables(), sizeof(vg_caller_tables), hipMemcpyHostToDevice));
+		HIP_TRY(hipMemset(d_esc.p, 0, sizeof(unsigned long long)));
+		vg_call_kernel<<<call_grid(n), VG_CALL_BLOCK>>>(d_cnt.p, d_rf.p, d_af.p, d_tab.p, n, guard, d_code.p, d_esc.p);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipDeviceSynchronize());
+		unsigned long long esc = 0;
+		HIP_TRY(hipMemcpy(code.data(), d_code.p, n * sizeof(uint16_t), hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(&esc, d_esc.p, sizeof esc, hipMemcpyDeviceToHost));
+		resolve_calls(code.data(), ref_cnt, alt_cnt, ref_freq, alt_freq, n, gt, gq);
+		if (n_escaped) *n_escaped = esc;
+		return VG_OK;
+	});
 }
 
 extern "C" int vg_counts_reset(vg_index *ix)
