@@ -243,6 +243,39 @@ int  vg_fastq_stream_begin_bgzf(vg_index *ix);
  * whole block, 0. */
 int  vg_fastq_stream_bgzf_locate(vg_index *ix, uint64_t text_offset, uint64_t *block_offset, uint32_t *within);
 
+/* The same stream over BAM (a BGZF file whose inflated bytes are a header and binary records): after vg_fastq_stream_begin_bam,
+ * vg_fastq_stream_push takes the BAM file's bytes cut anywhere.  The library inflates the leading blocks on the host until the BAM
+ * header parses (blocks wholly inside it never go to the device; bytes that inflate to something else make the push return VG_EIO);
+ * everything behind goes up compressed, is inflated on the device and FRAMED there: the chain of block_size fields is walked in
+ * fixed 64 KiB windows, speculatively in parallel and then confirmed (csrc/vg_bam.h has the record rules, vargeno_hip.hip the
+ * kernels); a record that straddles two slots is carried on the device.  No text exists on this route: bases are unpacked from
+ * their nibbles into the batch, the qualities are reduced to the read's gate word.  What a record becomes is defined by the
+ * equivalent FASTQ text (vg_bam_to_fastq_host): secondary / supplementary records (flag 0x900) and records without bases are
+ * skipped; flag 0x10 reverse-complements.
+ * vg_fastq_stream_end reports kept records, and consumed / last_record_start as offsets in the INFLATED BAM stream: consumed is the
+ * first byte not framed (a record boundary), last_record_start the last kept record; vg_fastq_stream_bgzf_locate maps both.  A
+ * chunk is refused (and everything behind it) when a record's block_size is smaller than its fields announce or above 65 532, or
+ * a read is longer than 1022 bases: the caller converts from `consumed` on the host.  A stream that ends inside the header or inside
+ * a record makes vg_fastq_stream_end return VG_EIO with the inflated offset in vg_last_error(); bad blocks as for BGZF.
+ * vg_bam_stream_stats: the counters of the handle's last BAM stream (any pointer may be NULL): kept records, records skipped by flag,
+ * skipped for l_seq == 0, and windows whose speculated entry was wrong and that were walked again.  Waits for the framing. */
+int  vg_fastq_stream_begin_bam(vg_index *ix);
+int  vg_bam_stream_stats(vg_index *ix, uint64_t *kept, uint64_t *skipped_flag, uint64_t *skipped_empty, uint64_t *repairs);
+
+/* BAM without a handle.
+ * vg_bam_frame_device: a whole BAM file in host memory through the stream's kernels as ONE slot, the flat batch layout back:
+ * offsets[0 .. n] (offsets[n] = total bases), the bases as ASCII, one gate word per read (bit c: quality character c < '8', for
+ * c < min(length / 32, 32)).  stats[4] = kept, skipped by flag, skipped empty, repairs.  *bad_offset = UINT64_MAX when the whole
+ * stream was framed, else the inflated offset of the first byte that was not (a refusal: vg_last_error() says which; the stream ends
+ * inside a record or the header; a bad block) -- the call still returns VG_OK and the arrays hold what was framed (nothing, after a
+ * refusal).  VG_EIO: not BAM.  VG_ETOOBIG: the reads do not fit cap_rec / cap_bases.  Files of less than 2 GiB.
+ * vg_bam_to_fastq_host: the equivalent FASTQ text, by the host build of the same record parser; no device is touched.  *n_records =
+ * records converted; *bad_offset as above (UINT64_MAX, or the inflated offset where conversion stopped: the stream ends inside a
+ * record or the header, a block_size too small for its record, a bad block); text of the records before it is there. */
+int  vg_bam_frame_device(int device, const uint8_t *bgzf, uint64_t nbytes, uint64_t *offsets, uint64_t cap_rec, uint8_t *bases, uint64_t cap_bases, uint32_t *gate,
+                         uint64_t *n_records, uint64_t stats[4], uint64_t *bad_offset);
+int  vg_bam_to_fastq_host(const uint8_t *bgzf, uint64_t nbytes, uint8_t *text, uint64_t text_cap, uint64_t *text_len, uint64_t *n_records, uint64_t *bad_offset);
+
 /* BGZF without a handle: the whole blocks of bgzf[0, nbytes) inflated into text[0, text_cap) in host memory -- on `device` by the
  * stream's kernel (compressed bytes up, text back), or on the host by the host build of the same decoder.  *text_len = bytes of text
  * written, *consumed = compressed bytes used (trailing bytes of an incomplete block are not), *bad_block_offset = compressed offset

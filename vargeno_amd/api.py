@@ -150,14 +150,19 @@ class GenoIndex:
         check(lib().vg_reads_submit_store(self._h, store._h))
         self._stores.append(store)        # (released by sync / counts / stats / close: the batches read the store's memory until then)
 
-    def fastq_stream(self, chunks, host_threads=None, bgzf=False):
+    def fastq_stream(self, chunks, host_threads=None, bgzf=False, bam=False):
         """FASTQ text as a stream of byte chunks cut anywhere (numpy uint8 arrays / bytes; pinned host memory copies at link
         speed): records are framed across the cuts -- on the device (host_threads None or 0), or framed and 2-bit packed by
         that many host threads inside the library (-1: the library picks).  Returns (records, bytes consumed, start of the
         last framed record, refused) once everything pushed has been processed.
         bgzf=True: the chunks are BGZF bytes (cut anywhere too), inflated on the device; the offsets returned are offsets in the
-        uncompressed text.  A bad block raises VgError (VG_EIO) naming its compressed offset; what was framed before it counts."""
-        if bgzf:
+        uncompressed text.  A bad block raises VgError (VG_EIO) naming its compressed offset; what was framed before it counts.
+        bam=True: the chunks are a BAM file's bytes, inflated and framed on the device; records counts kept records, the offsets
+        are offsets in the inflated BAM stream (bam_stats() has the stream's other counters).  A stream that ends inside the
+        header or a record raises VgError (VG_EIO) naming the inflated offset."""
+        if bam:
+            check(lib().vg_fastq_stream_begin_bam(self._h))
+        elif bgzf:
             check(lib().vg_fastq_stream_begin_bgzf(self._h))
         elif host_threads is None:
             check(lib().vg_fastq_stream_begin(self._h))
@@ -169,6 +174,12 @@ class GenoIndex:
         n, used, last, refused = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_int()
         check(lib().vg_fastq_stream_end(self._h, C.byref(n), C.byref(used), C.byref(last), C.byref(refused)))
         return int(n.value), int(used.value), int(last.value), bool(refused.value)
+
+    def bam_stats(self):
+        """(kept, skipped by flag, skipped empty, repairs) of the handle's last BAM stream."""
+        v = [C.c_uint64() for _ in range(4)]
+        check(lib().vg_bam_stream_stats(self._h, *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
 
     def bgzf_locate(self, text_offset):
         """(compressed offset of the block, offset inside its text) of an uncompressed offset of the last BGZF stream."""
@@ -424,6 +435,34 @@ def bgzf_inflate(data, device=0, out=None, text_cap=None):
     else:
         check(lib().vg_bgzf_inflate_device(int(device), _ptr(a), len(a), _ptr(out), int(text_cap), C.byref(n), C.byref(used), C.byref(bad)))
     return out[:int(n.value)].tobytes(), int(used.value), (None if bad.value == 2 ** 64 - 1 else int(bad.value))
+
+
+def bam_to_fastq(data):
+    """The equivalent FASTQ text of a BAM file's bytes, by the host build of the record parser (no device): (text as bytes, records
+    converted, inflated offset where conversion stopped or None when the whole stream was converted).  Raises VgError (VG_EIO) when
+    the bytes are not BAM."""
+    a = _u8(data)
+    cap = 64 + 3 * sum(b[4] for b in bgzf_scan(a)[0])          # a record's text: name + 2 characters per base + 7, from >= 37 + name + 1.5 bytes per base
+    out = np.zeros(cap, dtype=np.uint8)
+    n, recs, bad = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    check(lib().vg_bam_to_fastq_host(_ptr(a), len(a), _ptr(out), cap, C.byref(n), C.byref(recs), C.byref(bad)))
+    return out[:int(n.value)].tobytes(), int(recs.value), (None if bad.value == 2 ** 64 - 1 else int(bad.value))
+
+
+def bam_frame(data, device=0):
+    """A BAM file's bytes framed on `device` by the stream's kernels, as one slot: (offsets uint64[n + 1], bases uint8, gate words
+    uint32[n], (kept, skipped by flag, skipped empty, repairs), inflated offset of the first byte not framed or None)."""
+    a = _u8(data)
+    text_n = sum(b[4] for b in bgzf_scan(a)[0])
+    cap_rec, cap_bases = text_n // 36 + 2, text_n // 3 * 2 + 64
+    offsets = np.zeros(cap_rec + 1, dtype=np.uint64)
+    bases = np.zeros(cap_bases, dtype=np.uint8)
+    gate = np.zeros(cap_rec, dtype=np.uint32)
+    stats = np.zeros(4, dtype=np.uint64)
+    n, bad = C.c_uint64(), C.c_uint64()
+    check(lib().vg_bam_frame_device(int(device), _ptr(a), len(a), _ptr(offsets), cap_rec, _ptr(bases), cap_bases, _ptr(gate), C.byref(n), _ptr(stats), C.byref(bad)))
+    k = int(n.value)
+    return offsets[:k + 1].copy(), bases[:int(offsets[k])].copy(), gate[:k].copy(), tuple(int(v) for v in stats), (None if bad.value == 2 ** 64 - 1 else int(bad.value))
 
 
 # the caller kernel's launch: lanes per block, and the most blocks of a grid (a longer array wraps round the grid-stride loop)

@@ -21,15 +21,6 @@ namespace vgh {
 
 static std::string block_error(uint64_t comp_off, int rc) { return "BGZF block at compressed offset " + std::to_string(comp_off) + ": " + vg_inflate_strerror(rc); }
 
-FastqKind sniff_fastq(int fd)
-{
-	uint8_t head[4096];
-	const ssize_t n = pread(fd, head, sizeof head, 0);
-	if (n < 3 || !vg_is_gzip(head, (uint64_t)n)) return FastqKind::Text;
-	vg_bgzf_block b;
-	return vg_bgzf_header(head, (uint64_t)n, &b) == VG_INF_EHEADER ? FastqKind::PlainGzip : FastqKind::Bgzf;     // (0 / 1: a BGZF header, whole or as far as 4 KiB show)
-}
-
 // pread all of [at, at + n); returns the bytes read (short at the end of the file), -1 on an error
 static int64_t pread_all(int fd, uint8_t *dst, uint64_t n, uint64_t at)
 {
@@ -42,6 +33,30 @@ static int64_t pread_all(int fd, uint8_t *dst, uint64_t n, uint64_t at)
 		done += (uint64_t)g;
 	}
 	return (int64_t)done;
+}
+
+FastqKind sniff_fastq(int fd)
+{
+	uint8_t head[4096];
+	const ssize_t n = pread(fd, head, sizeof head, 0);
+	if (n >= 4 && !memcmp(head, "CRAM", 4)) return FastqKind::Cram;
+	if (n < 3 || !vg_is_gzip(head, (uint64_t)n)) return FastqKind::Text;
+	vg_bgzf_block b;
+	if (vg_bgzf_header(head, (uint64_t)n, &b) == VG_INF_EHEADER) return FastqKind::PlainGzip;     // (0 / 1: a BGZF header, whole or as far as 4 KiB show)
+	// BGZF: the first four inflated bytes say whether it is BAM (they may lie in several blocks: a block can hold one byte, or none)
+	std::vector<uint8_t> lead(1 << 18);
+	const int64_t got = pread_all(fd, lead.data(), lead.size(), 0);
+	std::vector<vg_bgzf_block> bl;
+	uint64_t tail = 0, bad = 0;
+	if (got > 0) (void)vg_bgzf_scan(lead.data(), (uint64_t)got, 0, 0, bl, &tail, &bad);
+	uint8_t first[4 + VG_BGZF_MAX_ISIZE];
+	size_t have = 0;
+	for (const vg_bgzf_block &k : bl) {
+		if (have >= 4) break;
+		if (vg_inflate_block_host(lead.data() + k.in_off, k.in_len, first + have, k.isize, k.crc)) break;
+		have += k.isize;
+	}
+	return have >= 4 && !memcmp(first, "BAM\1", 4) ? FastqKind::Bam : FastqKind::Bgzf;
 }
 
 // the whole blocks of buf inflated into text (sized here) by `threads` threads; "" or the first (lowest) block's error
@@ -194,6 +209,13 @@ void BgzfTextPipe::finish()
 {
 	if (p->producer.joinable()) p->producer.join();
 	if (p->writer.joinable()) p->writer.join();
+}
+std::string BgzfTextPipe::describe(const char *what, bool) const
+{
+	char line[512];
+	snprintf(line, sizeof line, "ingest, %s: BGZF inflated by %d host threads: %.3f GB compressed (%.2f GB/s), %.3f GB of text (%.2f GB/s) in %.2f s", what, p->threads,
+	         (double)comp_bytes / 1e9, seconds > 0 ? (double)comp_bytes / 1e9 / seconds : 0.0, (double)text_bytes / 1e9, seconds > 0 ? (double)text_bytes / 1e9 / seconds : 0.0, seconds);
+	return line;
 }
 
 }  // namespace vgh

@@ -77,6 +77,7 @@
 #include "../../../include/vargeno_hip.h"
 #include "vg_host.h"
 #include "bgzf.cpp"       // the host side of the BGZF routes, in this translation unit (csrc/Makefile: builds that list the four host files get it)
+#include "bam.cpp"        // the host side of the BAM routes, the same way; behind bgzf.cpp, whose helpers it uses
 
 static void print_help()
 {
@@ -220,8 +221,10 @@ struct StreamResult {
 	int refused = 0;
 	std::string error;                                               // empty: fine
 };
-// bgzf: the bytes are BGZF (vg_fastq_stream_begin_bgzf) -- the same ring over the compressed file; the result's offsets are text offsets.
-static StreamResult stream_range(vg_index *ix, int fd, uint64_t lo, uint64_t hi, uint64_t chunk, int n_readers, int pack_threads, bool bgzf = false)
+// STREAM_BGZF: the bytes are BGZF (vg_fastq_stream_begin_bgzf) -- the same ring over the compressed file; the result's offsets are text
+// offsets.  STREAM_BAM: a BAM file (vg_fastq_stream_begin_bam); the offsets are offsets in the inflated BAM stream.
+enum StreamBytes { STREAM_TEXT, STREAM_BGZF, STREAM_BAM };
+static StreamResult stream_range(vg_index *ix, int fd, uint64_t lo, uint64_t hi, uint64_t chunk, int n_readers, int pack_threads, StreamBytes bytes = STREAM_TEXT)
 {
 	StreamResult res;
 	const int NBUF = 4;
@@ -232,7 +235,7 @@ static StreamResult stream_range(vg_index *ix, int fd, uint64_t lo, uint64_t hi,
 		if (!ring[(size_t)i]) { pageable[(size_t)i].resize((size_t)chunk); ring[(size_t)i] = pageable[(size_t)i].data(); }
 	}
 	RangeReader rr(fd, lo, hi, chunk, n_readers, ring);
-	int rc = bgzf ? vg_fastq_stream_begin_bgzf(ix) : pack_threads > 0 ? vg_fastq_stream_begin_packed(ix, pack_threads) : vg_fastq_stream_begin(ix);
+	int rc = bytes == STREAM_BAM ? vg_fastq_stream_begin_bam(ix) : bytes == STREAM_BGZF ? vg_fastq_stream_begin_bgzf(ix) : pack_threads > 0 ? vg_fastq_stream_begin_packed(ix, pack_threads) : vg_fastq_stream_begin(ix);
 	for (uint64_t i = 0; i < rr.n_chunks() && rc == VG_OK; i++) {
 		if (!rr.wait(i)) break;
 		rc = vg_fastq_stream_push(ix, rr.buf(i), rr.chunk_len(i));
@@ -630,7 +633,8 @@ struct FastqInput {
 	bool cuts_ok = false;                      // a regular file, and cut[] holds a record-aligned range per replica
 	std::vector<uint64_t> cut;
 	bool bgzf_device = false;                  // a BGZF file, one replica, VARGENO_BGZF=device: the compressed bytes are streamed to the device
-	std::unique_ptr<vgh::BgzfTextPipe> bz_pipe;   // a BGZF file on every other route: inflated by host threads; fd is the pipe's read end
+	bool bam = false;                          // ... the file is BAM: the device frames its records (bgzf_device), or the pipe below converts them to text
+	std::unique_ptr<vgh::TextPipe> bz_pipe;    // a BGZF / BAM file on every other route: inflated (and converted) by host threads; fd is the pipe's read end
 	int file_fd = -1;                          // ... and the file itself
 };
 // Bytes of a once-only stream that are still in memory, for the host reader: [base, base + the spans); the descriptor continues behind them
@@ -665,10 +669,13 @@ static bool open_fastq(const std::string &fastq, const GenoOptions &o, FastqInpu
 	in.fsize = (uint64_t)sb.st_size;
 	in.once_only = !S_ISREG(sb.st_mode);
 	// a regular file says what it is (a FIFO or /dev/stdin cannot be looked at without taking its bytes: it is text, as before)
-	if (!in.once_only && vgh::sniff_fastq(in.fd) == vgh::FastqKind::Bgzf) {
+	const vgh::FastqKind kind = in.once_only ? vgh::FastqKind::Text : vgh::sniff_fastq(in.fd);
+	if (kind == vgh::FastqKind::Bgzf || kind == vgh::FastqKind::Bam) {
+		in.bam = kind == vgh::FastqKind::Bam;
 		if (o.bgzf_device && o.ngpu == 1 && !o.host_framing) { in.bgzf_device = true; return true; }
 		in.file_fd = in.fd;
-		in.bz_pipe.reset(new vgh::BgzfTextPipe(in.file_fd, 0, 0, o.bgzf_threads));
+		if (in.bam) in.bz_pipe.reset(new vgh::BamTextPipe(in.file_fd, 0, 0, o.bgzf_threads, true, 0));
+		else in.bz_pipe.reset(new vgh::BgzfTextPipe(in.file_fd, 0, 0, o.bgzf_threads));
 		if (in.bz_pipe->read_fd() < 0) { fprintf(stderr, "vargeno: %s\n", in.bz_pipe->error.c_str()); return false; }
 		in.fd = in.bz_pipe->read_fd();
 		in.once_only = true;
@@ -844,13 +851,13 @@ static HostHandover once_only_route(const GenoOptions &o, PipeIngest &pipe_in, c
 // span, and a BgzfTextPipe inflates the rest of the file into a pipe -- the span plus a descriptor, what the host reader takes.
 struct BgzfTakeover {
 	std::vector<uint8_t> text;
-	std::unique_ptr<vgh::BgzfTextPipe> rest;
+	std::unique_ptr<vgh::TextPipe> rest;
 	HostSpans mem;
 };
 static HostHandover bgzf_device_route(const GenoOptions &o, const FastqInput &in, vg_index *ix, BgzfTakeover &tk)
 {
 	struct timespec a, b; clock_gettime(CLOCK_MONOTONIC, &a);
-	const StreamResult r = stream_range(ix, in.fd, 0, in.fsize, o.chunk(16), o.range_readers(), 0, true);
+	const StreamResult r = stream_range(ix, in.fd, 0, in.fsize, o.chunk(16), o.range_readers(), 0, STREAM_BGZF);
 	if (!r.error.empty()) { fprintf(stderr, "vargeno: %s\n", r.error.c_str()); exit(EXIT_FAILURE); }
 	clock_gettime(CLOCK_MONOTONIC, &b);
 	const uint64_t from = r.nrec ? r.last : r.used;                      // the span starts with the last framed record (it primes the stale buffers)
@@ -867,13 +874,46 @@ static HostHandover bgzf_device_route(const GenoOptions &o, const FastqInput &in
 	                       (double)in.fsize / 1e9, (double)in.fsize / 1e9 / secs(a, b), (double)r.used / 1e9, (double)r.used / 1e9 / secs(a, b), secs(a, b), r.refused ? "; the stream framing refused a chunk: the host reader takes the rest" : "");
 	return HostHandover{r.nrec, r.used, r.nrec ? r.last : UINT64_MAX, 0};
 }
-// a BgzfTextPipe has met the end of its text: what it has to say (false: a bad block, said on stderr)
-static bool bgzf_pipe_verdict(const GenoOptions &o, vgh::BgzfTextPipe &bp, const char *what)
+// One replica, a BAM file, VARGENO_BGZF=device: as above, and the device frames the records too (vg_fastq_stream_begin_bam) -- no
+// text exists on this route.  The offsets it reports are offsets in the inflated BAM stream.  The host take-over behind it (a
+// refusal: a read beyond the reference's line buffer, ...) needs TEXT: the last kept record is converted here and is the memory span
+// that primes the host reader's line buffers (they must hold what they would after that record), and a BamTextPipe converts the
+// records from `consumed` on into a pipe.  The reader's offsets are offsets in that text: the span is [0, its length).
+static HostHandover bam_device_route(const GenoOptions &o, const FastqInput &in, vg_index *ix, BgzfTakeover &tk)
+{
+	struct timespec a, b; clock_gettime(CLOCK_MONOTONIC, &a);
+	const StreamResult r = stream_range(ix, in.fd, 0, in.fsize, o.chunk(16), o.range_readers(), 0, STREAM_BAM);
+	if (!r.error.empty()) { fprintf(stderr, "vargeno: %s\n", r.error.c_str()); exit(EXIT_FAILURE); }
+	clock_gettime(CLOCK_MONOTONIC, &b);
+	uint64_t kept = 0, skipped_flag = 0, skipped_empty = 0, repairs = 0;
+	VG_CHECK(vg_bam_stream_stats(ix, &kept, &skipped_flag, &skipped_empty, &repairs));
+	uint64_t block = 0;
+	uint32_t within = 0;
+	std::string err, primer;
+	if (r.nrec) {
+		VG_CHECK(vg_fastq_stream_bgzf_locate(ix, r.last, &block, &within));
+		if (!vgh::bam_record_text(in.fd, block, within, primer, err)) { fprintf(stderr, "vargeno: %s\n", err.c_str()); exit(EXIT_FAILURE); }
+	}
+	tk.text.assign(primer.begin(), primer.end());
+	tk.mem.base = 0;
+	tk.mem.spans.assign(1, std::make_pair((const uint8_t *)tk.text.data(), tk.text.size()));
+	VG_CHECK(vg_fastq_stream_bgzf_locate(ix, r.used, &block, &within));
+	tk.rest.reset(new vgh::BamTextPipe(in.fd, block, within, o.bgzf_threads, false, r.used));
+	if (tk.rest->read_fd() < 0) { fprintf(stderr, "vargeno: %s\n", tk.rest->error.c_str()); exit(EXIT_FAILURE); }
+	if (o.verbose) fprintf(stderr, "ingest, replica 0: BAM inflated and framed on the device: %lu records kept, %lu skipped by flag, %lu skipped empty, %lu window repairs; %.3f GB compressed (%.2f GB/s) in %.2f s%s\n",
+	                       (unsigned long)kept, (unsigned long)skipped_flag, (unsigned long)skipped_empty, (unsigned long)repairs, (double)in.fsize / 1e9, (double)in.fsize / 1e9 / secs(a, b), secs(a, b),
+	                       r.refused ? "; the device refused a chunk: the host converts the rest" : "");
+	return HostHandover{r.nrec, tk.text.size(), r.nrec ? 0 : UINT64_MAX, 0};
+}
+// a TextPipe has met the end of its text: what it has to say (false: a bad block or record, said on stderr)
+static bool bgzf_pipe_verdict(const GenoOptions &o, vgh::TextPipe &bp, const char *what, bool tail_of_device_route = false)
 {
 	bp.finish();
 	if (!bp.error.empty()) { fprintf(stderr, "vargeno: %s\n", bp.error.c_str()); return false; }
-	if (o.verbose) fprintf(stderr, "ingest, %s: BGZF inflated by %d host threads: %.3f GB compressed (%.2f GB/s), %.3f GB of text (%.2f GB/s) in %.2f s\n", what, o.bgzf_threads,
-	                       (double)bp.comp_bytes / 1e9, bp.seconds > 0 ? (double)bp.comp_bytes / 1e9 / bp.seconds : 0.0, (double)bp.text_bytes / 1e9, bp.seconds > 0 ? (double)bp.text_bytes / 1e9 / bp.seconds : 0.0, bp.seconds);
+	if (o.verbose) {
+		const std::string line = bp.describe(what, tail_of_device_route);
+		if (!line.empty()) fprintf(stderr, "%s\n", line.c_str());
+	}
 	return true;
 }
 
@@ -985,15 +1025,20 @@ static void verbose_report(uint64_t total, int ngpu, const struct timespec t[4])
 	}
 }
 
-// A regular file with gzip magic but no BGZF header: refused by name (framed as text it would yield garbage).  Said on stderr.
+// A regular file with gzip magic but no BGZF header, or a CRAM file: refused by name (framed as text it would yield garbage).  Said on stderr.
 static bool plain_gzip(const std::string &fastq)
 {
 	struct stat sb;
 	if (stat(fastq.c_str(), &sb) != 0 || !S_ISREG(sb.st_mode)) return false;      // (a FIFO is opened once, by its reader)
 	const int fd = open(fastq.c_str(), O_RDONLY);
 	if (fd < 0) return false;                                          // (open_fastq says so)
-	const bool plain = vgh::sniff_fastq(fd) == vgh::FastqKind::PlainGzip;
+	const vgh::FastqKind kind = vgh::sniff_fastq(fd);
+	const bool plain = kind == vgh::FastqKind::PlainGzip;
 	close(fd);
+	if (kind == vgh::FastqKind::Cram) {
+		fprintf(stderr, "vargeno: %s is a CRAM file: CRAM is not read here -- pipe `samtools fastq %s` through a FIFO (mkfifo reads.fq; samtools fastq %s > reads.fq &) and pass the FIFO\n", fastq.c_str(), fastq.c_str(), fastq.c_str());
+		return true;
+	}
 	if (plain) fprintf(stderr, "vargeno: %s is gzip but not BGZF: only BGZF (bgzip) is inflated here -- recompress with bgzip, or pass <(zcat %s)\n", fastq.c_str(), fastq.c_str());
 	return plain;
 }
@@ -1037,7 +1082,7 @@ static int run_geno(const std::string &prefix, const std::string &fastq, const s
 	int reader_fd = in.fd;
 	BgzfTakeover tk;
 	if (pipe_in) { hand = once_only_route(o, *pipe_in, ix, store); mem.base = pipe_in->span_base; mem.spans = pipe_in->spans; reader_mem = &mem; }
-	else if (in.bgzf_device) { hand = bgzf_device_route(o, in, ix[0], tk); reader_mem = &tk.mem; reader_fd = tk.rest->read_fd(); }
+	else if (in.bgzf_device) { hand = in.bam ? bam_device_route(o, in, ix[0], tk) : bgzf_device_route(o, in, ix[0], tk); reader_mem = &tk.mem; reader_fd = tk.rest->read_fd(); }
 	else if (!o.host_framing) {
 		hand = ranged_route(o, in, ix, store, pre);
 		pre.clear();
@@ -1048,7 +1093,7 @@ static int run_geno(const std::string &prefix, const std::string &fastq, const s
 	});
 	// a bad block ends a BgzfTextPipe's text early: no VCF from half a file
 	if (in.bz_pipe && !bgzf_pipe_verdict(o, *in.bz_pipe, "all replicas")) return EXIT_FAILURE;
-	if (tk.rest && !bgzf_pipe_verdict(o, *tk.rest, "the host reader's tail")) return EXIT_FAILURE;
+	if (tk.rest && !bgzf_pipe_verdict(o, *tk.rest, "the host reader's tail", true)) return EXIT_FAILURE;
 	for (auto *h : ix) VG_CHECK(vg_sync(h));
 	clock_gettime(CLOCK_MONOTONIC, &t[2]);
 	vgh::SiteCounts sc;
@@ -1171,9 +1216,12 @@ static int run_cohort(const std::string &prefix, const std::string &manifest, co
 			const int file_fd = open(s.fastq.c_str(), O_RDONLY);
 			if (file_fd < 0) { fprintf(stderr, "vargeno: %s line %d: cannot open %s\n", manifest.c_str(), s.line, s.fastq.c_str()); failed.store(1); continue; }
 			// a BGZF sample is inflated by host threads into a pipe: the once-only route below takes the pipe's descriptor in place of the file's
-			std::unique_ptr<vgh::BgzfTextPipe> bz;
+			// (a BAM sample likewise, its records converted to text on the way)
+			std::unique_ptr<vgh::TextPipe> bz;
 			struct stat sb;
-			if (fstat(file_fd, &sb) == 0 && S_ISREG(sb.st_mode) && vgh::sniff_fastq(file_fd) == vgh::FastqKind::Bgzf) bz.reset(new vgh::BgzfTextPipe(file_fd, 0, 0, std::max(1, o.bgzf_threads / K)));
+			const vgh::FastqKind kind = fstat(file_fd, &sb) == 0 && S_ISREG(sb.st_mode) ? vgh::sniff_fastq(file_fd) : vgh::FastqKind::Text;
+			if (kind == vgh::FastqKind::Bgzf) bz.reset(new vgh::BgzfTextPipe(file_fd, 0, 0, std::max(1, o.bgzf_threads / K)));
+			else if (kind == vgh::FastqKind::Bam) bz.reset(new vgh::BamTextPipe(file_fd, 0, 0, std::max(1, o.bgzf_threads / K), true, 0));
 			const int fd = bz ? bz->read_fd() : file_fd;
 			(void)fcntl(fd, F_SETPIPE_SZ, 1 << 20);
 			uint64_t total = 0;
@@ -1285,6 +1333,29 @@ int main(int argc, const char *argv[])
 			const int fd = open(argv[2], O_RDONLY);
 			if (fd < 0) throw vgh::Error{std::string("cannot open ") + argv[2]};
 			vgh::BgzfTextPipe bp(fd, 0, 0, std::max(1, std::min(env_int("VARGENO_BGZF_THREADS", vgh::bgzf_threads_default(usable_cpus())), 256)));
+			if (bp.read_fd() < 0) throw vgh::Error{bp.error};
+			std::vector<uint8_t> buf(1 << 20);
+			for (;;) {
+				const ssize_t n = read(bp.read_fd(), buf.data(), buf.size());
+				if (n < 0 && errno == EINTR) continue;
+				if (n <= 0) break;
+				if (fwrite(buf.data(), 1, (size_t)n, stdout) != (size_t)n) throw vgh::Error{"cannot write to stdout"};
+			}
+			bp.finish();
+			if (!bp.error.empty()) throw vgh::Error{bp.error};
+			return EXIT_SUCCESS;
+		} else if (opt == "bamcat") {
+			// hidden: a BAM file's equivalent FASTQ text on stdout, by the host threads of the BamTextPipe (no device needed; tests/test_bam_cpu.py)
+			arg_check(argc, 1);
+			if (plain_gzip(argv[2])) return EXIT_FAILURE;
+			const int fd = open(argv[2], O_RDONLY);
+			if (fd < 0) throw vgh::Error{std::string("cannot open ") + argv[2]};
+			if (vgh::sniff_fastq(fd) != vgh::FastqKind::Bam) {
+				uint64_t end = 0; int32_t n_ref = 0; std::string why;
+				(void)vgh::bam_header_info(fd, &end, &n_ref, why);            // (says what is wrong: not BGZF, not BAM, a header cut short)
+				throw vgh::Error{std::string(argv[2]) + ": " + (why.empty() ? "not a BAM file" : why)};
+			}
+			vgh::BamTextPipe bp(fd, 0, 0, std::max(1, std::min(env_int("VARGENO_BGZF_THREADS", vgh::bgzf_threads_default(usable_cpus())), 256)), true, 0);
 			if (bp.read_fd() < 0) throw vgh::Error{bp.error};
 			std::vector<uint8_t> buf(1 << 20);
 			for (;;) {

@@ -48,27 +48,41 @@ private:
 };
 
 // ---- BGZF-compressed FASTQ on the host (bgzf.cpp; the decoder is ../vg_inflate.h, shared with the device kernel) ----
-enum class FastqKind { Text, Bgzf, PlainGzip };
-// what a regular file's first bytes say: BGZF (gzip magic with the `BC` subfield), some other gzip, or anything else (text)
+enum class FastqKind { Text, Bgzf, PlainGzip, Bam, Cram };
+// what a regular file's first bytes say: BGZF (gzip magic with the `BC` subfield) -- BAM when its first inflated bytes are the magic
+// BAM\1 --, some other gzip, CRAM (its magic), or anything else (text)
 FastqKind sniff_fastq(int fd);
 // VARGENO_BGZF_THREADS' default: min(usable CPUs, 8)
 int bgzf_threads_default(int usable_cpus);
+// A compressed reads file as a once-only descriptor of FASTQ text, produced by threads of its own.  read_fd() is an ordinary FASTQ
+// descriptor (owned by the object: it must outlive its reader; < 0: no pipe could be made, error says so).  After the reader has met
+// the end of the text, finish() and look at `error`: a bad or incomplete block (or record) ends the text early and is named there.
+class TextPipe {
+public:
+	virtual ~TextPipe() {}
+	virtual int read_fd() const = 0;
+	virtual void finish() = 0;
+	// after finish(), for VARGENO_VERBOSE: the stderr line that says what the pipe did, "" when there is nothing to say.  what: whom
+	// it fed; takeover: it ran behind a device route, which has said its own line
+	virtual std::string describe(const char *what, bool takeover) const = 0;
+	std::string error;
+	uint64_t comp_bytes = 0, text_bytes = 0;       // valid after finish()
+	double seconds = 0.0;                          // from construction to the end of the text
+};
 // A BGZF file as a once-only text descriptor: from compressed offset comp_from (a block start) on, `threads` host threads inflate
 // the blocks, in order, into a pipe; the first `skip` bytes of text are dropped.  read_fd() is an ordinary FASTQ descriptor (owned
 // by the object: it must outlive its reader).  After the reader has met the end of the text, finish() and look at `error`: a bad or
 // incomplete block ends the text early and is named there, with its compressed offset.
 // read_fd() < 0: no pipe could be made (error says so).
-class BgzfTextPipe {
+class BgzfTextPipe : public TextPipe {
 public:
 	BgzfTextPipe(int fd, uint64_t comp_from, uint32_t skip, int threads);
-	~BgzfTextPipe();
+	~BgzfTextPipe() override;
 	BgzfTextPipe(const BgzfTextPipe &) = delete;
 	BgzfTextPipe &operator=(const BgzfTextPipe &) = delete;
-	int read_fd() const;
-	void finish();
-	std::string error;
-	uint64_t comp_bytes = 0, text_bytes = 0;       // valid after finish()
-	double seconds = 0.0;                          // from construction to the end of the text
+	int read_fd() const override;
+	void finish() override;
+	std::string describe(const char *what, bool takeover) const override;
 private:
 	struct Impl;
 	Impl *p;
@@ -76,6 +90,35 @@ private:
 // The blocks from compressed offset comp_from on, inflated on this thread until they hold more than want_text bytes (or the file
 // ends); *comp_next = offset of the block after them.  false: err says which block is bad.
 bool bgzf_inflate_span(int fd, uint64_t comp_from, uint64_t want_text, std::vector<uint8_t> &text, uint64_t *comp_next, std::string &err);
+
+// ---- BAM on the host (bam.cpp; the record parser is ../vg_bam.h, shared with the device kernels) ----
+// The header of the BAM file at fd, from its leading blocks: offset of the first record in the inflated stream, and n_ref.
+// false: err says why (not BAM, a bad block, a file that ends inside the header -- with the inflated offset)
+bool bam_header_info(int fd, uint64_t *header_end, int32_t *n_ref, std::string &err);
+// A BAM file as a once-only descriptor of its equivalent FASTQ text (../vg_bam.h has the conversion): a BgzfTextPipe(fd, comp_from,
+// skip, threads) inflates, a converter thread writes the text into a pipe.  at_header: the inflated bytes start with the BAM header
+// (comp_from = 0, skip = 0); else they start at a record boundary, which is inflated offset stream_from (error messages count from
+// it).  The header's n_ref is not asked for: the conversion follows the block_size chain from a known record boundary and never
+// has to judge whether a record is plausible.
+// After finish(): error names the inflated offset when the stream ends inside the header or a record, or a record's block_size is
+// too small for its fields; the counters say what became of the records.
+class BamTextPipe : public TextPipe {
+public:
+	BamTextPipe(int fd, uint64_t comp_from, uint32_t skip, int threads, bool at_header, uint64_t stream_from);
+	~BamTextPipe() override;
+	BamTextPipe(const BamTextPipe &) = delete;
+	BamTextPipe &operator=(const BamTextPipe &) = delete;
+	int read_fd() const override;
+	void finish() override;
+	std::string describe(const char *what, bool takeover) const override;
+	uint64_t kept = 0, skipped_flag = 0, skipped_empty = 0;
+private:
+	struct Impl;
+	Impl *p;
+};
+// The kept record at inflated offset `within` of the block at compressed offset `block`, as FASTQ text (the device route's
+// take-over primes the host reader's line buffers with the last record framed).  false: err says why
+bool bam_record_text(int fd, uint64_t block, uint32_t within, std::string &text, std::string &err);
 
 // ---- caller + VCF writer (behaviour of reference src/qv.cc:1573-1747, 1789-1848; the arithmetic is ../vg_caller.h) ----
 enum : uint8_t { GT_NONE = 0, GT_HOM_REF = 1, GT_HOM_ALT = 2, GT_HET = 3 };     // numbering of the reference's GTYPE_* (vartype.h)

@@ -13,6 +13,7 @@
 #include "vg_allreduce_plan.h"
 #include "vg_arena.h"
 #include "vg_inflate.h"
+#include "vg_bam.h"
 #include "vg_caller.h"
 
 #include <dlfcn.h>
@@ -730,6 +731,9 @@ struct FqStream {                                    // one per handle, device r
 	unsigned long long last_record;                  // stream offset of the last of them
 	uint32_t carry;                                  // bytes of the previous chunk's text that belong to its unfinished last record
 	uint32_t poisoned;                               // a chunk could not be framed here: it and everything after it is left to the host
+	// BAM streams (vg_fastq_stream_begin_bam): consumed / last_record are offsets in the inflated BAM stream, records counts kept records
+	unsigned long long skipped_flag, skipped_empty;  // records skipped: secondary / supplementary; l_seq == 0
+	unsigned long long repairs;                      // windows whose speculated entry was wrong and that were walked again
 };
 struct FqChunk {                                     // one per batch slot, device resident
 	uint32_t start, len;                             // the chunk's text is buf[start, start + len)
@@ -1032,6 +1036,243 @@ __global__ __launch_bounds__(64) void vg_bgzf_inflate_kernel(const uint8_t *__re
 }
 
 // ------------------------------------------------------------------------------------------------
+// kernels: BAM records framed on the device (vg_bam.h is the record parser; this is its wave policy)
+//
+// A slot's BGZF blocks inflate into bam_raw (BAM_CARRY bytes free in front, like the text buffer); the unfinished record of the
+// slot before is put right before them (vg_bam_prepare), so the slot's data starts at a record boundary -- in the first slot at
+// the header's end.  Finding the records is a chain of block_size fields, serial by nature.  It is cut into FIXED WINDOWS of
+// 64 KiB of the slot's data (VG_BAM_WINDOW; not BGZF blocks, which may hold one byte):
+//   vg_bam_walk_windows   one wave per window.  The lanes test candidate offsets, 64 at a time from the window's start: the guess is the
+//                    smallest one from which three consecutive records are plausible or the chain reaches the end of the data
+//                    (offset 0 of the window is in the first round: files whose records never straddle BGZF blocks hit at once).
+//                    Lane 0 then walks the chain from the guess to the window's end: kept records' offsets, counts, the exit
+//   vg_bam_confirm   in parallel: window k is right iff its guess is window k-1's exit (window 0's entry is exact).  Counts the
+//                    mismatches and finds the first
+//   vg_bam_repair    one wave; returns at once when every window was confirmed.  Else the mismatched windows in order: each is
+//                    walked again from its predecessor's (now final) exit, the new exit is compared with the next guess.  More than
+//                    VG_BAM_MAX_REPAIRS of them refuse the chunk.  By induction from window 0 the result is exact whatever was guessed
+//   vg_bam_lengths   per kept record: its offset into one table (behind a scan of the windows' counts), its length into the offsets
+//                    array for the scan the text route uses too; the windows' verdicts and counts summed
+//   vg_bam_finish    the chunk's verdict, the stream's state for the next slot
+//   vg_bam_gather    one wave per record: bases as ASCII from the nibbles (reverse-complemented where flagged), the gate word
+// Capacities follow from the slot's byte count alone: a record takes at least 37 bytes (records <= bytes / 36), and a read of l
+// bases takes 36 + (l + 1) / 2 + l bytes of its record (bases <= 2/3 of the bytes).
+// A chunk is refused -- the text stream's contract: FqChunk.bad, the stream poisoned, nothing of it or after it framed -- when a
+// record's block_size is below what its fields announce or above VG_BAM_MAX_BLOCK, a read is longer than VG_BAM_MAX_READ bases, or
+// the inflate kernel's bad_key is set.
+// ------------------------------------------------------------------------------------------------
+constexpr uint32_t BAM_CARRY = 1u << 16;             // room in front of a slot's bytes for the unfinished record of the slot before (at most 65 536 bytes)
+
+struct BamWin {                                      // one per window
+	uint32_t guess;                                  // the speculated entry (window 0: the exact one)
+	uint32_t exit, n_kept, n_flag, n_empty, bad;     // VgBamWalk of the walk from the entry in force
+};
+struct BamSlotInfo {                                 // one per slot
+	uint32_t n_mismatch, first_mismatch;             // vg_bam_confirm
+	uint32_t repairs;
+	uint32_t n_flag, n_empty;                        // sums over the windows (vg_bam_lengths)
+	uint32_t bad;                                    // vg_bam_lengths' verdict: a window's walk was bad, or a record beyond the tables.  Not FqChunk.bad,
+	                                                 // which that kernel's blocks read at entry: vg_bam_finish puts the two together
+};
+
+// carried bytes in front of the new ones; start / length of the slot's data (bad_key: see vg_fqs_prepare); first_record: stream offset
+// of the header's end, used by the stream's first slot
+__global__ __launch_bounds__(256) void vg_bam_prepare(FqStream *__restrict__ st, FqChunk *__restrict__ ck, BamSlotInfo *__restrict__ info, const uint8_t *__restrict__ prev_end,
+                                                      uint8_t *__restrict__ buf, uint32_t nbytes, const unsigned long long *__restrict__ bad_key, unsigned long long first_record)
+{
+	uint32_t c = prev_end ? st->carry : 0u;
+	if (c > BAM_CARRY) c = 0;                                               // (never: vg_bam_finish poisons the stream instead)
+	for (uint32_t i = threadIdx.x; i < c; i += 256) buf[BAM_CARRY - c + i] = prev_end[(int64_t)i - (int64_t)c];
+	if (threadIdx.x == 0) {
+		ck->start = BAM_CARRY - c; ck->len = c + nbytes; ck->n_reads = 0; ck->bad = st->poisoned | (bad_key && *bad_key != ~0ull ? 1u : 0u); ck->total = 0;
+		info->n_mismatch = 0; info->first_mismatch = VG_BAM_NONE; info->repairs = 0; info->n_flag = 0; info->n_empty = 0; info->bad = 0;
+		if (!prev_end) st->consumed = first_record;                        // the stream's first slot: nothing is framed before the header's end
+	}
+}
+
+// grid = windows the slot can have (its capacity: the carry's length is known on the device only)
+__global__ __launch_bounds__(64) void vg_bam_walk_windows(const uint8_t *__restrict__ buf, const FqChunk *__restrict__ ck, BamWin *__restrict__ win, uint32_t *__restrict__ woff,
+                                                  int32_t n_ref, uint32_t entry0)
+{
+	const uint32_t k = blockIdx.x, lane = threadIdx.x;
+	const uint32_t len = ck->len;
+	const uint8_t *d = buf + ck->start;
+	const uint64_t w0 = (uint64_t)k * VG_BAM_WINDOW;
+	if (ck->bad || (k > 0 && w0 >= len)) {                                  // a refused chunk; a window behind the data
+		if (lane == 0) { BamWin e; e.guess = VG_BAM_NONE; e.exit = VG_BAM_NONE; e.n_kept = 0; e.n_flag = 0; e.n_empty = 0; e.bad = 0; win[k] = e; }
+		return;
+	}
+	uint32_t guess = VG_BAM_NONE;
+	if (k == 0) guess = entry0 <= len ? entry0 : len;
+	else {
+		// (each round tests 64 offsets; the loop is wave-uniform: it ends for all lanes at the first round with a hit, at the
+		// window's end or at the data's)
+		for (uint32_t base = 0; base < VG_BAM_WINDOW && w0 + base < len; base += 64) {
+			const uint64_t c = w0 + base + lane;
+			const bool hit = c < len && vg_bam_chain(d, len, c, n_ref);
+			const uint64_t m = __ballot(hit);
+			if (m) { guess = (uint32_t)(w0 + base) + (uint32_t)__ffsll((long long)m) - 1u; break; }
+		}
+	}
+	if (lane == 0) {
+		BamWin e;
+		e.guess = guess;
+		if (guess == VG_BAM_NONE) { e.exit = VG_BAM_NONE; e.n_kept = 0; e.n_flag = 0; e.n_empty = 0; e.bad = 0; }
+		else {
+			VgBamWalk w;
+			vg_bam_walk(d, len, guess, w0 + VG_BAM_WINDOW, woff + (uint64_t)k * VG_BAM_WIN_RECS, VG_BAM_WIN_RECS, &w);
+			e.exit = w.exit; e.n_kept = w.n_kept; e.n_flag = w.n_flag; e.n_empty = w.n_empty; e.bad = w.bad;
+		}
+		win[k] = e;
+	}
+}
+
+// the windows of the slot's data: ceil(len / window), at least one
+__device__ __forceinline__ uint32_t bam_windows(uint32_t len) { return len ? (uint32_t)(((uint64_t)len + VG_BAM_WINDOW - 1) / VG_BAM_WINDOW) : 1u; }
+
+__global__ __launch_bounds__(256) void vg_bam_confirm(const FqChunk *__restrict__ ck, const BamWin *__restrict__ win, BamSlotInfo *__restrict__ info)
+{
+	if (ck->bad) return;
+	const uint32_t n_win = bam_windows(ck->len);
+	const uint32_t k = blockIdx.x * 256 + threadIdx.x;
+	const bool miss = k >= 1 && k < n_win && (win[k].guess != win[k - 1].exit || win[k].guess == VG_BAM_NONE);
+	const uint64_t m = __ballot(miss);
+	if (m && (threadIdx.x & 63) == 0) {
+		atomicAdd(&info->n_mismatch, (uint32_t)__popcll(m));
+		atomicMin(&info->first_mismatch, k + (uint32_t)__ffsll((long long)m) - 1u);
+	}
+}
+
+__global__ __launch_bounds__(64) void vg_bam_repair(const uint8_t *__restrict__ buf, FqChunk *__restrict__ ck, BamWin *__restrict__ win, uint32_t *__restrict__ woff, BamSlotInfo *__restrict__ info)
+{
+	if (ck->bad || info->n_mismatch == 0) return;                           // every window confirmed: nothing serial happens
+	const uint32_t lane = threadIdx.x;
+	const uint32_t len = ck->len, n_win = bam_windows(len);
+	const uint8_t *d = buf + ck->start;
+	uint32_t k = info->first_mismatch, repairs = 0;
+	bool refuse = false;
+	while (k < n_win) {                                                     // (k grows with every round)
+		if (repairs == VG_BAM_MAX_REPAIRS) { refuse = true; break; }
+		// window k - 1 is final: walk k again from its exit
+		uint32_t next_guess_ok = 1;
+		if (lane == 0) {
+			const BamWin pv = win[k - 1];
+			BamWin e = win[k];
+			if (pv.bad) e.bad = 1;                                           // (the chunk is refused below)
+			else {
+				VgBamWalk w;
+				w.exit = pv.exit; w.n_kept = 0; w.n_flag = 0; w.n_empty = 0; w.bad = 0;
+				if (pv.exit != VG_BAM_NONE) vg_bam_walk(d, len, pv.exit, (uint64_t)(k + 1) * VG_BAM_WINDOW, woff + (uint64_t)k * VG_BAM_WIN_RECS, VG_BAM_WIN_RECS, &w);
+				else w.bad = 1;
+				e.exit = w.exit; e.n_kept = w.n_kept; e.n_flag = w.n_flag; e.n_empty = w.n_empty; e.bad = w.bad;
+			}
+			win[k] = e;
+			if (e.bad) next_guess_ok = 2;
+			else if (k + 1 < n_win) next_guess_ok = win[k + 1].guess == e.exit && e.exit != VG_BAM_NONE ? 1u : 0u;
+		}
+		repairs++;
+		next_guess_ok = (uint32_t)__builtin_amdgcn_readfirstlane((int)next_guess_ok);
+		if (next_guess_ok == 2) { refuse = true; break; }
+		if (next_guess_ok == 0) { k++; continue; }
+		// the next window whose guess is not its predecessor's exit (exits behind k + 1 have not changed), 64 windows per round
+		uint32_t j = k + 2, found = VG_BAM_NONE;
+		for (; j < n_win; j += 64) {
+			const uint32_t q = j + lane;
+			const bool miss = q < n_win && (win[q].guess != win[q - 1].exit || win[q].guess == VG_BAM_NONE);
+			const uint64_t m = __ballot(miss);
+			if (m) { found = j + (uint32_t)__ffsll((long long)m) - 1u; break; }
+		}
+		k = found;                                                           // VG_BAM_NONE: none is left
+	}
+	if (lane == 0) { info->repairs = repairs; if (refuse) ck->bad = 1u; }
+}
+
+// the windows' kept-record counts as an array for the scan (cnt[n_win_cap] = 0: the scan's last entry is the total)
+__global__ __launch_bounds__(256) void vg_bam_counts(const FqChunk *__restrict__ ck, const BamWin *__restrict__ win, uint32_t n_win_cap, uint32_t *__restrict__ cnt)
+{
+	const uint32_t k = blockIdx.x * 256 + threadIdx.x;
+	if (k <= n_win_cap) cnt[k] = k < n_win_cap && !ck->bad && k < bam_windows(ck->len) ? win[k].n_kept : 0u;
+}
+
+// per window (one wave each): its kept records' offsets and lengths into the slot's tables, at the window's place in the scan of
+// the counts; the windows' verdicts (into info->bad); rlen behind the last record is zero (the scan that follows runs over the whole capacity)
+__global__ __launch_bounds__(256) void vg_bam_lengths(const uint8_t *__restrict__ buf, const FqChunk *__restrict__ ck, const BamWin *__restrict__ win, const uint32_t *__restrict__ woff,
+                                                      const uint32_t *__restrict__ rec_base, uint32_t n_win_cap, BamSlotInfo *__restrict__ info,
+                                                      uint32_t *__restrict__ rec_off, uint64_t *__restrict__ rlen, uint32_t cap_rec)
+{
+	const bool chunk_bad = ck->bad != 0;
+	const uint32_t len = ck->len, n_win = bam_windows(len);
+	const uint8_t *d = buf + ck->start;
+	const uint32_t total = chunk_bad ? 0u : min(rec_base[n_win_cap], cap_rec);
+	const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, n_t = (uint64_t)gridDim.x * blockDim.x;
+	for (uint64_t r = total + t; r <= cap_rec; r += n_t) rlen[r] = 0;
+	if (chunk_bad) return;
+	// one wave per window: the lanes share its records
+	const uint32_t lane = threadIdx.x & 63;
+	for (uint64_t k = t >> 6; k < n_win; k += n_t >> 6) {
+		const BamWin e = win[k];
+		if (lane == 0) {
+			if (e.bad) info->bad = 1u;
+			if (e.n_flag) atomicAdd(&info->n_flag, e.n_flag);
+			if (e.n_empty) atomicAdd(&info->n_empty, e.n_empty);
+		}
+		const uint32_t b = rec_base[k];
+		for (uint32_t i = lane; i < e.n_kept; i += 64) {
+			const uint32_t off = woff[k * VG_BAM_WIN_RECS + i];
+			VgBamRec rec;
+			const uint32_t l = vg_bam_view(d, len, off, &rec) == VG_BAM_OK ? rec.l_seq : 0u;
+			if (b + i < cap_rec) { rec_off[b + i] = off; rlen[b + i] = l; } else info->bad = 1u;
+		}
+	}
+}
+
+// after the offsets scan: the chunk's verdict, and the stream's state for the next slot.  text_off: offset in the inflated BAM
+// stream of the slot's first new byte (buf[BAM_CARRY])
+__global__ void vg_bam_finish(FqStream *__restrict__ st, FqChunk *__restrict__ ck, const BamWin *__restrict__ win, const BamSlotInfo *__restrict__ info, const uint32_t *__restrict__ rec_base,
+                              uint32_t n_win_cap, const uint32_t *__restrict__ rec_off, const uint64_t *__restrict__ offsets, uint32_t cap_rec, unsigned long long text_off)
+{
+	if (threadIdx.x != 0 || blockIdx.x != 0) return;
+	if (st->poisoned || ck->bad || info->bad) { st->poisoned = 1u; ck->bad = 1u; ck->n_reads = 0; ck->total = 0; return; }
+	const uint32_t n_win = bam_windows(ck->len);
+	const uint32_t end = win[n_win - 1].exit;                                // first byte not framed, relative to the data's start: a record boundary
+	const uint32_t n_rec = rec_base[n_win_cap];
+	if (end == VG_BAM_NONE || end > ck->len || ck->len - end > BAM_CARRY || n_rec > cap_rec) { st->poisoned = 1u; ck->bad = 1u; return; }
+	const long long data0 = (long long)text_off - (long long)(BAM_CARRY - ck->start);   // stream offset of the data's first byte (the carried bytes' own)
+	if (n_rec) st->last_record = (unsigned long long)(data0 + rec_off[n_rec - 1]);
+	st->consumed = (unsigned long long)(data0 + end);
+	st->records += n_rec;
+	st->skipped_flag += info->n_flag; st->skipped_empty += info->n_empty; st->repairs += info->repairs;
+	st->carry = ck->len - end;
+	ck->n_reads = n_rec;
+	ck->total = offsets[n_rec];
+}
+
+// one wave per record: the bases as ASCII from the nibbles, the gate word from the qualities
+__global__ __launch_bounds__(256) void vg_bam_gather(const uint8_t *__restrict__ buf, const uint32_t *__restrict__ rec_off, const uint64_t *__restrict__ offsets,
+                                                     const FqChunk *__restrict__ ck, uint8_t *__restrict__ bases, uint32_t *__restrict__ gate)
+{
+	const uint64_t n_rec = ck->n_reads;
+	const uint32_t len = ck->len;
+	const uint8_t *d = buf + ck->start;
+	const uint32_t lane = threadIdx.x & 63;
+	const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+	for (uint64_t r = wave; r < n_rec; r += n_waves) {
+		const uint64_t o = offsets[r];
+		const uint32_t off = rec_off[r];
+		VgBamRec rec = {};
+		// (the walk framed this record: its bytes are inside the data; the checks keep a lane from reading outside them all the same)
+		const bool ok = vg_bam_view(d, len, off, &rec) == VG_BAM_OK && rec.l_seq == offsets[r + 1] - o && rec.min_block() <= rec.block_size && (uint64_t)len - off >= 4ull + rec.block_size;
+		const uint32_t l = ok ? rec.l_seq : 0u;
+		const uint64_t so = rec.seq_off(off), qo = rec.qual_off(off);
+		const bool rev = rec.reversed();
+		for (uint32_t j = lane; j < l; j += 64) bases[o + j] = vg_bam_base(d, so, l, rev, j);
+		const bool open = ok && vg_bam_gate_bit(d, qo, l, rev, lane);
+		const uint64_t m = __ballot(open);
+		if (lane == 0) gate[r] = (uint32_t)m;
+	}
+}
+
+// ------------------------------------------------------------------------------------------------
 // host side of the handle
 // ------------------------------------------------------------------------------------------------
 static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -1146,6 +1387,10 @@ struct Slot {
 	DevBuf<FqChunk> fq_chunk;                                         // this chunk's framing results (one FqChunk), device resident
 	uint64_t fq_text_len = 0;                                        // bytes of text copied into fq_text (after the FQ_CARRY gap)
 	DevBuf<uint8_t> bz_comp; DevBuf<vg_bgzf_block> bz_tab; DevBuf<uint32_t> bz_status;   // a BGZF chunk: compressed bytes, block table, per-block results
+	// a BAM chunk: the inflated bytes (BAM_CARRY free in front), per window its result and its kept records' offsets, the counts'
+	// scan, the records' offsets in one table, the slot's sums
+	DevBuf<uint8_t> bam_raw; DevBuf<BamWin> bam_win; DevBuf<uint32_t> bam_woff, bam_cnt, bam_rec; DevBuf<BamSlotInfo> bam_info;
+	uint64_t bam_raw_len = 0;                                        // bytes inflated into bam_raw (after the BAM_CARRY gap)
 	SlotEvent e_in;                                                  // the batch's buffers are complete (when another stream produced them)
 	SlotEvent e_fq; bool fq_tail_wanted = false;                     // the NEXT chunk's prepare kernel reads this text's tail: recorded after it
 	// the batch's timeline (harvest reads the times between them): the pack kernel on its stream; the wave kernel (main tier) on the main
@@ -1174,6 +1419,11 @@ struct BgzfStream {
 	uint64_t slot_text = 0;                                       // most text one slot takes: a longer push is split at block boundaries
 	bool header_bad = false;                                      // a push met bytes that are no BGZF block: the stream is over
 	std::vector<vg_bgzf_block> blocks, tab;                       // scratch of a push
+	// a BAM stream (vg_fastq_stream_begin_bam): the leading blocks are inflated here until the header parses
+	bool bam = false, bam_hdr_done = false, bam_not_bam = false;
+	std::vector<uint8_t> bam_hdr;                                 // inflated bytes of the leading blocks, while the header is incomplete
+	uint64_t bam_hdr_end = 0;                                     // offset of the first record in the inflated stream
+	int32_t bam_n_ref = 0;
 };
 
 struct vg_index {
@@ -3109,6 +3359,7 @@ extern "C" int vg_fastq_stream_begin_bgzf(vg_index *ix)
 		HIP_TRY(hipMemsetAsync(bz.d_key, 0xff, sizeof *bz.d_key, ix->ingest_or_main()));
 		bz.carry.clear(); bz.index.clear();
 		bz.comp_pos = 0; bz.text_pos = 0; bz.host_key = ~0ull; bz.header_bad = false;
+		bz.bam = false; bz.bam_hdr_done = false; bz.bam_not_bam = false; bz.bam_hdr.clear(); bz.bam_hdr_end = 0; bz.bam_n_ref = 0;
 		bz.slot_text = BZ_SLOT_TEXT_MAX;
 		if (const char *e = getenv("VG_BGZF_SLOT_TEXT")) bz.slot_text = std::min<uint64_t>(BZ_SLOT_TEXT_MAX, std::max<uint64_t>(VG_BGZF_MAX_ISIZE, strtoull(e, nullptr, 10)));   // (tests: the split path with small inputs)
 		ix->fq_bgzf = true;
@@ -3118,6 +3369,8 @@ extern "C" int vg_fastq_stream_begin_bgzf(vg_index *ix)
 
 // blocks [i0, i1) of a push (bz.blocks; their bytes are in p, in_off relative to it) -> one slot: copy the compressed bytes and the
 // table up, inflate into the slot's text, frame
+static int bam_slot_frame(vg_index *ix, Slot &sl, int slot_no, uint64_t text_n, uint64_t text_off);
+static int bam_reserve(Slot &sl, uint64_t nbytes);
 static int bgzf_slot(vg_index *ix, const uint8_t *p, size_t i0, size_t i1, uint64_t text_n)
 {
 	BgzfStream &bz = ix->bz;
@@ -3140,14 +3393,15 @@ static int bgzf_slot(vg_index *ix, const uint8_t *p, size_t i0, size_t i1, uint6
 	int rc = acquire_slot(ix, &slp, ix->fq_sample);
 	if (rc) return rc;
 	Slot &sl = *slp;
-	if ((rc = fq_reserve(sl, text_n))) return rc;
+	if ((rc = bz.bam ? bam_reserve(sl, text_n) : fq_reserve(sl, text_n))) return rc;
 	if ((rc = sl.bz_comp.reserve(c1 - c0 + 64, "BGZF bytes"))) return rc;   // (the kernel loads whole aligned 16-byte vectors around a payload)
 	if ((rc = sl.bz_tab.reserve(bz.tab.size(), "BGZF block table"))) return rc;
 	if ((rc = sl.bz_status.reserve(bz.tab.size(), "BGZF block results"))) return rc;
 	HIP_TRY(hipMemcpy(sl.bz_comp.p, p + c0, c1 - c0, hipMemcpyHostToDevice));
 	HIP_TRY(hipMemcpy(sl.bz_tab.p, bz.tab.data(), bz.tab.size() * sizeof(vg_bgzf_block), hipMemcpyHostToDevice));
-	vg_bgzf_inflate_kernel<<<(unsigned)bz.tab.size(), 64, 0, ix->ingest_or_main()>>>(sl.bz_comp.p, sl.bz_tab.p, (uint32_t)bz.tab.size(), sl.fq_text.p + FQ_CARRY, sl.bz_status.p, bz.d_key);
+	vg_bgzf_inflate_kernel<<<(unsigned)bz.tab.size(), 64, 0, ix->ingest_or_main()>>>(sl.bz_comp.p, sl.bz_tab.p, (uint32_t)bz.tab.size(), bz.bam ? sl.bam_raw.p + BAM_CARRY : sl.fq_text.p + FQ_CARRY, sl.bz_status.p, bz.d_key);
 	HIP_TRY(hipGetLastError());
+	if (bz.bam) return bam_slot_frame(ix, sl, slot_no, text_n, first.text_off);
 	return fq_frame_and_launch(ix, sl, slot_no, text_n, bz.d_key);
 }
 
@@ -3161,7 +3415,29 @@ static int push_bgzf(vg_index *ix, const uint8_t *data, uint64_t nbytes)
 	bz.blocks.clear();
 	uint64_t tail = 0, bad_off = 0;
 	const int hdr_rc = vg_bgzf_scan(p, len, bz.comp_pos, bz.text_pos, bz.blocks, &tail, &bad_off);
-	for (size_t i0 = 0; i0 < bz.blocks.size();) {                     // slots of at most slot_text bytes of text, cut at block boundaries
+	size_t first_send = 0;
+	if (bz.bam && !bz.bam_hdr_done) {
+		// the leading blocks are inflated here until the BAM header parses; blocks wholly inside it never go to the device
+		first_send = bz.blocks.size();
+		for (size_t i = 0; i < bz.blocks.size() && bz.host_key == ~0ull; i++) {
+			const vg_bgzf_block &b = bz.blocks[i];
+			const size_t o = bz.bam_hdr.size();
+			bz.bam_hdr.resize(o + b.isize + 1);
+			const int brc = vg_inflate_block_host(p + b.in_off, b.in_len, bz.bam_hdr.data() + o, b.isize, b.crc);
+			bz.bam_hdr.resize(o + b.isize);
+			if (brc) { bz.host_key = std::min(bz.host_key, (unsigned long long)b.comp_off << 4 | (unsigned)brc); break; }   // (vg_fastq_stream_end names it; nothing behind it is framed)
+			const int rc = vg_bam_header(bz.bam_hdr.data(), bz.bam_hdr.size(), &bz.bam_hdr_end, &bz.bam_n_ref);
+			if (rc == VG_BAM_BAD) { bz.bam_not_bam = true; bz.header_bad = true; return fail(VG_EIO, "the BGZF stream does not hold BAM: its inflated bytes do not start with the magic BAM\\1 and a header"); }
+			if (rc == VG_BAM_OK) {
+				bz.bam_hdr_done = true;
+				first_send = bz.bam_hdr_end < b.text_off + b.isize ? i : i + 1;
+				std::vector<uint8_t>().swap(bz.bam_hdr);
+				break;
+			}
+		}
+	}
+	if (bz.bam && bz.host_key != ~0ull) first_send = bz.blocks.size();   // a bad block among those checked here: the stream is over
+	for (size_t i0 = first_send; i0 < bz.blocks.size();) {            // slots of at most slot_text bytes of text, cut at block boundaries
 		size_t i1 = i0;
 		uint64_t text_n = 0;
 		while (i1 < bz.blocks.size() && (i1 == i0 || text_n + bz.blocks[i1].isize <= bz.slot_text)) text_n += bz.blocks[i1++].isize;
@@ -3297,7 +3573,260 @@ extern "C" int vg_bgzf_inflate_device(int device, const uint8_t *bgzf, uint64_t 
 	});
 }
 
-static int fq_collect(vg_index *ix, bool drain, uint64_t *n_records, uint64_t *consumed, uint64_t *last_record_start, int *refused)
+// ---- BAM streams: BGZF pushes as above; the blocks inflate into the slot's bam_raw and the records are framed there (vg_bam_*)
+extern "C" int vg_fastq_stream_begin_bam(vg_index *ix)
+{
+	const int rc = vg_fastq_stream_begin_bgzf(ix);
+	if (rc == VG_OK) ix->bz.bam = true;
+	return rc;
+}
+
+// What the framing of `nbytes` inflated bytes needs: capacities follow from the byte count alone -- a record takes at least 37 bytes
+// (records <= bytes / 36; + one per window for a refused chunk's speculation), and l bases take at least 3/2 l bytes of their record
+// (bases <= 2/3 of the bytes)
+struct BamCaps {
+	uint64_t span, n_win, cap_rec, cap_bases, tmp_bytes;
+	explicit BamCaps(uint64_t nbytes)
+	{
+		span = (uint64_t)BAM_CARRY + nbytes;
+		n_win = (span + VG_BAM_WINDOW - 1) / VG_BAM_WINDOW;
+		cap_rec = span / 36 + n_win + 2;
+		cap_bases = span / 3 * 2 + 64;
+		tmp_bytes = vg_dev_scan_temp_bytes(n_win + 1, cap_rec + 1);
+	}
+};
+struct BamFrame {                                    // the buffers of one framing, all on the device
+	uint8_t *raw; FqStream *st; FqChunk *ck; BamSlotInfo *info; BamWin *win; uint32_t *woff, *cnt, *rec; uint64_t *offsets; uint8_t *bases; uint32_t *gate; void *tmp;
+};
+
+// The framing sequence behind vg_bam_prepare, enqueued on `is`
+static int bam_frame_enqueue(hipStream_t is, int cus, const BamFrame &f, const BamCaps &c, int32_t n_ref, uint32_t entry0, uint64_t text_off)
+{
+	const unsigned nw = (unsigned)c.n_win;
+	vg_bam_walk_windows<<<nw, 64, 0, is>>>(f.raw, f.ck, f.win, f.woff, n_ref, entry0);
+	vg_bam_confirm<<<(nw + 255) / 256, 256, 0, is>>>(f.ck, f.win, f.info);
+	vg_bam_repair<<<1, 64, 0, is>>>(f.raw, f.ck, f.win, f.woff, f.info);
+	vg_bam_counts<<<(nw + 1 + 255) / 256, 256, 0, is>>>(f.ck, f.win, nw, f.cnt);
+	HIP_TRY(hipGetLastError());
+	int se = vg_dev_exclusive_scan_u32(f.cnt, f.cnt, c.n_win + 1, is, f.tmp, c.tmp_bytes);
+	if (se != 0) return fail(VG_ENODEV, "device scan failed: %s", hipGetErrorString((hipError_t)se));
+	const unsigned lg = (unsigned)std::min<uint64_t>(std::max<uint64_t>((c.n_win + 3) / 4, 64), (uint64_t)cus * 16);
+	vg_bam_lengths<<<lg, 256, 0, is>>>(f.raw, f.ck, f.win, f.woff, f.cnt, nw, f.info, f.rec, f.offsets, (uint32_t)c.cap_rec);
+	HIP_TRY(hipGetLastError());
+	se = vg_dev_exclusive_scan_u64(f.offsets, f.offsets, c.cap_rec + 1, is, f.tmp, c.tmp_bytes);
+	if (se != 0) return fail(VG_ENODEV, "device scan failed: %s", hipGetErrorString((hipError_t)se));
+	vg_bam_finish<<<1, 1, 0, is>>>(f.st, f.ck, f.win, f.info, f.cnt, nw, f.rec, f.offsets, (uint32_t)c.cap_rec, (unsigned long long)text_off);
+	vg_bam_gather<<<(unsigned)std::min<uint64_t>((c.cap_rec + 3) / 4, (uint64_t)cus * 32), 256, 0, is>>>(f.raw, f.rec, f.offsets, f.ck, f.bases, f.gate);
+	HIP_TRY(hipGetLastError());
+	return VG_OK;
+}
+
+static int bam_reserve(Slot &sl, uint64_t nbytes)
+{
+	int rc;
+	const BamCaps c(nbytes);
+	// (the slot after this one's last chunk copied the tail of its bytes on the ingest stream: see fq_reserve)
+	if (sl.fq_tail_wanted) { HIP_TRY(hipEventSynchronize(sl.e_fq)); sl.fq_tail_wanted = false; }
+	if ((rc = sl.bam_raw.reserve(c.span + 64, "BAM bytes"))) return rc;
+	if ((rc = sl.bam_win.reserve(c.n_win + 1, "BAM windows"))) return rc;
+	if ((rc = sl.bam_woff.reserve(c.n_win * VG_BAM_WIN_RECS, "BAM window records"))) return rc;
+	if ((rc = sl.bam_cnt.reserve(c.n_win + 2, "BAM window counts"))) return rc;
+	if ((rc = sl.bam_rec.reserve(c.cap_rec + 2, "BAM record offsets"))) return rc;
+	if ((rc = sl.bam_info.reserve(1, "BAM slot sums"))) return rc;
+	if ((rc = sl.fq_chunk.reserve(1, "FASTQ chunk"))) return rc;
+	if ((rc = sl.st_offsets.reserve(c.cap_rec + 2, "read offsets"))) return rc;
+	if ((rc = sl.st_bases.reserve(c.cap_bases, "base text"))) return rc;
+	if ((rc = sl.st_gate.reserve(c.cap_rec + 2, "gate words"))) return rc;
+	if ((rc = sl.fq_tmp.reserve(c.tmp_bytes, "scan scratch"))) return rc;
+	return VG_OK;
+}
+
+// One slot of a BAM stream whose text_n bytes are being inflated into sl.bam_raw.p + BAM_CARRY (text_off: their offset in the
+// inflated stream): carry, framing, and the read loop behind them exactly as fq_frame_and_launch starts it
+static int bam_slot_frame(vg_index *ix, Slot &sl, int slot_no, uint64_t text_n, uint64_t text_off)
+{
+	BgzfStream &bz = ix->bz;
+	hipStream_t is = ix->ingest_or_main();
+	const BamCaps c(text_n);
+	sl.bam_raw_len = text_n;
+	const uint8_t *prev_end = nullptr;
+	uint32_t entry0 = 0;
+	if (ix->fq_prev_slot >= 0) { const Slot &pv = ix->slot[ix->fq_prev_slot]; prev_end = pv.bam_raw.p + BAM_CARRY + pv.bam_raw_len; }
+	else entry0 = (uint32_t)(bz.bam_hdr_end > text_off ? bz.bam_hdr_end - text_off : 0);      // the first slot: its first block holds the header's end
+	vg_bam_prepare<<<1, 256, 0, is>>>(ix->d_fq, sl.fq_chunk.p, sl.bam_info.p, prev_end, sl.bam_raw.p, (uint32_t)text_n, bz.d_key, (unsigned long long)(text_off + entry0));
+	if (ix->fq_prev_slot >= 0) { Slot &pv = ix->slot[ix->fq_prev_slot]; HIP_TRY(hipEventRecord(pv.e_fq, is)); pv.fq_tail_wanted = true; }
+	const BamFrame f{sl.bam_raw.p, ix->d_fq, sl.fq_chunk.p, sl.bam_info.p, sl.bam_win.p, sl.bam_woff.p, sl.bam_cnt.p, sl.bam_rec.p, sl.st_offsets.p, sl.st_bases.p, sl.st_gate.p, sl.fq_tmp.p};
+	const int rc = bam_frame_enqueue(is, ix->cus, f, c, bz.bam_n_ref, entry0, text_off);
+	if (rc) return rc;
+	ix->fq_prev_slot = slot_no;
+	return launch_batch(ix, sl, sl.st_bases.p, nullptr, sl.st_offsets.p, c.cap_rec, is, &sl.fq_chunk.p->n_reads, c.cap_bases, sl.st_gate.p);
+}
+
+extern "C" int vg_bam_stream_stats(vg_index *ix, uint64_t *kept, uint64_t *skipped_flag, uint64_t *skipped_empty, uint64_t *repairs)
+{
+	if (!ix) return fail(VG_EINVAL, "null argument");
+	HIP_TRY(hipSetDevice(ix->device));
+	HIP_TRY(hipStreamSynchronize(ix->ingest_or_main()));
+	FqStream h;
+	HIP_TRY(hipMemcpy(&h, ix->d_fq, sizeof h, hipMemcpyDeviceToHost));
+	if (kept) *kept = h.records;
+	if (skipped_flag) *skipped_flag = h.skipped_flag;
+	if (skipped_empty) *skipped_empty = h.skipped_empty;
+	if (repairs) *repairs = h.repairs;
+	return VG_OK;
+}
+
+// ---- BAM without a handle: a whole file in host memory
+// the whole blocks of a buffer inflated on the host, and the BAM header in front of them parsed.  VG_OK: *hdr_rc is vg_bam_header's
+// verdict on what was inflated; a bad block ends the text early (*bad_block: its compressed offset, UINT64_MAX: none)
+static int bam_inflate_host(const uint8_t *bgzf, uint64_t nbytes, std::vector<vg_bgzf_block> &bl, std::vector<uint8_t> &raw, uint64_t *bad_block, std::string &why)
+{
+	uint64_t tail = 0, bad = UINT64_MAX;
+	*bad_block = UINT64_MAX;
+	const int scan_rc = vg_bgzf_scan(bgzf, nbytes, 0, 0, bl, &tail, &bad);
+	raw.resize(bl.empty() ? 1 : (size_t)(bl.back().text_off + bl.back().isize) + 1);
+	uint64_t n = 0;
+	for (const vg_bgzf_block &b : bl) {
+		const int brc = vg_inflate_block_host(bgzf + b.in_off, b.in_len, raw.data() + b.text_off, b.isize, b.crc);
+		if (brc) { *bad_block = b.comp_off; why = bz_describe((unsigned long long)b.comp_off << 4 | (unsigned)brc); break; }
+		n = b.text_off + b.isize;
+	}
+	raw.resize((size_t)n);
+	if (*bad_block == UINT64_MAX && scan_rc) { *bad_block = bad; why = "BGZF block at compressed offset " + std::to_string(bad) + ": not a BGZF block header"; }
+	else if (*bad_block == UINT64_MAX && tail) { *bad_block = nbytes - tail; why = "BGZF block at compressed offset " + std::to_string(nbytes - tail) + ": incomplete"; }
+	return VG_OK;
+}
+static int bam_not_bam(const uint8_t *bgzf, uint64_t nbytes)
+{
+	if (nbytes >= 4 && !memcmp(bgzf, "CRAM", 4)) return fail(VG_EIO, "this is a CRAM file, not BAM: CRAM is not read here -- convert it, e.g. with samtools fastq through a FIFO");
+	return fail(VG_EIO, "not a BAM file: the inflated bytes do not start with the magic BAM\\1 and a header");
+}
+
+extern "C" int vg_bam_to_fastq_host(const uint8_t *bgzf, uint64_t nbytes, uint8_t *text, uint64_t text_cap, uint64_t *text_len, uint64_t *n_records, uint64_t *bad_offset)
+{
+	if ((!bgzf && nbytes) || (!text && text_cap) || !text_len || !n_records || !bad_offset) return fail(VG_EINVAL, "null argument");
+	if (nbytes >= (1ull << 32)) return fail(VG_EINVAL, "BAM buffer of 4 GiB or more");
+	*text_len = 0; *n_records = 0; *bad_offset = UINT64_MAX;
+	return guarded([&]() -> int {
+		std::vector<vg_bgzf_block> bl;
+		std::vector<uint8_t> raw;
+		uint64_t bad_block = UINT64_MAX, hdr_end = 0, used = 0;
+		std::string why, out;
+		int32_t n_ref = 0;
+		(void)bam_inflate_host(bgzf, nbytes, bl, raw, &bad_block, why);
+		const int hrc = vg_bam_header(raw.data(), raw.size(), &hdr_end, &n_ref);
+		if (hrc == VG_BAM_BAD || (raw.empty() && bl.empty())) return bam_not_bam(bgzf, nbytes);
+		if (hrc == VG_BAM_MORE) {
+			*bad_offset = raw.size();
+			(void)fail(VG_EIO, "the BAM stream ends inside its header, at inflated offset %s%s", std::to_string(raw.size()).c_str(), why.empty() ? "" : (" (" + why + ")").c_str());
+			return VG_OK;
+		}
+		VgBamCounts n;
+		const int crc = vg_bam_convert(raw.data(), raw.size(), hdr_end, out, &used, n);
+		if (out.size() > text_cap) return fail(VG_ETOOBIG, "the FASTQ text of the BAM records does not fit the caller's buffer");
+		if (!out.empty()) memcpy(text, out.data(), out.size());
+		*text_len = out.size(); *n_records = n.kept;
+		if (crc == VG_BAM_BAD) { *bad_offset = used; (void)fail(VG_EIO, "BAM record at inflated offset %s: its block_size is smaller than its own fields announce", std::to_string(used).c_str()); }
+		else if (used < raw.size() || bad_block != UINT64_MAX) {
+			*bad_offset = used;
+			(void)fail(VG_EIO, "the BAM stream ends inside a record, at inflated offset %s%s", std::to_string(used).c_str(), why.empty() ? "" : (" (" + why + ")").c_str());
+		}
+		return VG_OK;
+	});
+}
+
+extern "C" int vg_bam_frame_device(int device, const uint8_t *bgzf, uint64_t nbytes, uint64_t *offsets, uint64_t cap_rec, uint8_t *bases, uint64_t cap_bases, uint32_t *gate,
+                                   uint64_t *n_records, uint64_t stats[4], uint64_t *bad_offset)
+{
+	if ((!bgzf && nbytes) || !offsets || (!bases && cap_bases) || (!gate && cap_rec) || !n_records || !stats || !bad_offset) return fail(VG_EINVAL, "null argument");
+	if (nbytes >= (1ull << 31)) return fail(VG_EINVAL, "BAM buffer of 2 GiB or more");
+	*n_records = 0; *bad_offset = UINT64_MAX; offsets[0] = 0;
+	for (int i = 0; i < 4; i++) stats[i] = 0;
+	return guarded([&]() -> int {
+		// the header on the host, as the stream does it: the leading blocks only
+		std::vector<vg_bgzf_block> bl;
+		uint64_t tail = 0, bad = UINT64_MAX, hdr_end = 0;
+		const int scan_rc = vg_bgzf_scan(bgzf, nbytes, 0, 0, bl, &tail, &bad);
+		std::vector<uint8_t> hdr;
+		int32_t n_ref = 0;
+		int hrc = VG_BAM_MORE;
+		size_t first = bl.size();
+		for (size_t i = 0; i < bl.size() && hrc == VG_BAM_MORE; i++) {
+			const vg_bgzf_block &b = bl[i];
+			const size_t o = hdr.size();
+			hdr.resize(o + b.isize + 1);
+			const int brc = vg_inflate_block_host(bgzf + b.in_off, b.in_len, hdr.data() + o, b.isize, b.crc);
+			hdr.resize(o + b.isize);
+			if (brc) { *bad_offset = o; return fail(VG_EIO, "%s", bz_describe((unsigned long long)b.comp_off << 4 | (unsigned)brc).c_str()); }
+			hrc = vg_bam_header(hdr.data(), hdr.size(), &hdr_end, &n_ref);
+			if (hrc == VG_BAM_OK) first = hdr_end < b.text_off + b.isize ? i : i + 1;
+		}
+		if (hrc == VG_BAM_BAD || bl.empty()) return bam_not_bam(bgzf, nbytes);
+		if (hrc == VG_BAM_MORE) { *bad_offset = hdr.size(); (void)fail(VG_EIO, "the BAM stream ends inside its header, at inflated offset %s", std::to_string(hdr.size()).c_str()); return VG_OK; }
+		const uint64_t text_end = bl.back().text_off + bl.back().isize;
+		if (first == bl.size() || text_end == bl[first].text_off) {           // a header and no records
+			if (scan_rc || tail) { *bad_offset = hdr_end; (void)fail(VG_EIO, "BGZF block at compressed offset %s: incomplete or not a BGZF block", std::to_string(scan_rc ? bad : nbytes - tail).c_str()); }
+			return VG_OK;
+		}
+		const uint64_t text_off = bl[first].text_off, text_n = text_end - text_off;
+		const uint64_t c0 = bl[first].comp_off, comp_n = (uint64_t)bl.back().in_off + bl.back().in_len + 8 - c0;
+		std::vector<vg_bgzf_block> tab(bl.begin() + (long)first, bl.end());
+		for (vg_bgzf_block &b : tab) { b.in_off -= (uint32_t)c0; b.text_off -= text_off; }
+		const BamCaps c(text_n);
+		HIP_TRY(hipSetDevice(device));
+		hipDeviceProp_t prop;
+		HIP_TRY(hipGetDeviceProperties(&prop, device));
+		int rc;
+		DevBuf<uint8_t> d_comp, d_raw, d_bases, d_tmp; DevBuf<vg_bgzf_block> d_tab; DevBuf<uint32_t> d_status, d_woff, d_cnt, d_rec, d_gate; DevBuf<unsigned long long> d_key;
+		DevBuf<FqStream> d_st; DevBuf<FqChunk> d_ck; DevBuf<BamSlotInfo> d_info; DevBuf<BamWin> d_win; DevBuf<uint64_t> d_off;
+		if ((rc = d_comp.reserve(comp_n + 64, "BGZF bytes")) || (rc = d_raw.reserve(c.span + 64, "BAM bytes")) || (rc = d_tab.reserve(tab.size(), "BGZF block table"))
+		    || (rc = d_status.reserve(tab.size(), "BGZF block results")) || (rc = d_key.reserve(1, "BGZF verdict")) || (rc = d_st.reserve(1, "stream state")) || (rc = d_ck.reserve(1, "chunk"))
+		    || (rc = d_info.reserve(1, "BAM slot sums")) || (rc = d_win.reserve(c.n_win + 1, "BAM windows")) || (rc = d_woff.reserve(c.n_win * VG_BAM_WIN_RECS, "BAM window records"))
+		    || (rc = d_cnt.reserve(c.n_win + 2, "BAM window counts")) || (rc = d_rec.reserve(c.cap_rec + 2, "BAM record offsets")) || (rc = d_off.reserve(c.cap_rec + 2, "read offsets"))
+		    || (rc = d_bases.reserve(c.cap_bases, "base text")) || (rc = d_gate.reserve(c.cap_rec + 2, "gate words")) || (rc = d_tmp.reserve(c.tmp_bytes, "scan scratch"))) return rc;
+		HIP_TRY(hipMemcpy(d_comp.p, bgzf + c0, comp_n, hipMemcpyHostToDevice));
+		HIP_TRY(hipMemcpy(d_tab.p, tab.data(), tab.size() * sizeof(vg_bgzf_block), hipMemcpyHostToDevice));
+		HIP_TRY(hipMemset(d_key.p, 0xff, sizeof(unsigned long long)));
+		HIP_TRY(hipMemset(d_st.p, 0, sizeof(FqStream)));
+		const bool timed = getenv("VG_VERBOSE") != nullptr;
+		hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+		if (timed) for (hipEvent_t &e : ev) HIP_TRY(hipEventCreate(&e));
+		if (timed) HIP_TRY(hipEventRecord(ev[0], nullptr));
+		vg_bgzf_inflate_kernel<<<(unsigned)tab.size(), 64>>>(d_comp.p, d_tab.p, (uint32_t)tab.size(), d_raw.p + BAM_CARRY, d_status.p, d_key.p);
+		if (timed) HIP_TRY(hipEventRecord(ev[1], nullptr));
+		const uint32_t entry0 = (uint32_t)(hdr_end > text_off ? hdr_end - text_off : 0);
+		vg_bam_prepare<<<1, 256>>>(d_st.p, d_ck.p, d_info.p, nullptr, d_raw.p, (uint32_t)text_n, d_key.p, (unsigned long long)(text_off + entry0));
+		HIP_TRY(hipGetLastError());
+		const BamFrame f{d_raw.p, d_st.p, d_ck.p, d_info.p, d_win.p, d_woff.p, d_cnt.p, d_rec.p, d_off.p, d_bases.p, d_gate.p, d_tmp.p};
+		if ((rc = bam_frame_enqueue(nullptr, prop.multiProcessorCount, f, c, n_ref, entry0, text_off))) return rc;
+		if (timed) HIP_TRY(hipEventRecord(ev[2], nullptr));
+		HIP_TRY(hipDeviceSynchronize());
+		if (timed) {
+			float ms_inf = 0, ms_frame = 0;
+			HIP_TRY(hipEventElapsedTime(&ms_inf, ev[0], ev[1])); HIP_TRY(hipEventElapsedTime(&ms_frame, ev[1], ev[2]));
+			fprintf(stderr, "[vargeno_hip] bam frame: %zu blocks, %llu inflated bytes, %llu windows: inflate %.3f ms, framing + gather %.3f ms\n", tab.size(), (unsigned long long)text_n, (unsigned long long)c.n_win, ms_inf, ms_frame);
+			for (hipEvent_t &e : ev) (void)hipEventDestroy(e);
+		}
+		FqStream st; FqChunk ck; unsigned long long key = ~0ull;
+		HIP_TRY(hipMemcpy(&st, d_st.p, sizeof st, hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(&ck, d_ck.p, sizeof ck, hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(&key, d_key.p, sizeof key, hipMemcpyDeviceToHost));
+		stats[0] = st.records; stats[1] = st.skipped_flag; stats[2] = st.skipped_empty; stats[3] = st.repairs;
+		if (ck.n_reads > cap_rec || ck.total > cap_bases) return fail(VG_ETOOBIG, "the BAM file's reads do not fit the caller's arrays");
+		if (ck.n_reads) {
+			HIP_TRY(hipMemcpy(offsets, d_off.p, ((size_t)ck.n_reads + 1) * 8, hipMemcpyDeviceToHost));
+			HIP_TRY(hipMemcpy(gate, d_gate.p, (size_t)ck.n_reads * 4, hipMemcpyDeviceToHost));
+			if (ck.total) HIP_TRY(hipMemcpy(bases, d_bases.p, ck.total, hipMemcpyDeviceToHost));
+		}
+		*n_records = ck.n_reads;
+		if (key != ~0ull) { *bad_offset = st.consumed; (void)fail(VG_EIO, "%s", bz_describe(key).c_str()); }
+		else if (st.poisoned) { *bad_offset = st.consumed; (void)fail(VG_EBADREAD, "the BAM records could not be framed on the device (a block_size out of range, a read of more than 1022 bases, or more than 64 repairs): frame from inflated offset %s on the host", std::to_string(st.consumed).c_str()); }
+		else if (st.carry || scan_rc || tail) { *bad_offset = st.consumed; (void)fail(VG_EIO, "the BAM stream ends inside a record, at inflated offset %s", std::to_string(st.consumed).c_str()); }
+		return VG_OK;
+	});
+}
+
+static int fq_collect(vg_index *ix, bool drain, uint64_t *n_records, uint64_t *consumed, uint64_t *last_record_start, int *refused, FqStream *state = nullptr)
 {
 	HIP_TRY(hipSetDevice(ix->device));
 	if (drain) { int rc = finish_pending(ix); if (rc) return rc; }
@@ -3308,6 +3837,7 @@ static int fq_collect(vg_index *ix, bool drain, uint64_t *n_records, uint64_t *c
 	if (consumed) *consumed = h.consumed;
 	if (last_record_start) *last_record_start = h.last_record;
 	if (refused) *refused = h.poisoned ? 1 : 0;
+	if (state) *state = h;
 	return VG_OK;
 }
 
@@ -3326,7 +3856,8 @@ extern "C" int vg_fastq_stream_end(vg_index *ix, uint64_t *n_records, uint64_t *
 		if (refused) *refused = ix->packer->poisoned() ? 1 : 0;
 		return VG_OK;
 	}
-	int rc = fq_collect(ix, true, n_records, consumed, last_record_start, refused);
+	FqStream h;
+	int rc = fq_collect(ix, true, n_records, consumed, last_record_start, refused, &h);
 	if (rc || !ix->fq_bgzf) return rc;
 	ix->fq_bgzf = false;
 	return guarded([&]() -> int {
@@ -3335,6 +3866,16 @@ extern "C" int vg_fastq_stream_end(vg_index *ix, uint64_t *n_records, uint64_t *
 		HIP_TRY(hipMemcpy(&key, bz.d_key, sizeof key, hipMemcpyDeviceToHost));
 		key = std::min(key, bz.host_key);
 		if (key != ~0ull) return fail(VG_EIO, "%s", bz_describe(key).c_str());
+		if (bz.bam && !bz.header_bad) {
+			// a BAM stream must end at a record boundary: say where it ends instead (and what the BGZF layer has to add)
+			const std::string tail = bz.carry.empty() ? std::string() : " (BGZF block at compressed offset " + std::to_string(bz.comp_pos) + ": incomplete)";
+			if (bz.bam_hdr_done && ix->fq_prev_slot < 0 && consumed) *consumed = bz.bam_hdr_end;   // (no slot was framed: nothing behind the header)
+			if (!bz.bam_hdr_done) {
+				if (consumed) *consumed = bz.text_pos;
+				return fail(VG_EIO, "the BAM stream ends inside its header, at inflated offset %s%s", std::to_string(bz.text_pos).c_str(), tail.c_str());
+			}
+			if (!h.poisoned && (h.carry || !bz.carry.empty())) return fail(VG_EIO, "the BAM stream ends inside a record, at inflated offset %s%s", std::to_string(h.consumed).c_str(), tail.c_str());
+		}
 		if (bz.header_bad) return fail(VG_EIO, "BGZF block at compressed offset %s: not a BGZF block header", std::to_string(bz.comp_pos).c_str());
 		if (!bz.carry.empty()) return fail(VG_EIO, "BGZF block at compressed offset %s: incomplete (the stream ends %s bytes into it)", std::to_string(bz.comp_pos).c_str(), std::to_string(bz.carry.size()).c_str());
 		return VG_OK;
