@@ -289,6 +289,63 @@ int  vg_bgzf_inflate_host(const uint8_t *bgzf, uint64_t nbytes, uint8_t *text, u
  * payload offset, payload length, ISIZE, CRC32.  *consumed / *bad_block_offset as above (header errors only). */
 int  vg_bgzf_scan_host(const uint8_t *bgzf, uint64_t nbytes, uint64_t *blocks, uint64_t blocks_cap, uint64_t *n_blocks, uint64_t *consumed, uint64_t *bad_block_offset);
 
+/* Plain gzip (RFC 1952 members around one DEFLATE stream: what gzip, pigz and sequencers write; no block table) without a handle.
+ * gz[0, nbytes) is inflated member after member into text[0, text_cap) in host memory; *text_len = bytes of text, *consumed =
+ * compressed bytes used, both at the end of the last member that was decoded whole with its CRC32 and ISIZE (mod 2^32) verified.
+ * Bad data -- a truncated member, a CRC32 or ISIZE mismatch, bytes after a member that are no gzip header, a broken DEFLATE block --
+ * returns VG_EIO: *bad_offset is the compressed offset and vg_last_error() names it with the decoder's reason.  VG_ETOOBIG: the
+ * text does not fit.
+ *   vg_gunzip_host            the reference decoder: sequential, one thread
+ *   vg_gunzip_device          the chunked route on `device`: the compressed bytes are cut into slots and the slots into chunks; a
+ *                             wave per chunk guesses a block start and decodes from it into 16-bit symbols, the guesses are
+ *                             confirmed against their predecessors' exits, the wrong ones repaired in order, and the symbols
+ *                             resolved into text (DESIGN.md §4 "The plain-gzip kernels"; the routes are in §5).  The result is the reference decoder's whatever was guessed.
+ *   vg_gunzip_chunked_host    the same stages run on the host, one after the other: what the kernels do, with no device
+ * The chunked calls take their sizes from `opts` (a field that is 0, or opts NULL: from the environment, read at every call): VG_GZ_CHUNK (compressed bytes per chunk, default 16384),
+ * VG_GZ_SLOT (compressed bytes per slot, default 16 MiB, at most 64 MiB), VG_GZ_MAX_RATIO (a slot's text capacity as a multiple of
+ * its compressed bytes, default 8), VG_GZ_SLOT_MAX (a slot that holds no whole DEFLATE block is tried again twice as long, up to
+ * this many bytes, default and at most 64 MiB; beyond it the call fails with VG_EIO, "deflate block larger than a slot").  A slot whose text would exceed that bound, or that needs more than 64 repairs, is REFUSED, never
+ * overrun: the call returns VG_OK with stats->slots_refused = 1, *text_len / *consumed at that slot's entry -- a block boundary,
+ * whose exact bit offset is stats->resume_bit (*consumed = resume_bit / 8) -- and the caller decodes on from there by other means. */
+typedef struct vg_gzip_opts {
+	uint64_t chunk_bytes;      /* VG_GZ_CHUNK */
+	uint64_t slot_bytes;       /* VG_GZ_SLOT */
+	uint64_t max_ratio;        /* VG_GZ_MAX_RATIO */
+	uint64_t slot_max;         /* VG_GZ_SLOT_MAX */
+} vg_gzip_opts;
+typedef struct vg_gzip_stats {
+	uint64_t members;          /* members decoded whole and verified */
+	uint64_t chunks;           /* chunks of all slots */
+	uint64_t guessed;          /* chunks with an entry: a slot's chunk 0, or a guess of the finder */
+	uint64_t confirmed;        /* guesses that were their predecessor's exit */
+	uint64_t repaired;         /* chunks decoded again from their predecessor's exit */
+	uint64_t tested;           /* bit offsets that passed the prefilter and took the full header test */
+	uint64_t slots_refused;
+	uint64_t resume_bit;       /* compressed bit offset of the last block boundary reached (a member's end: its next byte) */
+} vg_gzip_stats;
+int  vg_gunzip_host(const uint8_t *gz, uint64_t nbytes, uint8_t *text, uint64_t text_cap, uint64_t *text_len, uint64_t *consumed, uint64_t *bad_offset);
+int  vg_gunzip_device(int device, const uint8_t *gz, uint64_t nbytes, uint8_t *text, uint64_t text_cap, uint64_t *text_len, uint64_t *consumed, uint64_t *bad_offset, vg_gzip_stats *stats, const vg_gzip_opts *opts);
+int  vg_gunzip_chunked_host(const uint8_t *gz, uint64_t nbytes, uint8_t *text, uint64_t text_cap, uint64_t *text_len, uint64_t *consumed, uint64_t *bad_offset, vg_gzip_stats *stats, const vg_gzip_opts *opts);
+/* The same decisions over PUSHES of push_bytes, on the host: what a gzip stream (below) does with bytes cut anywhere -- the incomplete
+ * tail block, a header or a trailer cut short wait for the next push.  Results as vg_gunzip_chunked_host's, byte for byte. */
+int  vg_gunzip_pushed_host(const uint8_t *gz, uint64_t nbytes, uint64_t push_bytes, uint8_t *text, uint64_t text_cap, uint64_t *text_len, uint64_t *consumed, uint64_t *bad_offset, vg_gzip_stats *stats, const vg_gzip_opts *opts);
+
+/* The device-framed FASTQ stream over plain gzip.  After vg_fastq_stream_begin_gzip, vg_fastq_stream_push takes gzip bytes cut
+ * anywhere; whole slots of them (VG_GZ_SLOT, read at begin like the other VG_GZ_* sizes) are inflated on the device by the chunked
+ * route above and their text is framed where it lies; the bytes of an incomplete block wait on the host for the next push.
+ * vg_fastq_stream_end inflates what is left, and returns VG_OK only when every member's CRC32 and ISIZE were verified; bad data is
+ * VG_EIO, vg_last_error() naming the compressed offset and the reason.  Offsets it reports (consumed, last_record_start) are TEXT
+ * offsets.  A REFUSED slot (text beyond the ratio bound, more than 64 repairs) poisons the stream as a refused text chunk does:
+ * nothing of it or after it is framed, *refused = 1, and the caller takes over on the host:
+ *   vg_fastq_stream_gzip_checkpoint   the last slot entry at or before a text offset: its compressed BIT offset in the file (a
+ *                                     DEFLATE block boundary inside a member), the text offset there, and the member's text in
+ *                                     front of it (window[0, *window_len), at most 32768 bytes) -- enough to inflate on from there.
+ *                                     The member's CRC32 cannot be checked by who starts there.  No slot entered: bit offset 0.
+ *   vg_gzip_stream_stats              the counts of the stream so far (valid until the next vg_fastq_stream_begin_gzip) */
+int  vg_fastq_stream_begin_gzip(vg_index *ix);
+int  vg_gzip_stream_stats(vg_index *ix, vg_gzip_stats *stats);
+int  vg_fastq_stream_gzip_checkpoint(vg_index *ix, uint64_t text_offset, uint64_t *comp_bit_offset, uint64_t *ckpt_text_offset, uint8_t *window, uint32_t *window_len);
+
 /* One self-contained chunk, synchronously: *consumed = bytes used (the rest, an incomplete last record, is the caller's to
  * resubmit with the next chunk); waits for the framing, not for the read loop.  VG_EBADREAD: the chunk was refused (see above);
  * nothing was processed. */

@@ -25,7 +25,11 @@ SYMBOLS = ["vg_last_error", "vg_build_id", "vg_device_count", "vg_device_memory"
            "vg_samples_reserve", "vg_num_samples", "vg_sample_select", "vg_sample_selected", "vg_sample_reset", "vg_sample_invalid_reads",
            "vg_fastq_stream_begin_bgzf", "vg_fastq_stream_bgzf_locate", "vg_bgzf_inflate_device", "vg_bgzf_inflate_host", "vg_bgzf_scan_host",
            "vg_sample_calls_fetch", "vg_call_device",
-           "vg_fastq_stream_begin_bam", "vg_bam_stream_stats", "vg_bam_frame_device", "vg_bam_to_fastq_host"]
+           "vg_fastq_stream_begin_bam", "vg_bam_stream_stats", "vg_bam_frame_device", "vg_bam_to_fastq_host",
+           "vg_gunzip_host", "vg_gunzip_device", "vg_gunzip_chunked_host", "vg_gunzip_pushed_host",
+           "vg_fastq_stream_begin_gzip", "vg_gzip_stream_stats", "vg_fastq_stream_gzip_checkpoint"]
+
+GZIP_STAT_FIELDS = ["members", "chunks", "guessed", "confirmed", "repaired", "tested", "slots_refused", "resume_bit"]
 
 
 class VgStats(C.Structure):
@@ -33,6 +37,17 @@ class VgStats(C.Structure):
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n in STAT_FIELDS}
+
+
+class VgGzipStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in GZIP_STAT_FIELDS]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n in GZIP_STAT_FIELDS}
+
+
+class VgGzipOpts(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("chunk_bytes", "slot_bytes", "max_ratio", "slot_max")]
 
 
 class VgTiming(C.Structure):
@@ -162,6 +177,13 @@ def lib():
         L.vg_fastq_stream_bgzf_locate.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
         L.vg_bgzf_inflate_device.argtypes = [C.c_int, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.vg_bgzf_inflate_host.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.vg_gunzip_host.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.vg_gunzip_device.argtypes = [C.c_int, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(VgGzipStats), C.POINTER(VgGzipOpts)]
+        L.vg_gunzip_chunked_host.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(VgGzipStats), C.POINTER(VgGzipOpts)]
+        L.vg_gunzip_pushed_host.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(VgGzipStats), C.POINTER(VgGzipOpts)]
+        L.vg_fastq_stream_begin_gzip.argtypes = [vp]
+        L.vg_gzip_stream_stats.argtypes = [vp, C.POINTER(VgGzipStats)]
+        L.vg_fastq_stream_gzip_checkpoint.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp, C.POINTER(C.c_uint32)]
         L.vg_bgzf_scan_host.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.vg_fastq_stream_begin_bam.argtypes = [vp]
         L.vg_bam_stream_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]

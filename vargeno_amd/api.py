@@ -9,6 +9,7 @@ library.  Nothing here can run without it.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 
@@ -150,7 +151,7 @@ class GenoIndex:
         check(lib().vg_reads_submit_store(self._h, store._h))
         self._stores.append(store)        # (released by sync / counts / stats / close: the batches read the store's memory until then)
 
-    def fastq_stream(self, chunks, host_threads=None, bgzf=False, bam=False):
+    def fastq_stream(self, chunks, host_threads=None, bgzf=False, bam=False, gzip=False):
         """FASTQ text as a stream of byte chunks cut anywhere (numpy uint8 arrays / bytes; pinned host memory copies at link
         speed): records are framed across the cuts -- on the device (host_threads None or 0), or framed and 2-bit packed by
         that many host threads inside the library (-1: the library picks).  Returns (records, bytes consumed, start of the
@@ -159,8 +160,13 @@ class GenoIndex:
         uncompressed text.  A bad block raises VgError (VG_EIO) naming its compressed offset; what was framed before it counts.
         bam=True: the chunks are a BAM file's bytes, inflated and framed on the device; records counts kept records, the offsets
         are offsets in the inflated BAM stream (bam_stats() has the stream's other counters).  A stream that ends inside the
-        header or a record raises VgError (VG_EIO) naming the inflated offset."""
-        if bam:
+        header or a record raises VgError (VG_EIO) naming the inflated offset.
+        gzip=True: the chunks are plain gzip bytes (cut anywhere), inflated on the device by the chunked route and framed there; the
+        offsets returned are text offsets, refused is also set by a refused slot (gzip_stats(), gzip_checkpoint()).  Bad data -- a
+        CRC32 mismatch included -- raises VgError (VG_EIO) naming the compressed offset."""
+        if gzip:
+            check(lib().vg_fastq_stream_begin_gzip(self._h))
+        elif bam:
             check(lib().vg_fastq_stream_begin_bam(self._h))
         elif bgzf:
             check(lib().vg_fastq_stream_begin_bgzf(self._h))
@@ -180,6 +186,20 @@ class GenoIndex:
         v = [C.c_uint64() for _ in range(4)]
         check(lib().vg_bam_stream_stats(self._h, *[C.byref(x) for x in v]))
         return tuple(int(x.value) for x in v)
+
+    def gzip_stats(self):
+        """vg_gzip_stats of the handle's last gzip stream, as a dict."""
+        from ._lib import VgGzipStats
+        st = VgGzipStats()
+        check(lib().vg_gzip_stream_stats(self._h, C.byref(st)))
+        return st.as_dict()
+
+    def gzip_checkpoint(self, text_offset):
+        """The last slot entry of the last gzip stream at or before a text offset: (compressed bit offset, text offset, window bytes)."""
+        bit, at, n = C.c_uint64(), C.c_uint64(), C.c_uint32()
+        win = np.zeros(32768, dtype=np.uint8)
+        check(lib().vg_fastq_stream_gzip_checkpoint(self._h, int(text_offset), C.byref(bit), C.byref(at), _ptr(win), C.byref(n)))
+        return int(bit.value), int(at.value), win[:int(n.value)].tobytes()
 
     def bgzf_locate(self, text_offset):
         """(compressed offset of the block, offset inside its text) of an uncompressed offset of the last BGZF stream."""
@@ -435,6 +455,44 @@ def bgzf_inflate(data, device=0, out=None, text_cap=None):
     else:
         check(lib().vg_bgzf_inflate_device(int(device), _ptr(a), len(a), _ptr(out), int(text_cap), C.byref(n), C.byref(used), C.byref(bad)))
     return out[:int(n.value)].tobytes(), int(used.value), (None if bad.value == 2 ** 64 - 1 else int(bad.value))
+
+
+class GunzipResult(collections.namedtuple("GunzipResult", "text consumed bad_offset stats error")):
+    """text: the bytes of the members decoded whole and verified; consumed: compressed bytes up to there; bad_offset / error: the
+    compressed offset and the library's message when the data is bad (None otherwise); stats: vg_gzip_stats as a dict (chunked
+    routes; None for the sequential decoder)."""
+
+
+def gunzip(data, device=0, chunked=False, text_cap=None, chunk=None, slot=None, ratio=None, slot_max=None, push=None):
+    """Plain gzip (RFC 1952, any number of members) inflated: on `device` by the chunked kernels, or (device=None) on the host --
+    by the sequential reference decoder, or with chunked=True by the same chunked stages the kernels run.  chunk / slot / ratio /
+    slot_max: the sizes of this call, passed as vg_gzip_opts (one left None is the environment's VG_GZ_CHUNK / VG_GZ_SLOT /
+    VG_GZ_MAX_RATIO / VG_GZ_SLOT_MAX, or the default).  text_cap: room for the
+    text (default 16 bytes per compressed byte + 64 KiB).  Returns a GunzipResult; bad data is reported in it, not raised."""
+    from ._lib import VgGzipOpts, VgGzipStats
+
+    a = _u8(data)
+    if text_cap is None:
+        text_cap = 16 * len(a) + 65536
+    out = np.zeros(max(1, int(text_cap)), dtype=np.uint8)
+    n, used, bad = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    st = VgGzipStats()
+    op = VgGzipOpts(*[int(v or 0) for v in (chunk, slot, ratio, slot_max)])
+    if push is not None:                                       # (host only: the push driver over the host stages, `push` bytes at a time)
+        rc = lib().vg_gunzip_pushed_host(_ptr(a), len(a), int(push), _ptr(out), int(text_cap), C.byref(n), C.byref(used), C.byref(bad), C.byref(st), C.byref(op))
+    elif device is not None:
+        rc = lib().vg_gunzip_device(int(device), _ptr(a), len(a), _ptr(out), int(text_cap), C.byref(n), C.byref(used), C.byref(bad), C.byref(st), C.byref(op))
+    elif chunked:
+        rc = lib().vg_gunzip_chunked_host(_ptr(a), len(a), _ptr(out), int(text_cap), C.byref(n), C.byref(used), C.byref(bad), C.byref(st), C.byref(op))
+    else:
+        rc = lib().vg_gunzip_host(_ptr(a), len(a), _ptr(out), int(text_cap), C.byref(n), C.byref(used), C.byref(bad))
+    error = None
+    if rc == -2:                                               # VG_EIO: bad data
+        error = lib().vg_last_error().decode()
+    else:
+        check(rc)
+    stats = st.as_dict() if (device is not None or chunked or push is not None) else None
+    return GunzipResult(out[:int(n.value)].tobytes(), int(used.value), (None if bad.value == 2 ** 64 - 1 else int(bad.value)), stats, error)
 
 
 def bam_to_fastq(data):

@@ -78,6 +78,7 @@
 #include "vg_host.h"
 #include "bgzf.cpp"       // the host side of the BGZF routes, in this translation unit (csrc/Makefile: builds that list the four host files get it)
 #include "bam.cpp"        // the host side of the BAM routes, the same way; behind bgzf.cpp, whose helpers it uses
+#include "gzip.cpp"       // the host side of the plain-gzip route, the same way
 
 static void print_help()
 {
@@ -95,6 +96,15 @@ static void arg_check(int argc, int expected)
 }
 static int env_int(const char *name, int dflt) { const char *e = getenv(name); return e && *e ? atoi(e) : dflt; }
 static const char *env_str(const char *name) { const char *e = getenv(name); return e ? e : ""; }
+// VARGENO_GZIP, read once: what becomes of a plain gzip file (gzip magic, no BGZF block table).  Unset or empty: refused by name.
+// `host`: inflated by one host thread into a pipe.  `device`: `geno` with one replica streams the compressed file to the device
+// (gzip_device_route); every other job takes the host route.  Anything else is refused like unset.
+enum class GzipRoute { Refuse, Host, Device };
+static GzipRoute gzip_route()
+{
+	static const GzipRoute r = [] { const std::string v = env_str("VARGENO_GZIP"); return v == "host" ? GzipRoute::Host : v == "device" ? GzipRoute::Device : GzipRoute::Refuse; }();
+	return r;
+}
 // CPUs this process may use: the hardware threads, capped by a cgroup CPU quota (cpu.max: "<quota> <period>"; this pool's GPU boxes
 // give a container 16 CPUs' worth of time on a 256-thread host)
 static int usable_cpus()
@@ -137,6 +147,11 @@ struct GenoOptions {
 	// and are inflated there; `host` (the default until profiles/bgzf_ingest.txt says otherwise): inflated here, then the once-only route
 	const int bgzf_threads = std::max(1, std::min(env_int("VARGENO_BGZF_THREADS", vgh::bgzf_threads_default(hw)), 256));
 	const bool bgzf_device = std::string(env_str("VARGENO_BGZF")) == "device";
+	// plain gzip input (no block table): refused unless VARGENO_GZIP asks for it -- `host`: one thread inflates into a pipe (GzipTextPipe)
+	// `device`: one replica streams the compressed file to the device, which inflates it slot by slot (vg_fastq_stream_begin_gzip);
+	// several replicas and every `cohort` / `joint` sample take the host route, as BGZF does
+	const bool gzip_host = gzip_route() != GzipRoute::Refuse;
+	const bool gzip_device = gzip_route() == GzipRoute::Device;
 	const bool caller_device = std::string(env_str("VARGENO_CALLER")) == "device";      // genotypes from the caller kernel (default: the host loop)
 	explicit GenoOptions(int devices) : have(devices)
 	{
@@ -223,7 +238,8 @@ struct StreamResult {
 };
 // STREAM_BGZF: the bytes are BGZF (vg_fastq_stream_begin_bgzf) -- the same ring over the compressed file; the result's offsets are text
 // offsets.  STREAM_BAM: a BAM file (vg_fastq_stream_begin_bam); the offsets are offsets in the inflated BAM stream.
-enum StreamBytes { STREAM_TEXT, STREAM_BGZF, STREAM_BAM };
+// STREAM_GZIP: plain gzip (vg_fastq_stream_begin_gzip); text offsets too.
+enum StreamBytes { STREAM_TEXT, STREAM_BGZF, STREAM_BAM, STREAM_GZIP };
 static StreamResult stream_range(vg_index *ix, int fd, uint64_t lo, uint64_t hi, uint64_t chunk, int n_readers, int pack_threads, StreamBytes bytes = STREAM_TEXT)
 {
 	StreamResult res;
@@ -235,7 +251,7 @@ static StreamResult stream_range(vg_index *ix, int fd, uint64_t lo, uint64_t hi,
 		if (!ring[(size_t)i]) { pageable[(size_t)i].resize((size_t)chunk); ring[(size_t)i] = pageable[(size_t)i].data(); }
 	}
 	RangeReader rr(fd, lo, hi, chunk, n_readers, ring);
-	int rc = bytes == STREAM_BAM ? vg_fastq_stream_begin_bam(ix) : bytes == STREAM_BGZF ? vg_fastq_stream_begin_bgzf(ix) : pack_threads > 0 ? vg_fastq_stream_begin_packed(ix, pack_threads) : vg_fastq_stream_begin(ix);
+	int rc = bytes == STREAM_GZIP ? vg_fastq_stream_begin_gzip(ix) : bytes == STREAM_BAM ? vg_fastq_stream_begin_bam(ix) : bytes == STREAM_BGZF ? vg_fastq_stream_begin_bgzf(ix) : pack_threads > 0 ? vg_fastq_stream_begin_packed(ix, pack_threads) : vg_fastq_stream_begin(ix);
 	for (uint64_t i = 0; i < rr.n_chunks() && rc == VG_OK; i++) {
 		if (!rr.wait(i)) break;
 		rc = vg_fastq_stream_push(ix, rr.buf(i), rr.chunk_len(i));
@@ -633,6 +649,7 @@ struct FastqInput {
 	bool cuts_ok = false;                      // a regular file, and cut[] holds a record-aligned range per replica
 	std::vector<uint64_t> cut;
 	bool bgzf_device = false;                  // a BGZF file, one replica, VARGENO_BGZF=device: the compressed bytes are streamed to the device
+	bool gzip_device = false;                  // a plain gzip file, one replica, VARGENO_GZIP=device: the same, through the chunked inflate
 	bool bam = false;                          // ... the file is BAM: the device frames its records (bgzf_device), or the pipe below converts them to text
 	std::unique_ptr<vgh::TextPipe> bz_pipe;    // a BGZF / BAM file on every other route: inflated (and converted) by host threads; fd is the pipe's read end
 	int file_fd = -1;                          // ... and the file itself
@@ -676,6 +693,13 @@ static bool open_fastq(const std::string &fastq, const GenoOptions &o, FastqInpu
 		in.file_fd = in.fd;
 		if (in.bam) in.bz_pipe.reset(new vgh::BamTextPipe(in.file_fd, 0, 0, o.bgzf_threads, true, 0));
 		else in.bz_pipe.reset(new vgh::BgzfTextPipe(in.file_fd, 0, 0, o.bgzf_threads));
+		if (in.bz_pipe->read_fd() < 0) { fprintf(stderr, "vargeno: %s\n", in.bz_pipe->error.c_str()); return false; }
+		in.fd = in.bz_pipe->read_fd();
+		in.once_only = true;
+	} else if (kind == vgh::FastqKind::PlainGzip && o.gzip_host) {          // (VARGENO_GZIP unset: plain_gzip() has refused the file before)
+		if (o.gzip_device && o.ngpu == 1 && !o.host_framing) { in.gzip_device = true; return true; }
+		in.file_fd = in.fd;
+		in.bz_pipe.reset(new vgh::GzipTextPipe(in.file_fd));
 		if (in.bz_pipe->read_fd() < 0) { fprintf(stderr, "vargeno: %s\n", in.bz_pipe->error.c_str()); return false; }
 		in.fd = in.bz_pipe->read_fd();
 		in.once_only = true;
@@ -905,6 +929,34 @@ static HostHandover bam_device_route(const GenoOptions &o, const FastqInput &in,
 	                       r.refused ? "; the device refused a chunk: the host converts the rest" : "");
 	return HostHandover{r.nrec, tk.text.size(), r.nrec ? 0 : UINT64_MAX, 0};
 }
+// One replica, a plain gzip file, VARGENO_GZIP=device: the compressed file goes to the device through the same reader ring
+// (vg_fastq_stream_begin_gzip), which inflates it slot by slot and frames the text.  The host take-over behind it (a refused slot, a
+// framing refusal, a truncated final record) needs text from the last framed record on: vg_fastq_stream_gzip_checkpoint gives the
+// last slot entry at or before it -- a bit offset and the 32 KiB in front of it --, the text from there to the hand-over point is
+// inflated here into a memory span, and the same GzipTextPipe inflates the rest of the file into a pipe.
+static HostHandover gzip_device_route(const GenoOptions &o, const FastqInput &in, vg_index *ix, BgzfTakeover &tk)
+{
+	struct timespec a, b; clock_gettime(CLOCK_MONOTONIC, &a);
+	const StreamResult r = stream_range(ix, in.fd, 0, in.fsize, o.chunk(16), o.range_readers(), 0, STREAM_GZIP);
+	if (!r.error.empty()) { fprintf(stderr, "vargeno: %s\n", r.error.c_str()); exit(EXIT_FAILURE); }
+	clock_gettime(CLOCK_MONOTONIC, &b);
+	vg_gzip_stats st;
+	VG_CHECK(vg_gzip_stream_stats(ix, &st));
+	const uint64_t from = r.nrec ? r.last : r.used;                      // the span starts at or before the last framed record (it primes the stale buffers)
+	uint64_t at_bit = 0, ck_text = 0;
+	uint32_t win_len = 0;
+	std::vector<uint8_t> win(32768);
+	VG_CHECK(vg_fastq_stream_gzip_checkpoint(ix, from, &at_bit, &ck_text, win.data(), &win_len));
+	tk.rest.reset(new vgh::GzipTextPipe(in.fd, at_bit, win.data(), win_len, r.used - ck_text, tk.text));
+	if (tk.rest->read_fd() < 0) { fprintf(stderr, "vargeno: %s\n", tk.rest->error.c_str()); exit(EXIT_FAILURE); }
+	tk.mem.base = ck_text;
+	tk.mem.spans.assign(1, std::make_pair((const uint8_t *)tk.text.data(), tk.text.size()));
+	if (o.verbose) fprintf(stderr, "ingest, replica 0: gzip inflated on the device: %lu reads framed, %lu members, %lu chunks, %lu guessed, %lu confirmed, %lu repaired, %lu header tests, %lu slots refused; "
+	                               "%.3f GB compressed (%.2f GB/s), %.3f GB of text (%.2f GB/s) in %.2f s%s\n", (unsigned long)r.nrec, (unsigned long)st.members, (unsigned long)st.chunks, (unsigned long)st.guessed,
+	                       (unsigned long)st.confirmed, (unsigned long)st.repaired, (unsigned long)st.tested, (unsigned long)st.slots_refused, (double)in.fsize / 1e9, (double)in.fsize / 1e9 / secs(a, b), (double)r.used / 1e9,
+	                       (double)r.used / 1e9 / secs(a, b), secs(a, b), st.slots_refused ? "; a slot was refused: the host inflates the rest" : r.refused ? "; the stream framing refused a chunk: the host reader takes the rest" : "");
+	return HostHandover{r.nrec, r.used, r.nrec ? r.last : UINT64_MAX, 0};
+}
 // a TextPipe has met the end of its text: what it has to say (false: a bad block or record, said on stderr)
 static bool bgzf_pipe_verdict(const GenoOptions &o, vgh::TextPipe &bp, const char *what, bool tail_of_device_route = false)
 {
@@ -1039,8 +1091,9 @@ static bool plain_gzip(const std::string &fastq)
 		fprintf(stderr, "vargeno: %s is a CRAM file: CRAM is not read here -- pipe `samtools fastq %s` through a FIFO (mkfifo reads.fq; samtools fastq %s > reads.fq &) and pass the FIFO\n", fastq.c_str(), fastq.c_str(), fastq.c_str());
 		return true;
 	}
-	if (plain) fprintf(stderr, "vargeno: %s is gzip but not BGZF: only BGZF (bgzip) is inflated here -- recompress with bgzip, or pass <(zcat %s)\n", fastq.c_str(), fastq.c_str());
-	return plain;
+	if (!plain || gzip_route() != GzipRoute::Refuse) return false;     // (VARGENO_GZIP=device|host: open_fastq / the cohort worker inflate it)
+	fprintf(stderr, "vargeno: %s is gzip but not BGZF: only BGZF (bgzip) is inflated here unless VARGENO_GZIP=device|host asks for plain gzip (on the device, or by one host thread) -- or recompress with bgzip, or pass <(zcat %s)\n", fastq.c_str(), fastq.c_str());
+	return true;
 }
 
 static int run_geno(const std::string &prefix, const std::string &fastq, const std::string &vcf_in, const std::string &vcf_out)
@@ -1063,7 +1116,7 @@ static int run_geno(const std::string &prefix, const std::string &fastq, const s
 	std::unique_ptr<PipeIngest> pipe_in;
 	std::vector<std::unique_ptr<PrePacker>> pre;
 	if (in.once_only && !o.host_framing) pipe_in = start_pipe_ingest(o, in.fd, store, ix);
-	else if (!in.bgzf_device && !o.host_framing) pre = start_prepackers(o, in, store);
+	else if (!in.bgzf_device && !in.gzip_device && !o.host_framing) pre = start_prepackers(o, in, store);
 	// the SNP list is read now, beside the index open (the VCF pass at the end of the job starts from its bytes)
 	std::string vcf_text;
 	bool vcf_ok = false;
@@ -1083,6 +1136,7 @@ static int run_geno(const std::string &prefix, const std::string &fastq, const s
 	BgzfTakeover tk;
 	if (pipe_in) { hand = once_only_route(o, *pipe_in, ix, store); mem.base = pipe_in->span_base; mem.spans = pipe_in->spans; reader_mem = &mem; }
 	else if (in.bgzf_device) { hand = in.bam ? bam_device_route(o, in, ix[0], tk) : bgzf_device_route(o, in, ix[0], tk); reader_mem = &tk.mem; reader_fd = tk.rest->read_fd(); }
+	else if (in.gzip_device) { hand = gzip_device_route(o, in, ix[0], tk); reader_mem = &tk.mem; reader_fd = tk.rest->read_fd(); }
 	else if (!o.host_framing) {
 		hand = ranged_route(o, in, ix, store, pre);
 		pre.clear();
@@ -1222,6 +1276,7 @@ static int run_cohort(const std::string &prefix, const std::string &manifest, co
 			const vgh::FastqKind kind = fstat(file_fd, &sb) == 0 && S_ISREG(sb.st_mode) ? vgh::sniff_fastq(file_fd) : vgh::FastqKind::Text;
 			if (kind == vgh::FastqKind::Bgzf) bz.reset(new vgh::BgzfTextPipe(file_fd, 0, 0, std::max(1, o.bgzf_threads / K)));
 			else if (kind == vgh::FastqKind::Bam) bz.reset(new vgh::BamTextPipe(file_fd, 0, 0, std::max(1, o.bgzf_threads / K), true, 0));
+			else if (kind == vgh::FastqKind::PlainGzip && o.gzip_host) bz.reset(new vgh::GzipTextPipe(file_fd));
 			const int fd = bz ? bz->read_fd() : file_fd;
 			(void)fcntl(fd, F_SETPIPE_SZ, 1 << 20);
 			uint64_t total = 0;
@@ -1343,6 +1398,14 @@ int main(int argc, const char *argv[])
 			}
 			bp.finish();
 			if (!bp.error.empty()) throw vgh::Error{bp.error};
+			return EXIT_SUCCESS;
+		} else if (opt == "gzcat") {
+			// hidden: a plain gzip file's text on stdout, by the host build of the decoder alone (no device needed; tests/test_gzip_cpu.py)
+			arg_check(argc, 1);
+			const int fd = open(argv[2], O_RDONLY);
+			if (fd < 0) throw vgh::Error{std::string("cannot open ") + argv[2]};
+			std::string err;
+			if (!vgh::gzip_cat(fd, stdout, err)) throw vgh::Error{std::string(argv[2]) + ": " + err};
 			return EXIT_SUCCESS;
 		} else if (opt == "bamcat") {
 			// hidden: a BAM file's equivalent FASTQ text on stdout, by the host threads of the BamTextPipe (no device needed; tests/test_bam_cpu.py)

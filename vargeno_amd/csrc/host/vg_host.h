@@ -3,6 +3,7 @@
 // what sits on either side of the C-ABI in include/vargeno_hip.h.
 #pragma once
 #include <stdint.h>
+#include <stdio.h>
 
 #include <string>
 #include <utility>
@@ -90,6 +91,32 @@ private:
 // The blocks from compressed offset comp_from on, inflated on this thread until they hold more than want_text bytes (or the file
 // ends); *comp_next = offset of the block after them.  false: err says which block is bad.
 bool bgzf_inflate_span(int fd, uint64_t comp_from, uint64_t want_text, std::vector<uint8_t> &text, uint64_t *comp_next, std::string &err);
+
+// ---- plain gzip on the host (gzip.cpp; the decoder is ../vg_gunzip.h, shared with the device kernels) ----
+// A plain gzip file (any number of members) as a once-only text descriptor: one thread runs the sequential decoder into a pipe.
+// After finish(): error names the compressed offset of bad data -- a broken block, a CRC32 or ISIZE mismatch, a truncated member,
+// bytes behind a member that are no gzip header.
+class GzipTextPipe : public TextPipe {
+public:
+	explicit GzipTextPipe(int fd);
+	// Behind a device stream (vg_fastq_stream_gzip_checkpoint): the decoder starts at compressed bit offset at_bit, a block boundary
+	// inside a member whose text in front of it is win[0, win_len); the first span_len bytes of its text are decoded by the
+	// constructor into `span`, the rest goes into the pipe.  The CRC32 of the member it starts in is not checked (the device checks
+	// it when it inflates that member to its end).  read_fd() < 0: error says why.
+	GzipTextPipe(int fd, uint64_t at_bit, const uint8_t *win, uint32_t win_len, uint64_t span_len, std::vector<uint8_t> &span);
+	~GzipTextPipe() override;
+	GzipTextPipe(const GzipTextPipe &) = delete;
+	GzipTextPipe &operator=(const GzipTextPipe &) = delete;
+	int read_fd() const override;
+	void finish() override;
+	std::string describe(const char *what, bool takeover) const override;
+private:
+	void start(int fd);
+	struct Impl;
+	Impl *p;
+};
+// the text of the gzip file at fd written to `to` by the same decoder on this thread; false: err says what is wrong, and where
+bool gzip_cat(int fd, FILE *to, std::string &err);
 
 // ---- BAM on the host (bam.cpp; the record parser is ../vg_bam.h, shared with the device kernels) ----
 // The header of the BAM file at fd, from its leading blocks: offset of the first record in the inflated stream, and n_ref.

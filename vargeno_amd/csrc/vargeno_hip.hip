@@ -14,6 +14,7 @@
 #include "vg_arena.h"
 #include "vg_inflate.h"
 #include "vg_bam.h"
+#include "vg_gunzip.h"
 #include "vg_caller.h"
 
 #include <dlfcn.h>
@@ -1036,6 +1037,299 @@ __global__ __launch_bounds__(64) void vg_bgzf_inflate_kernel(const uint8_t *__re
 }
 
 // ------------------------------------------------------------------------------------------------
+// kernels: plain gzip inflated on the device (vg_gunzip.h is the finder, the decoder and the resolve; this is their wave policy)
+//
+// A slot of compressed bytes is cut into fixed chunks; ONE WAVE PER CHUNK finds a block start in its range (vg_gz_find) and decodes
+// from it into 16-bit symbols (vg_gz_decode), one decode state per wave as in BzWaveIO.  vg_gz_confirm compares each guess with its
+// predecessor's exit, vg_gz_repair (one wave) decodes the mismatched chunks again in order and writes the slot's record and the
+// chunks' output lengths; after the scan of those, vg_gz_windows (one workgroup, serial over the chunks) resolves each chunk's last
+// 32 Ki symbols against a window it keeps in LDS, and vg_gz_resolve (a full grid) the rest; vg_gz_crc folds the text's CRC32.
+//
+// LDS per decode workgroup (GzShared, 70 144 B: two per CU of 160 KiB):
+//   sym   65 536   the most recent 32 Ki symbols: back-references never read global memory another lane has just written
+//   ring   1 024   compressed input, as in BzShared
+//   t      3 648   code tables (vg_inflate.h)
+// Symbols are also stored straight to the chunk's staging area in global memory, never read back by this kernel.
+// ------------------------------------------------------------------------------------------------
+struct GzFindShared { uint4 ring[64]; VgInfTables t; };
+struct GzShared { uint16_t sym[VG_GZ_WINDOW]; uint4 ring[64]; VgInfTables t; };
+
+struct GzWaveIO {
+	typedef uint32_t opos;
+	uint16_t *symp;                // LDS: the symbol ring (decode only)
+	uint16_t *outg;                // global: the chunk's staging area
+	uint32_t *ring32;              // LDS: 256 words of input
+	uint4 *ring16;
+	const uint4 *src;              // global: the 16-byte aligned address at or below the slot's first byte
+	const uint8_t *in;             // global: the slot's bytes
+	uint32_t in_len, skew;         // slot bytes; in - (const uint8_t *)src
+	uint32_t n_vec;                // 16-byte vectors of src that hold slot bytes: nothing beyond them is loaded
+	uint32_t g0;                   // vector index of ring16[0]
+	uint4 pre;                     // this lane's vector of the NEXT KiB
+	uint32_t wpos;                 // next word of the ring
+	uint64_t bitbuf; uint32_t bitcnt;
+	int32_t bits_left;             // slot bits not yet consumed; negative: the decoder ran past the end (in_len <= VG_GZ_SLOT_MAX: below 2^29)
+	uint32_t ln;
+
+	__device__ __forceinline__ void init(const uint8_t *in_, uint32_t in_len_, uint4 *ring, uint16_t *sym)
+	{
+		ln = threadIdx.x; symp = sym; outg = nullptr;
+		ring16 = ring; ring32 = (uint32_t *)ring;
+		in = in_; in_len = in_len_;
+		skew = (uint32_t)((uintptr_t)in & 15u);
+		src = (const uint4 *)(in - skew);
+		n_vec = (skew + in_len + 15u) >> 4;
+		g0 = 0; wpos = 0; bitbuf = 0; bitcnt = 0; bits_left = 0; pre = make_uint4(0, 0, 0, 0);
+	}
+	__device__ __forceinline__ void set_out(uint16_t *p) { outg = p; }
+	__device__ __forceinline__ uint32_t lane() const { return ln; }
+	__device__ __forceinline__ static uint32_t lanes() { return 64; }
+	__device__ __forceinline__ static void sync() { __syncthreads(); }            // (one wave: a wait for its own LDS traffic, no s_barrier)
+	__device__ __forceinline__ static uint32_t u(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
+	__device__ __forceinline__ static uint64_t u64(uint64_t x) { return (uint64_t)u((uint32_t)x) | (uint64_t)u((uint32_t)(x >> 32)) << 32; }
+	__device__ __forceinline__ static uint64_t ballot(bool p) { return __ballot(p); }
+	__device__ __forceinline__ static uint32_t reduce_add(uint32_t x) { for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o); return x; }
+	__device__ __forceinline__ static uint32_t reduce_max(uint32_t x) { for (int o = 32; o > 0; o >>= 1) x = max(x, (uint32_t)__shfl_xor(x, o)); return x; }
+	__device__ __forceinline__ uint4 load(uint32_t v) const { return v < n_vec ? src[v] : make_uint4(0, 0, 0, 0); }
+	// the reader at slot byte `at` (<= in_len): ring and bit buffer start over
+	__device__ __forceinline__ void seek(uint32_t at)
+	{
+		const uint32_t a = skew + at;
+		g0 = a >> 4;
+		sync();                                                              // (nobody still reads the ring's old contents)
+		ring16[ln] = load(g0 + ln);
+		pre = load(g0 + 64 + ln);
+		sync();
+		wpos = (a & 15u) >> 2;
+		bitbuf = 0; bitcnt = 0;
+		need();
+		const uint32_t lead = (a & 3u) * 8u;                                 // bytes of the first word in front of `at`
+		bitbuf >>= lead; bitcnt -= lead;
+		bits_left = (int32_t)((in_len - at) * 8u);
+	}
+	__device__ __forceinline__ void seek_bit(uint64_t bit)
+	{
+		const uint32_t at = (uint32_t)(bit >> 3);
+		seek(at < in_len ? at : in_len);
+		drop((uint32_t)bit & 7u);
+	}
+	__device__ __forceinline__ uint64_t bitpos() const { return (uint64_t)((int64_t)in_len * 8 - bits_left); }
+	__device__ __forceinline__ void need()
+	{
+		if (bitcnt <= 32) {
+			if (wpos == 256) {                                               // the ring's KiB is used up: the waiting one takes its place
+				sync();
+				ring16[ln] = pre;
+				g0 += 64;
+				pre = load(g0 + 64 + ln);
+				sync();
+				wpos = 0;
+			}
+			const uint32_t w = u(ring32[wpos]);
+			bitbuf |= (uint64_t)w << bitcnt;
+			bitcnt += 32; wpos++;
+		}
+	}
+	__device__ __forceinline__ uint32_t peek() const { return (uint32_t)bitbuf; }
+	__device__ __forceinline__ void drop(uint32_t n) { bitbuf >>= n; bitcnt -= n; bits_left -= (int32_t)n; }
+	__device__ __forceinline__ uint32_t bits(uint32_t n) { const uint32_t v = (uint32_t)bitbuf & ((1u << n) - 1u); drop(n); return v; }
+	__device__ __forceinline__ void align_byte() { drop(bitcnt & 7u); }
+	__device__ __forceinline__ bool overrun() const { return bits_left < 0; }
+	// symbol at output position s of this decode: in the ring, or (s < 0) a placeholder for the window in front of the entry
+	__device__ __forceinline__ uint16_t sym_at(int32_t s) const { return s >= 0 ? symp[(uint32_t)s & (VG_GZ_WINDOW - 1u)] : (uint16_t)(0x8000 + (int32_t)VG_GZ_WINDOW + s); }
+	__device__ __forceinline__ void store(uint32_t o, uint16_t v) { symp[o & (VG_GZ_WINDOW - 1u)] = v; outg[o] = v; }
+	__device__ __forceinline__ void put(uint32_t o, uint8_t b) { if (ln == 0) store(o, b); }
+	// len symbols from `dist` back (dist <= 32768: the ring holds them, or they are placeholders).  dist >= 64: a round of 64 lanes
+	// reads what earlier rounds (or earlier symbols) wrote; a lane that writes the ring slot of position o + j - 32768 has read it
+	// itself before.  dist < 64: the copy replicates a period; every lane reads below o only.
+	__device__ __forceinline__ bool copy(uint32_t o, uint32_t dist, uint32_t len)
+	{
+		sync();
+		if (dist >= 64) {
+			for (uint32_t base = 0; base < len; base += 64) {                // at most 5 rounds (len <= 258), 64 output symbols each
+				const uint32_t j = base + ln;
+				if (j < len) store(o + j, sym_at((int32_t)(o + j) - (int32_t)dist));
+				if (base + 64 < len) sync();
+			}
+		} else {
+			for (uint32_t base = 0; base < len; base += 64) {
+				const uint32_t j = base + ln;
+				if (j < len) store(o + j, sym_at((int32_t)o - (int32_t)dist + (int32_t)(j % dist)));
+			}
+		}
+		return true;
+	}
+	// a stored block's bytes straight from global memory; then the reader starts over behind them
+	__device__ __forceinline__ bool stored_copy(uint32_t o, uint32_t n)
+	{
+		const uint32_t at = in_len - ((uint32_t)bits_left >> 3);             // byte-aligned here, and not past the end (the caller checked)
+		if (n > in_len - at) return false;
+		const uint8_t *s = in + at;
+		sync();
+		for (uint32_t j = ln; j < n; j += 64) store(o + j, s[j]);            // 64 output symbols per round
+		seek(at + n);
+		return true;
+	}
+};
+
+// the device's buffers of one slot (all on the device)
+struct GzSlotDev {
+	const uint8_t *in; uint32_t in_len, n_chunks, chunk_bytes, entry_bit;
+	uint64_t area;                 // staging symbols per chunk: chunk_bytes * ratio
+	VgGzChunkRec *ck; uint16_t *stag; uint64_t *lens, *offs; VgGzSlotRec *rec; uint32_t *counters;     // counters: [0] mismatches, [1] full tests
+};
+
+// grid = chunks.  The record of every chunk starts over; chunk 0's guess is the slot's exact entry.
+__global__ __launch_bounds__(64) void vg_gz_find(GzSlotDev d)
+{
+	__shared__ GzFindShared sh;
+	const uint32_t c = blockIdx.x;
+	if (c >= d.n_chunks) return;
+	GzWaveIO io;
+	io.init(d.in, d.in_len, sh.ring, nullptr);
+	uint32_t tested = 0;
+	uint64_t g = d.entry_bit;
+	if (c) g = vg_gz_find_chunk(io, sh.t, d.in, (uint64_t)d.in_len, (uint64_t)c, (uint64_t)d.chunk_bytes, &tested);
+	if (io.ln == 0) {
+		VgGzChunkRec r = {};
+		r.guess = g; r.entry = g;
+		d.ck[c] = r;
+		if (tested) atomicAdd(&d.counters[1], tested);
+	}
+}
+
+// grid = chunks; a chunk without a guess has nothing to do.  From the guess to the first block boundary at or beyond the next guess.
+__global__ __launch_bounds__(64) void vg_gz_decode(GzSlotDev d)
+{
+	__shared__ GzShared sh;
+	const uint32_t c = blockIdx.x;
+	if (c >= d.n_chunks) return;
+	const uint64_t g = GzWaveIO::u64(d.ck[c].guess);
+	if (g == VG_GZ_NONE) return;
+	GzWaveIO io;
+	io.init(d.in, d.in_len, sh.ring, sh.sym);
+	const uint32_t nx = GzWaveIO::u(vg_gz_next_guess(d.ck, d.n_chunks, c));
+	const uint64_t stop = nx < d.n_chunks ? GzWaveIO::u64(d.ck[nx].guess) : (uint64_t)d.in_len * 8;
+	io.set_out(d.stag + (uint64_t)c * d.area);
+	VgGzChunkRec r = {};
+	r.guess = g;
+	vg_gz_decode_chunk(io, sh.t, g, stop, (uint64_t)(nx - c) * d.area, &r);
+	if (io.ln == 0) {
+		VgGzChunkRec *o = d.ck + c;                                          // (the guess stays: other waves read it meanwhile)
+		o->entry = r.entry; o->exit_bit = r.exit_bit; o->err_bit = r.err_bit; o->out_len = r.out_len; o->rc = r.rc; o->ended = r.ended; o->state = r.state;
+	}
+}
+
+__global__ __launch_bounds__(256) void vg_gz_confirm(GzSlotDev d)
+{
+	const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+	if (c == 0 || c >= d.n_chunks || d.ck[c].guess == VG_GZ_NONE) return;
+	if (!vg_gz_confirm_one(d.ck, c)) atomicAdd(&d.counters[0], 1u);
+}
+
+// one wave: the chain of the slot made final (at once when every chunk was confirmed), its record, the chunks' output lengths
+__global__ __launch_bounds__(64) void vg_gz_repair(GzSlotDev d)
+{
+	__shared__ GzShared sh;
+	GzWaveIO io;
+	io.init(d.in, d.in_len, sh.ring, sh.sym);
+	const bool all_ok = GzWaveIO::u(d.counters[0]) == 0;
+	vg_gz_repair_chain(io, sh.t, d.ck, d.n_chunks, (uint64_t)d.in_len * 8, d.area, d.stag, all_ok, d.rec);
+	__threadfence();                                                         // (lane 0's records, read by the other lanes below)
+	__syncthreads();
+	for (uint32_t c = io.ln; c <= d.n_chunks; c += 64) d.lens[c] = c < d.n_chunks && d.ck[c].state == VG_GZ_ST_VALID ? d.ck[c].out_len : 0;
+	if (io.ln == 0) d.rec->tested = d.counters[1];
+}
+
+// One workgroup, serial over the chunks: the last 32 Ki symbols of every chunk on the chain -> bytes at text[offs[c] + ...], against
+// the window of the 32 KiB in front of the chunk, which is kept in LDS (indexed by text position mod 32 KiB) -- no byte this kernel
+// has written is read back from global memory.  `before` bytes of the member lie in front of text[0] (at most 32 KiB matter).
+constexpr uint32_t GZ_WIN_T = 1024, GZ_WIN_PER = VG_GZ_WINDOW / GZ_WIN_T;
+__global__ __launch_bounds__(GZ_WIN_T) void vg_gz_windows(GzSlotDev d, uint8_t *__restrict__ text, uint32_t before, unsigned long long *__restrict__ bad_bit)
+{
+	__shared__ uint8_t win[VG_GZ_WINDOW];
+	const uint32_t tid = threadIdx.x;
+	for (uint32_t i = tid; i < before; i += GZ_WIN_T) { const int64_t p = (int64_t)i - (int64_t)before; win[(uint64_t)p & (VG_GZ_WINDOW - 1u)] = text[p]; }
+	__syncthreads();
+	for (uint32_t c = 0; c < d.n_chunks; c++) {                              // serial over the chunks, 32 Ki symbols at most of each
+		const uint32_t len = d.lens[c];
+		if (len == 0) continue;
+		const int64_t off = (int64_t)d.offs[c];
+		const uint32_t first = len > VG_GZ_WINDOW ? len - VG_GZ_WINDOW : 0;
+		const uint16_t *s = d.stag + (uint64_t)c * d.area;
+		uint8_t v[GZ_WIN_PER];
+		bool ok = true;
+#pragma unroll
+		for (uint32_t k = 0; k < GZ_WIN_PER; k++) {
+			const uint32_t j = first + k * GZ_WIN_T + tid;
+			v[k] = 0;
+			if (j < len) {
+				const uint16_t y = s[j];
+				if (y < 0x8000u) v[k] = (uint8_t)y;
+				else {
+					const int64_t p = off - (int64_t)VG_GZ_WINDOW + (int64_t)(y - 0x8000u);
+					if (p < -(int64_t)before) ok = false; else v[k] = win[(uint64_t)p & (VG_GZ_WINDOW - 1u)];
+				}
+			}
+		}
+		if (!ok) atomicMin(bad_bit, (unsigned long long)d.ck[c].entry);
+		__syncthreads();                                                     // (every read of the old window is done)
+#pragma unroll
+		for (uint32_t k = 0; k < GZ_WIN_PER; k++) {
+			const uint32_t j = first + k * GZ_WIN_T + tid;
+			if (j < len) { win[(uint64_t)(off + j) & (VG_GZ_WINDOW - 1u)] = v[k]; text[off + j] = v[k]; }
+		}
+		__syncthreads();
+	}
+}
+
+// A full grid over the slot's text: what vg_gz_windows left (all but the last 32 Ki symbols of a chunk) -> bytes.  A placeholder reads
+// the 32 KiB in front of its chunk: written by vg_gz_windows, or text of the slot before.
+constexpr uint32_t GZ_RES_T = 256, GZ_RES_PER = 16;
+__global__ __launch_bounds__(GZ_RES_T) void vg_gz_resolve(GzSlotDev d, uint8_t *__restrict__ text, uint32_t text_len, uint32_t before, unsigned long long *__restrict__ bad_bit)
+{
+	const uint32_t base = blockIdx.x * (GZ_RES_T * GZ_RES_PER) + threadIdx.x;
+	if (base >= text_len) return;
+	// the chunk of text position `base`: the last c with offs[c] <= base
+	uint32_t lo = 0, hi = d.n_chunks;
+	while (hi - lo > 1) { const uint32_t m = lo + ((hi - lo) >> 1); if (d.offs[m] <= base) lo = m; else hi = m; }      // log2(chunks) steps
+	uint32_t c = lo;
+	for (uint32_t k = 0; k < GZ_RES_PER; k++) {
+		const uint32_t i = base + k * GZ_RES_T;
+		if (i >= text_len) break;
+		while (c + 1 < d.n_chunks && d.offs[c + 1] <= i) c++;                // (forward only: at most the chunks of this tile)
+		const uint32_t off = (uint32_t)d.offs[c], len = (uint32_t)d.lens[c], j = i - off;
+		if (j >= len || j + VG_GZ_WINDOW >= len) continue;                   // (the tail is vg_gz_windows')
+		uint8_t b;
+		if (vg_gz_resolve_sym(d.stag[(uint64_t)c * d.area + j], text, (int64_t)off, (int64_t)before, &b)) text[i] = b;
+		else atomicMin(bad_bit, (unsigned long long)d.ck[c].entry);
+	}
+}
+
+// CRC32 of text[0, text_len), tiles of 64 KiB: each thread a slice (vg_crc32_share), the tile's CRC moved to its place by
+// x^(8 * bytes behind it) mod P and folded into *crc by XOR.
+constexpr uint32_t GZ_CRC_TILE = 65536;
+struct GzBlockLanes {
+	__device__ static uint32_t lane() { return threadIdx.x; }
+	__device__ static uint32_t lanes() { return 256; }
+	__device__ static void sync() { __syncthreads(); }
+};
+__global__ __launch_bounds__(256) void vg_gz_crc(const uint8_t *__restrict__ text, uint32_t text_len, uint32_t *__restrict__ crc)
+{
+	__shared__ VgCrcTab tab;
+	__shared__ uint32_t acc;
+	GzBlockLanes l;
+	if (threadIdx.x == 0) acc = 0;
+	vg_crc_tab_build(l, tab);
+	const uint32_t t0 = blockIdx.x * GZ_CRC_TILE, n = min(GZ_CRC_TILE, text_len - t0);
+	uint32_t x = vg_crc32_share(tab, text + t0, n, threadIdx.x, 256);
+	for (int o = 32; o > 0; o >>= 1) x ^= __shfl_xor(x, o);
+	if ((threadIdx.x & 63u) == 0) atomicXor(&acc, x);
+	__syncthreads();
+	if (threadIdx.x == 0) atomicXor(crc, vg_crc_mul(vg_crc_x8n(text_len - t0 - n), acc));
+}
+
+// ------------------------------------------------------------------------------------------------
 // kernels: BAM records framed on the device (vg_bam.h is the record parser; this is its wave policy)
 //
 // A slot's BGZF blocks inflate into bam_raw (BAM_CARRY bytes free in front, like the text buffer); the unfinished record of the
@@ -1496,6 +1790,8 @@ struct vg_index {
 	bool fq_open = false; int fq_prev_slot = -1;
 	BgzfStream bz;                        // the BGZF side of a stream opened with vg_fastq_stream_begin_bgzf
 	bool fq_bgzf = false;                 // the open FASTQ stream takes BGZF bytes
+	struct GzipStream *gz = nullptr;      // the plain-gzip side of a stream opened with vg_fastq_stream_begin_gzip (kept until the next one: stats, checkpoints)
+	bool fq_gzip = false;                 // the open FASTQ stream takes plain gzip bytes
 	uint64_t max_device_bytes = 0;        // the caller's budget for this replica (vg_index_open_ex; 0: the whole device)
 	std::string plan_text;                // what the budget bought: views kept / left out (vg_index_plan)
 	std::string aux_note;                 // ... and what the loader found in the auxiliary rows, if anything
@@ -1603,6 +1899,7 @@ static int alloc_scratch(vg_index *ix, ScratchBuf &b, uint32_t nlanes, uint32_t 
 	return VG_OK;
 }
 
+static void gzip_stream_free(struct GzipStream *gs);
 extern "C" void vg_index_close(vg_index *ix)
 {
 	if (!ix) return;
@@ -1614,6 +1911,7 @@ extern "C" void vg_index_close(vg_index *ix)
 	for (void *p : ix->owned) (void)hipFree(p);
 	ix->arena.destroy();
 	delete ix->packer;
+	gzip_stream_free(ix->gz);
 	if (ix->stream) (void)hipStreamDestroy(ix->stream);
 	if (ix->tail) (void)hipStreamDestroy(ix->tail);
 	if (ix->tail2) (void)hipStreamDestroy(ix->tail2);
@@ -3226,7 +3524,7 @@ extern "C" int vg_fastq_stream_begin_packed(vg_index *ix, int host_threads)
 		HIP_TRY(hipSetDevice(ix->device));
 		if (!ix->packer || ix->packer->threads() != host_threads) { delete ix->packer; ix->packer = nullptr; ix->packer = new vgp::Packer(host_threads); }
 		ix->packer->begin();
-		ix->fq_open = true; ix->fq_packed = true; ix->fq_bgzf = false; ix->fq_prev_slot = -1;
+		ix->fq_open = true; ix->fq_packed = true; ix->fq_bgzf = false; ix->fq_gzip = false; ix->fq_prev_slot = -1;
 		ix->fq_sample = ix->cur_sample;                          // the stream stays with the sample selected now
 		return VG_OK;
 	});
@@ -3256,7 +3554,7 @@ static int push_packed(vg_index *ix, const uint8_t *text, uint64_t nbytes)
 extern "C" int vg_fastq_stream_begin(vg_index *ix)
 {
 	if (!ix) return fail(VG_EINVAL, "null argument");
-	ix->fq_packed = false; ix->fq_bgzf = false;
+	ix->fq_packed = false; ix->fq_bgzf = false; ix->fq_gzip = false;
 	HIP_TRY(hipSetDevice(ix->device));
 	HIP_TRY(hipMemsetAsync(ix->d_fq, 0, sizeof(FqStream), ix->ingest_or_main()));
 	ix->fq_open = true; ix->fq_prev_slot = -1;
@@ -3319,6 +3617,8 @@ static int fq_frame_and_launch(vg_index *ix, Slot &sl, int slot_no, uint64_t nby
 }
 
 static int push_bgzf(vg_index *ix, const uint8_t *data, uint64_t nbytes);
+static int push_gzip(vg_index *ix, const uint8_t *data, uint64_t nbytes);
+static int end_gzip(vg_index *ix);
 
 // One chunk of the stream: a blocking host-to-device copy (the caller's buffer is free when the call returns), then framing
 // and the read loop are only ENQUEUED -- record counts stay on the device until vg_fastq_stream_end.
@@ -3330,6 +3630,7 @@ extern "C" int vg_fastq_stream_push(vg_index *ix, const uint8_t *text, uint64_t 
 	if (nbytes >= (1ull << 31)) return fail(VG_EINVAL, "FASTQ chunk of 2 GiB or more");
 	if (ix->fq_packed) return guarded([&] { return push_packed(ix, text, nbytes); });
 	if (ix->fq_bgzf) return guarded([&] { return push_bgzf(ix, text, nbytes); });
+	if (ix->fq_gzip) return guarded([&] { return push_gzip(ix, text, nbytes); });
 	HIP_TRY(hipSetDevice(ix->device));
 	const int slot_no = ix->next_slot;
 	Slot *slp = nullptr;
@@ -3570,6 +3871,275 @@ extern "C" int vg_bgzf_inflate_device(int device, const uint8_t *bgzf, uint64_t 
 		if (key != ~0ull) { *bad_block_offset = key >> 4; *consumed = key >> 4; (void)fail(VG_EIO, "%s", bz_describe(key).c_str()); }
 		else if (hdr_rc) { *bad_block_offset = bad; (void)fail(VG_EIO, "BGZF block at compressed offset %s: not a BGZF block header", std::to_string(bad).c_str()); }
 		return VG_OK;
+	});
+}
+
+// ---- plain gzip without a handle (vg_gunzip.h: the reference decoder, the chunked stages on the host, and on the device) ----------
+// the sizes of a call: the caller's, and for every field it left 0 (or with no opts at all) the environment's
+static VgGzOpts gz_env_opts(uint64_t nbytes, const vg_gzip_opts *o = nullptr)
+{
+	auto num = [](uint64_t given, const char *name) -> uint64_t { if (given) return given; const char *e = getenv(name); return e && *e ? strtoull(e, nullptr, 10) : 0; };
+	return vg_gz_opts_checked(VgGzOpts{num(o ? o->chunk_bytes : 0, "VG_GZ_CHUNK"), num(o ? o->slot_bytes : 0, "VG_GZ_SLOT"), num(o ? o->max_ratio : 0, "VG_GZ_MAX_RATIO"), num(o ? o->slot_max : 0, "VG_GZ_SLOT_MAX")}, nbytes);
+}
+static int gz_buffer_args(const uint8_t *gz, uint64_t nbytes, uint8_t *text, uint64_t *text_len, uint64_t *consumed, uint64_t *bad_offset)
+{
+	if ((!gz && nbytes) || !text_len || !consumed || !bad_offset || !text) return fail(VG_EINVAL, "null argument");
+	*text_len = 0; *consumed = 0; *bad_offset = UINT64_MAX;
+	return VG_OK;
+}
+// the result of a decoder as the C-ABI gives it: bad data is VG_EIO with the compressed offset and the VG_INF_* text
+static int gz_finish(const VgGzResult &r, uint64_t *text_len, uint64_t *consumed, uint64_t *bad_offset, vg_gzip_stats *stats)
+{
+	static_assert(sizeof(vg_gzip_stats) == sizeof(VgGzStats), "vg_gzip_stats mirrors VgGzStats");
+	*text_len = r.text_len; *consumed = r.consumed; *bad_offset = r.bad_offset;
+	if (stats) memcpy(stats, &r.st, sizeof r.st);
+	if (r.rc == VG_GZ_ECAP) return fail(VG_ETOOBIG, "the text of the gzip members does not fit the caller's buffer");
+	if (r.rc) return fail(VG_EIO, "gzip stream at compressed offset %s: %s", std::to_string(r.bad_offset).c_str(), vg_gunzip_strerror(r.rc));
+	return VG_OK;
+}
+
+extern "C" int vg_gunzip_host(const uint8_t *gz, uint64_t nbytes, uint8_t *text, uint64_t text_cap, uint64_t *text_len, uint64_t *consumed, uint64_t *bad_offset)
+{
+	const int rc = gz_buffer_args(gz, nbytes, text, text_len, consumed, bad_offset);
+	if (rc) return rc;
+	return guarded([&]() -> int {
+		VgGzResult r;
+		vg_gunzip_sequential(gz, nbytes, text, text_cap, &r);
+		return gz_finish(r, text_len, consumed, bad_offset, nullptr);
+	});
+}
+
+extern "C" int vg_gunzip_chunked_host(const uint8_t *gz, uint64_t nbytes, uint8_t *text, uint64_t text_cap, uint64_t *text_len, uint64_t *consumed, uint64_t *bad_offset, vg_gzip_stats *stats, const vg_gzip_opts *opts)
+{
+	const int rc = gz_buffer_args(gz, nbytes, text, text_len, consumed, bad_offset);
+	if (rc) return rc;
+	return guarded([&]() -> int {
+		const VgGzOpts op = gz_env_opts(nbytes, opts);
+		VgGzHostStages be(gz, text, op);
+		VgGzResult r;
+		const int brc = vg_gunzip_chunked(be, gz, nbytes, text_cap, op, &r);
+		if (brc) return brc;
+		return gz_finish(r, text_len, consumed, bad_offset, stats);
+	});
+}
+
+// the stages of a slot as kernels; the host reads back one record per slot and one CRC
+struct GzDeviceStages {
+	VgGzOpts op;
+	DevBuf<uint8_t> d_comp, d_text, d_tmp;
+	DevBuf<VgGzChunkRec> d_ck; DevBuf<uint16_t> d_stag; DevBuf<uint64_t> d_lens, d_offs; DevBuf<VgGzSlotRec> d_rec; DevBuf<uint32_t> d_cnt; DevBuf<unsigned long long> d_bad;
+	GzSlotDev d{};
+	size_t tmp_bytes = 0;
+	hipStream_t s = nullptr;                                             // where the stages run (a stream of a handle; null: the default stream)
+	static constexpr uint64_t TEXT_PAD = 64;
+
+	int prepare(const uint8_t *gz, uint64_t nbytes, uint64_t text_cap)
+	{
+		int rc;
+		if ((rc = d_comp.reserve(nbytes + 64, "gzip bytes")) || (rc = d_text.reserve(text_cap + TEXT_PAD, "inflated text")) || (rc = d_rec.reserve(1, "gzip slot record"))
+		    || (rc = d_cnt.reserve(4, "gzip counters")) || (rc = d_bad.reserve(1, "gzip verdict"))) return rc;
+		HIP_TRY(hipMemcpy(d_comp.p, gz, nbytes, hipMemcpyHostToDevice));
+		d.rec = d_rec.p; d.counters = d_cnt.p;
+		d.chunk_bytes = (uint32_t)op.chunk_bytes; d.area = op.chunk_bytes * op.max_ratio;
+		return slot_buffers((op.slot_bytes + op.chunk_bytes - 1) / op.chunk_bytes);
+	}
+	// the buffers that follow a slot's chunk count (grow-only: a slot is longer than slot_bytes only when a block did not fit it)
+	int slot_buffers(uint64_t n_chunks)
+	{
+		int rc;
+		tmp_bytes = std::max(tmp_bytes, vg_dev_scan_temp_bytes(1, n_chunks + 1));
+		if ((rc = d_tmp.reserve(tmp_bytes, "scan scratch")) || (rc = d_ck.reserve(n_chunks, "gzip chunk records")) || (rc = d_stag.reserve(n_chunks * d.area, "gzip symbol staging"))
+		    || (rc = d_lens.reserve(n_chunks + 1, "gzip chunk lengths")) || (rc = d_offs.reserve(n_chunks + 1, "gzip chunk offsets"))) return rc;
+		d.ck = d_ck.p; d.stag = d_stag.p; d.lens = d_lens.p; d.offs = d_offs.p;
+		return VG_OK;
+	}
+	int chain(uint64_t in_off, uint64_t in_len, uint32_t entry_bit, VgGzSlotRec *rec, uint64_t *text_len)
+	{
+		d.in = d_comp.p + in_off; d.in_len = (uint32_t)in_len; d.entry_bit = entry_bit;
+		d.n_chunks = (uint32_t)((in_len + op.chunk_bytes - 1) / op.chunk_bytes);
+		const int brc = slot_buffers(d.n_chunks);
+		if (brc) return brc;
+		HIP_TRY(hipMemsetAsync(d_cnt.p, 0, 4 * sizeof(uint32_t), s));
+		vg_gz_find<<<d.n_chunks, 64, 0, s>>>(d);
+		vg_gz_decode<<<d.n_chunks, 64, 0, s>>>(d);
+		vg_gz_confirm<<<(d.n_chunks + 255) / 256, 256, 0, s>>>(d);
+		vg_gz_repair<<<1, 64, 0, s>>>(d);
+		HIP_TRY(hipGetLastError());
+		const int se = vg_dev_exclusive_scan_u64(d.lens, d.offs, d.n_chunks + 1, s, d_tmp.p, tmp_bytes);
+		if (se) return fail(VG_ENODEV, "scan of the gzip chunk lengths: %s", hipGetErrorString((hipError_t)se));
+		HIP_TRY(hipMemcpyAsync(rec, d_rec.p, sizeof *rec, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipMemcpyAsync(text_len, d.offs + d.n_chunks, sizeof *text_len, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		return VG_OK;
+	}
+	int resolve(uint64_t text_off, uint64_t before, uint64_t text_len, uint32_t *crc, uint64_t *bad_bit) { return resolve_at(d_text.p + text_off, before, text_len, crc, bad_bit); }
+	// the slot's symbols -> tx[0, text_len); `before` bytes of the member's text lie in front of tx
+	int resolve_at(uint8_t *tx, uint64_t before, uint64_t text_len, uint32_t *crc, uint64_t *bad_bit)
+	{
+		*crc = 0;
+		if (text_len == 0) return VG_OK;
+		HIP_TRY(hipMemsetAsync(d_bad.p, 0xff, sizeof(unsigned long long), s));
+		HIP_TRY(hipMemsetAsync(d_cnt.p + 2, 0, sizeof(uint32_t), s));
+		vg_gz_windows<<<1, GZ_WIN_T, 0, s>>>(d, tx, (uint32_t)before, d_bad.p);
+		vg_gz_resolve<<<(unsigned)((text_len + GZ_RES_T * GZ_RES_PER - 1) / (GZ_RES_T * GZ_RES_PER)), GZ_RES_T, 0, s>>>(d, tx, (uint32_t)text_len, (uint32_t)before, d_bad.p);
+		vg_gz_crc<<<(unsigned)((text_len + GZ_CRC_TILE - 1) / GZ_CRC_TILE), 256, 0, s>>>(tx, (uint32_t)text_len, d_cnt.p + 2);
+		HIP_TRY(hipGetLastError());
+		unsigned long long bad = ~0ull;
+		HIP_TRY(hipMemcpyAsync(&bad, d_bad.p, sizeof bad, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipMemcpyAsync(crc, d_cnt.p + 2, sizeof *crc, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		*bad_bit = bad;
+		return VG_OK;
+	}
+};
+
+extern "C" int vg_gunzip_device(int device, const uint8_t *gz, uint64_t nbytes, uint8_t *text, uint64_t text_cap, uint64_t *text_len, uint64_t *consumed, uint64_t *bad_offset, vg_gzip_stats *stats, const vg_gzip_opts *opts)
+{
+	int rc = gz_buffer_args(gz, nbytes, text, text_len, consumed, bad_offset);
+	if (rc) return rc;
+	return guarded([&]() -> int {
+		VgGzResult r;
+		if (nbytes) {
+			HIP_TRY(hipSetDevice(device));
+			GzDeviceStages be;
+			be.op = gz_env_opts(nbytes, opts);
+			if ((rc = be.prepare(gz, nbytes, text_cap))) return rc;
+			const auto t0 = std::chrono::steady_clock::now();
+			if ((rc = vg_gunzip_chunked(be, gz, nbytes, text_cap, be.op, &r))) return rc;
+			HIP_TRY(hipDeviceSynchronize());
+			if (getenv("VG_VERBOSE")) {                                 // the stages of all slots, without the copies of the whole file in and out
+				const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+				fprintf(stderr, "[vargeno_hip] gzip inflate: chunk %lu slot %lu ratio %lu: %lu chunks, %lu guessed, %lu repaired, %.3f ms, %.2f GB/s text, %.2f GB/s compressed\n", (unsigned long)be.op.chunk_bytes,
+				        (unsigned long)be.op.slot_bytes, (unsigned long)be.op.max_ratio, (unsigned long)r.st.chunks, (unsigned long)r.st.guessed, (unsigned long)r.st.repaired, ms, r.text_len / 1e6 / ms, r.consumed / 1e6 / ms);
+			}
+			if (r.text_len) HIP_TRY(hipMemcpy(text, be.d_text.p, r.text_len, hipMemcpyDeviceToHost));
+		}
+		return gz_finish(r, text_len, consumed, bad_offset, stats);
+	});
+}
+
+// ---- plain gzip streams: compressed bytes cut anywhere cross the link slot by slot, the stages above write a slot's text, and the
+// text route's framing takes it from there (fq_frame_and_launch, as it is).  VgGzPush (vg_gunzip.h) decides what a slot is and
+// carries the incomplete tail block on the host; per slot the host reads back one record (text length, exit, verdict, counts) and
+// one CRC.  The text of a slot is resolved into d_text behind a copy of the window -- the last 32 KiB of the member's text so far,
+// kept in d_win (32 KiB device to device in, 32 KiB out: the slot's own text buffer has the carry of the framing in front of it) --
+// and copied device to device into the batch slot's fq_text.  Everything is enqueued on the ingest stream, in order.
+struct GzipStream {
+	vg_index *ix;
+	GzDeviceStages g;
+	DevBuf<uint8_t> d_win;
+	VgGzPush<GzipStream> drv;
+	GzipStream(vg_index *ix_, const VgGzOpts &op) : ix(ix_), drv(*this, op) { g.op = op; }
+	int init()
+	{
+		int rc;
+		if ((rc = g.d_rec.reserve(1, "gzip slot record")) || (rc = g.d_cnt.reserve(4, "gzip counters")) || (rc = g.d_bad.reserve(1, "gzip verdict")) || (rc = d_win.reserve(VG_GZ_WINDOW, "gzip window"))) return rc;
+		g.s = ix->ingest_or_main();
+		g.d.rec = g.d_rec.p; g.d.counters = g.d_cnt.p;
+		g.d.chunk_bytes = (uint32_t)g.op.chunk_bytes; g.d.area = g.op.chunk_bytes * g.op.max_ratio;
+		return VG_OK;
+	}
+	int chain_at(const uint8_t *in, uint64_t in_len, uint32_t entry_bit, VgGzSlotRec *rec, uint64_t *text_len)
+	{
+		int rc;
+		if ((rc = g.d_comp.reserve(in_len + 64, "gzip bytes"))) return rc;
+		HIP_TRY(hipMemcpyAsync(g.d_comp.p, in, in_len, hipMemcpyHostToDevice, g.s));
+		return g.chain(0, in_len, entry_bit, rec, text_len);
+	}
+	int resolve_next(uint64_t before, uint64_t text_len, uint32_t *crc, uint64_t *bad_bit)
+	{
+		*crc = 0;
+		if (text_len == 0) return VG_OK;
+		if (text_len >= (1ull << 31)) return fail(VG_ETOOBIG, "a gzip slot's text of 2 GiB or more");
+		int rc;
+		if ((rc = g.d_text.reserve(VG_GZ_WINDOW + text_len + GzDeviceStages::TEXT_PAD, "inflated text"))) return rc;
+		uint8_t *tx = g.d_text.p + VG_GZ_WINDOW;
+		if (before) HIP_TRY(hipMemcpyAsync(tx - before, d_win.p + VG_GZ_WINDOW - before, before, hipMemcpyDeviceToDevice, g.s));
+		if ((rc = g.resolve_at(tx, before, text_len, crc, bad_bit)) || *bad_bit != VG_GZ_NONE) return rc;
+		const uint64_t keep = std::min<uint64_t>(VG_GZ_WINDOW, before + text_len);   // the window of the next slot
+		HIP_TRY(hipMemcpyAsync(d_win.p + VG_GZ_WINDOW - keep, tx + text_len - keep, keep, hipMemcpyDeviceToDevice, g.s));
+		const int slot_no = ix->next_slot;
+		Slot *slp = nullptr;
+		if ((rc = acquire_slot(ix, &slp, ix->fq_sample))) return rc;
+		Slot &sl = *slp;
+		if ((rc = fq_reserve(sl, text_len))) return rc;
+		HIP_TRY(hipMemcpyAsync(sl.fq_text.p + FQ_CARRY, tx, text_len, hipMemcpyDeviceToDevice, g.s));
+		return fq_frame_and_launch(ix, sl, slot_no, text_len, nullptr);
+	}
+	// (enqueued only: the driver runs the slot's chain next, whose read-back waits for the stream; dst is a checkpoint's own heap
+	// block, which stays where it is, and nobody reads it before vg_fastq_stream_end has returned)
+	int window(uint8_t *dst, uint64_t before)
+	{
+		HIP_TRY(hipMemcpyAsync(dst, d_win.p + VG_GZ_WINDOW - before, before, hipMemcpyDeviceToHost, g.s));
+		return VG_OK;
+	}
+};
+static void gzip_stream_free(GzipStream *gs) { delete gs; }
+
+extern "C" int vg_fastq_stream_begin_gzip(vg_index *ix)
+{
+	if (!ix) return fail(VG_EINVAL, "null argument");
+	return guarded([&]() -> int {
+		int rc = vg_fastq_stream_begin(ix);
+		if (rc) return rc;
+		ix->fq_open = false;                                              // (until the gzip side stands)
+		delete ix->gz; ix->gz = nullptr;
+		ix->gz = new GzipStream(ix, gz_env_opts(UINT64_MAX));
+		if ((rc = ix->gz->init())) return rc;
+		ix->fq_open = true; ix->fq_gzip = true;
+		return VG_OK;
+	});
+}
+static int push_gzip(vg_index *ix, const uint8_t *data, uint64_t nbytes)
+{
+	HIP_TRY(hipSetDevice(ix->device));
+	return ix->gz->drv.push(data, nbytes);                                 // (bad data or a refused slot stops the decoder: vg_fastq_stream_end says which)
+}
+static int end_gzip(vg_index *ix)
+{
+	HIP_TRY(hipSetDevice(ix->device));
+	return ix->gz->drv.end();
+}
+static int gzip_verdict(vg_index *ix, int *refused)
+{
+	const VgGzResult &r = ix->gz->drv.r;
+	if (r.rc) return fail(VG_EIO, "gzip stream at compressed offset %s: %s", std::to_string(r.bad_offset).c_str(), vg_gunzip_strerror(r.rc));
+	if (refused && r.st.slots_refused) *refused = 1;
+	return VG_OK;
+}
+extern "C" int vg_gzip_stream_stats(vg_index *ix, vg_gzip_stats *stats)
+{
+	if (!ix || !stats) return fail(VG_EINVAL, "null argument");
+	if (!ix->gz) return fail(VG_EINVAL, "vg_gzip_stream_stats without vg_fastq_stream_begin_gzip");
+	memcpy(stats, &ix->gz->drv.r.st, sizeof *stats);
+	return VG_OK;
+}
+extern "C" int vg_fastq_stream_gzip_checkpoint(vg_index *ix, uint64_t text_offset, uint64_t *comp_bit_offset, uint64_t *ckpt_text_offset, uint8_t *window, uint32_t *window_len)
+{
+	if (!ix || !comp_bit_offset || !ckpt_text_offset || !window || !window_len) return fail(VG_EINVAL, "null argument");
+	if (!ix->gz) return fail(VG_EINVAL, "vg_fastq_stream_gzip_checkpoint without vg_fastq_stream_begin_gzip");
+	*comp_bit_offset = 0; *ckpt_text_offset = 0; *window_len = 0;          // no slot was entered: the file's first byte
+	if (const VgGzCheckpoint *c = ix->gz->drv.checkpoint(text_offset)) {
+		*comp_bit_offset = c->comp_bit; *ckpt_text_offset = c->text_off; *window_len = (uint32_t)c->window.size();
+		if (!c->window.empty()) memcpy(window, c->window.data(), c->window.size());
+	}
+	return VG_OK;
+}
+
+// the push driver over the host stages, `push_bytes` at a time: what a gzip stream decides, with no device (the CPU suite)
+extern "C" int vg_gunzip_pushed_host(const uint8_t *gz, uint64_t nbytes, uint64_t push_bytes, uint8_t *text, uint64_t text_cap, uint64_t *text_len, uint64_t *consumed, uint64_t *bad_offset, vg_gzip_stats *stats, const vg_gzip_opts *opts)
+{
+	const int rc = gz_buffer_args(gz, nbytes, text, text_len, consumed, bad_offset);
+	if (rc) return rc;
+	if (!push_bytes) return fail(VG_EINVAL, "pushes of no bytes");
+	return guarded([&]() -> int {
+		VgGzHostPushStages be(gz_env_opts(UINT64_MAX, opts));
+		VgGzPush<VgGzHostPushStages> drv(be, be.st.op);
+		for (uint64_t at = 0; at < nbytes; at += push_bytes) (void)drv.push(gz + at, std::min(push_bytes, nbytes - at));
+		(void)drv.end();
+		if (drv.r.text_len > text_cap) return fail(VG_ETOOBIG, "the text of the gzip members does not fit the caller's buffer");
+		if (drv.r.text_len) memcpy(text, be.out.data(), drv.r.text_len);
+		return gz_finish(drv.r, text_len, consumed, bad_offset, stats);
 	});
 }
 
@@ -3841,6 +4411,7 @@ static int fq_collect(vg_index *ix, bool drain, uint64_t *n_records, uint64_t *c
 	return VG_OK;
 }
 
+static int gzip_verdict(vg_index *ix, int *refused);
 extern "C" int vg_fastq_stream_end(vg_index *ix, uint64_t *n_records, uint64_t *consumed, uint64_t *last_record_start, int *refused)
 {
 	if (!ix) return fail(VG_EINVAL, "null argument");
@@ -3856,8 +4427,15 @@ extern "C" int vg_fastq_stream_end(vg_index *ix, uint64_t *n_records, uint64_t *
 		if (refused) *refused = ix->packer->poisoned() ? 1 : 0;
 		return VG_OK;
 	}
+	const bool gzip = ix->fq_gzip;
+	ix->fq_gzip = false;
+	if (gzip) {                                                          // what waits in the carry is decoded and framed first
+		const int grc = guarded([&] { return end_gzip(ix); });
+		if (grc) return grc;
+	}
 	FqStream h;
 	int rc = fq_collect(ix, true, n_records, consumed, last_record_start, refused, &h);
+	if (rc == VG_OK && gzip) return gzip_verdict(ix, refused);
 	if (rc || !ix->fq_bgzf) return rc;
 	ix->fq_bgzf = false;
 	return guarded([&]() -> int {

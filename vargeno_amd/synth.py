@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import io
 import os
+import struct
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -418,6 +419,129 @@ def bgzf_bytes(text, block=65280, level=6, strategy=None, flush_at=None, eof=Tru
     if eof:
         out.append(BGZF_EOF)
     return b"".join(out)
+
+
+_LEN_BASE = [3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258]
+_LEN_EXT = [0] * 8 + [1] * 4 + [2] * 4 + [3] * 4 + [4] * 4 + [5] * 4 + [0]
+_DIST_BASE = [1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577]
+_DIST_EXT = [0, 0, 0, 0] + [k for k in range(1, 14) for _ in (0, 1)]
+
+
+def _fixed_block(ops, final=False):
+    """One fixed-Huffman DEFLATE block (RFC 1951 3.2.6) from ops: an int is a literal byte, (length, distance) a back-reference --
+    any length 3..258 and distance 1..32768, also those zlib's deflate never writes.  Returns (bits as a list of 0/1)."""
+    bits = []
+
+    def put(value, n):                       # n bits, least significant first (header fields, extra bits)
+        bits.extend((value >> i) & 1 for i in range(n))
+
+    def code(value, n):                      # a Huffman code: most significant bit first
+        bits.extend((value >> i) & 1 for i in range(n - 1, -1, -1))
+
+    def lit(sym):
+        if sym < 144:
+            code(0x30 + sym, 8)
+        elif sym < 256:
+            code(0x190 + sym - 144, 9)
+        elif sym < 280:
+            code(sym - 256, 7)
+        else:
+            code(0xc0 + sym - 280, 8)
+
+    put(1 if final else 0, 1)
+    put(1, 2)
+    for op in ops:
+        if isinstance(op, int):
+            lit(op)
+            continue
+        length, dist = op
+        assert 3 <= length <= 258 and 1 <= dist <= 32768
+        c = max(k for k in range(29) if _LEN_BASE[k] <= length)
+        lit(257 + c)
+        put(length - _LEN_BASE[c], _LEN_EXT[c])
+        d = max(k for k in range(30) if _DIST_BASE[k] <= dist)
+        code(d, 5)
+        put(dist - _DIST_BASE[d], _DIST_EXT[d])
+    lit(256)
+    return bits
+
+
+def gzip_member(raw, text_crc, text_len, name=None, extra=None, comment=None, hcrc=False):
+    """One gzip member (RFC 1952) around a raw DEFLATE stream: optional FEXTRA / FNAME / FCOMMENT / FHCRC fields."""
+    import zlib
+
+    flg = (4 if extra is not None else 0) | (8 if name is not None else 0) | (16 if comment is not None else 0) | (2 if hcrc else 0)
+    h = bytes([0x1f, 0x8b, 8, flg, 0, 0, 0, 0, 0, 255])
+    if extra is not None:
+        h += struct.pack("<H", len(extra)) + bytes(extra)
+    if name is not None:
+        h += bytes(name) + b"\0"
+    if comment is not None:
+        h += bytes(comment) + b"\0"
+    if hcrc:
+        h += struct.pack("<H", zlib.crc32(h) & 0xffff)
+    return h + bytes(raw) + struct.pack("<II", text_crc & 0xffffffff, text_len & 0xffffffff)
+
+
+def gzip_bytes(text=b"", level=6, mem_level=8, strategy=None, flush=None, flush_every=10000, segments=None, **header):
+    """`text` as one plain gzip member, on Python's zlib (raw deflate, wbits=-15).  flush: zlib.Z_SYNC_FLUSH / Z_FULL_FLUSH after
+    every `flush_every` bytes of text.  header: name / extra / comment / hcrc for gzip_member.
+    segments: instead of `text`, raw DEFLATE pieces joined at byte boundaries -- ("deflate", bytes[, level]) a fresh compressor's
+    output ended by a full flush (no reference leaves the piece); ("stored", bytes) one stored block of at most 65535 bytes;
+    ("fixed", ops) one fixed-Huffman block from literals and (length, distance) pairs (_fixed_block), padded to a byte boundary by
+    an empty stored block; ("pad", n, origin) a stored block of b"A" sized so that the NEXT piece's first payload byte lies at a
+    file offset that is `origin` mod n (n <= 65535; the next piece is a stored block: 5 bytes of header).  An empty final stored
+    block ends the stream.  Returns the member's bytes; with segments, (bytes, text, {index of the piece: file offset of its first byte})."""
+    import zlib
+
+    st = zlib.Z_DEFAULT_STRATEGY if strategy is None else strategy
+    if segments is None:
+        text = bytes(text)
+        co = zlib.compressobj(level, zlib.DEFLATED, -15, mem_level, st)
+        if flush is None:
+            raw = co.compress(text) + co.flush()
+        else:
+            raw = b"".join(co.compress(text[i:i + flush_every]) + co.flush(flush) for i in range(0, len(text), flush_every)) + co.flush()
+        return gzip_member(raw, zlib.crc32(text), len(text), **header)
+
+    def stored(payload, final=False):
+        assert len(payload) <= 65535
+        return bytes([1 if final else 0]) + struct.pack("<HH", len(payload), len(payload) ^ 0xffff) + bytes(payload)
+
+    hdr_len = len(gzip_member(b"", 0, 0, **header)) - 8
+    raw, out, where = b"", b"", {}
+    for i, seg in enumerate(segments):
+        where[i] = hdr_len + len(raw)
+        kind = seg[0]
+        if kind == "deflate":
+            co = zlib.compressobj(seg[2] if len(seg) > 2 else level, zlib.DEFLATED, -15, mem_level, st)
+            raw += co.compress(bytes(seg[1])) + co.flush(zlib.Z_FULL_FLUSH)
+            out += bytes(seg[1])
+        elif kind == "stored":
+            raw += stored(seg[1])
+            out += bytes(seg[1])
+        elif kind == "pad":
+            n, origin = seg[1], seg[2]
+            fill = (origin - (hdr_len + len(raw) + 5 + 5)) % n
+            raw += stored(b"A" * fill)
+            out += b"A" * fill
+        elif kind == "fixed":
+            bits = _fixed_block(seg[1])
+            bits += [0] * 3                                    # an empty stored block's header: BFINAL 0, BTYPE 0; then the padding
+            bits += [0] * (-len(bits) % 8)
+            raw += bytes(sum(b << k for k, b in enumerate(bits[j:j + 8])) for j in range(0, len(bits), 8)) + struct.pack("<HH", 0, 0xffff)
+            out = bytearray(out)
+            for op in seg[1]:
+                if isinstance(op, int):
+                    out.append(op)
+                else:
+                    for _ in range(op[0]):
+                        out.append(out[-op[1]])
+            out = bytes(out)
+        else:
+            raise ValueError(kind)
+    raw += stored(b"", final=True)
+    return gzip_member(raw, zlib.crc32(out), len(out), **header), out, where
 
 
 # ----------------------------------------------------------------------------- named data sets
