@@ -404,7 +404,36 @@ int  vg_sample_calls_fetch(vg_index *ix, uint8_t *gt, int32_t *gq, uint64_t *n_e
 int  vg_call_device(int device, const uint8_t *ref_cnt, const uint8_t *alt_cnt, const uint8_t *ref_freq, const uint8_t *alt_freq,
                     uint64_t n, double guard, uint8_t *gt, int32_t *gq, uint64_t *n_escaped);
 
-/* Sample planes: several samples against ONE resident index.  The reference genotypes one sample per process: the counters it hands
+/* The genotype matrix of a cohort and its first consumer, the pairwise sample table: are two samples the same individual, swapped,
+ * related?  No reference counterpart (the reference genotypes one sample per process).  The rules live in csrc/vg_pairs.h, one
+ * statement for the host loop and the kernels: a call (gt, gq) of vg_sample_calls_fetch is COUNTED iff gt != 0 && gq >= min_gq; a
+ * counted call is of class R (gt 1), A (gt 2) or H (gt 3), C = R | H | A; a sample is three bit planes of ceil(n_sites / 64) words.
+ * The table is counts[i][j][5] for ALL i, j, in the order n = |Ci & Cj|, ibs0 = |Ri&Aj | Ai&Rj|, ibs2 = |Ri&Rj | Hi&Hj | Ai&Aj|,
+ * hethet = |Hi & Hj|, het_i = |Hi & Cj| ([j][i][4] is "j het where i is counted"); the diagonal is the sample with itself:
+ * n = its counted sites = ibs2, ibs0 = 0, hethet = het_i = its hets.  Integer sums: the result is exact whatever the launch.
+ * A vg_gmatrix lives on one device and is tied to no vg_index; a handle is thread-compatible.
+ *   vg_gmatrix_create        planes for n_samples samples (1 .. 16 384; 0: VG_EINVAL, more: VG_ETOOBIG) of n_sites sites (below 2^32,
+ *                            else VG_EINVAL; 0 is allowed: every count is 0), the n_samples^2 x 40-byte result (10.7 GB at the cap)
+ *                            and one sample's columns of staging (5 bytes per site).  VG_ENOMEM leaves nothing behind
+ *   vg_gmatrix_set           one sample's final gt / gq columns (host arrays of n_sites entries, free again on return) packed into its
+ *                            planes by a kernel.  A sample never set is all-missing; setting a sample again replaces it.  VG_EINVAL:
+ *                            a null pointer, a sample out of range -- the matrix stays as it was
+ *   vg_gmatrix_pairs         the table into counts[n_samples * n_samples * 5] (host memory).  Synchronous.  words_per_block: site
+ *                            words one workgroup of the pair kernel counts (the site range is a grid dimension, so that a few
+ *                            samples still make many workgroups); 0 = the default, 1024; made larger where the grid would pass
+ *                            65 535 blocks, and at most 2^24.  With VG_VERBOSE set the call prints the kernels' own time and rate
+ *   vg_gmatrix_device_bytes  device memory the matrix holds (0 for a null handle)
+ *   vg_pairs_host            the same table by the same header on `threads` host threads (< 1: one), from gt / gq laid out
+ *                            [n_samples][n_sites], sample-major.  Touches no device */
+typedef struct vg_gmatrix vg_gmatrix;
+int  vg_gmatrix_create(int device, uint64_t n_sites, uint32_t n_samples, vg_gmatrix **out);
+int  vg_gmatrix_set(vg_gmatrix *gm, uint32_t sample, const uint8_t *gt, const int32_t *gq, int32_t min_gq);
+int  vg_gmatrix_pairs(vg_gmatrix *gm, uint64_t words_per_block, uint64_t *counts);
+uint64_t vg_gmatrix_device_bytes(const vg_gmatrix *gm);
+void vg_gmatrix_destroy(vg_gmatrix *gm);
+int  vg_pairs_host(const uint8_t *gt, const int32_t *gq, uint64_t n_sites, uint32_t n_samples, int32_t min_gq, int threads, uint64_t *counts);
+
+/* Sample planes: several samples against ONE resident index. The reference genotypes one sample per process: the counters it hands
  * to the caller (qv.cc:1573-1626) are the only per-sample state of its read loop, the dictionaries are read-only.  A PLANE is that
  * state for one sample on the device: the exact sums (8 bytes per SNP site) and the wave kernel's base-indexed counters (16 bytes
  * per site, + 16): 24 * vg_num_sites + 16 bytes of HBM per plane -- 240 MB at 10 M sites --, taken outside the handle's plan and

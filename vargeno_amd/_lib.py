@@ -27,7 +27,8 @@ SYMBOLS = ["vg_last_error", "vg_build_id", "vg_device_count", "vg_device_memory"
            "vg_sample_calls_fetch", "vg_call_device",
            "vg_fastq_stream_begin_bam", "vg_bam_stream_stats", "vg_bam_frame_device", "vg_bam_to_fastq_host",
            "vg_gunzip_host", "vg_gunzip_device", "vg_gunzip_chunked_host", "vg_gunzip_pushed_host",
-           "vg_fastq_stream_begin_gzip", "vg_gzip_stream_stats", "vg_fastq_stream_gzip_checkpoint"]
+           "vg_fastq_stream_begin_gzip", "vg_gzip_stream_stats", "vg_fastq_stream_gzip_checkpoint",
+           "vg_gmatrix_create", "vg_gmatrix_set", "vg_gmatrix_pairs", "vg_gmatrix_device_bytes", "vg_gmatrix_destroy", "vg_pairs_host"]
 
 GZIP_STAT_FIELDS = ["members", "chunks", "guessed", "confirmed", "repaired", "tested", "slots_refused", "resume_bit"]
 
@@ -191,6 +192,14 @@ def lib():
         L.vg_bam_to_fastq_host.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.vg_sample_calls_fetch.argtypes = [vp, vp, vp, C.POINTER(C.c_uint64)]
         L.vg_call_device.argtypes = [C.c_int, vp, vp, vp, vp, C.c_uint64, C.c_double, vp, vp, C.POINTER(C.c_uint64)]
+        L.vg_gmatrix_create.argtypes = [C.c_int, C.c_uint64, C.c_uint32, C.POINTER(vp)]
+        L.vg_gmatrix_set.argtypes = [vp, C.c_uint32, vp, vp, C.c_int32]
+        L.vg_gmatrix_pairs.argtypes = [vp, C.c_uint64, vp]
+        L.vg_gmatrix_device_bytes.argtypes = [vp]
+        L.vg_gmatrix_device_bytes.restype = C.c_uint64
+        L.vg_gmatrix_destroy.argtypes = [vp]
+        L.vg_gmatrix_destroy.restype = None
+        L.vg_pairs_host.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_int32, C.c_int, vp]
         # The library is a build product that travels next to its sources (not in git): refuse a stale one.  Its build id is the
         # sha256 of the sources it was compiled from (csrc/Makefile); VARGENO_HIP_LIB (A/B variants) opts out.
         if not os.environ.get("VARGENO_HIP_LIB"):

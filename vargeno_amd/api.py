@@ -540,6 +540,72 @@ def call_device(ref_cnt, alt_cnt, ref_freq, alt_freq, device=0, guard=0.0):
     return gt, gq, int(esc.value)
 
 
+# the pair kernel's launch: a workgroup owns a PAIR_TILE x PAIR_TILE tile of sample pairs and, unless the caller says otherwise,
+# PAIR_WORDS_DEFAULT 64-site words; counts[i, j] = (n, ibs0, ibs2, hethet, het_i), PAIR_COUNTERS of them
+PAIR_TILE, PAIR_WORDS_DEFAULT, PAIR_COUNTERS, PAIR_MAX_SAMPLES = 32, 1024, 5, 16384
+
+
+class GenotypeMatrix:
+    """The calls of a cohort as bit planes on a device (vg_gmatrix_*), and the pairwise sample table over them."""
+
+    def __init__(self, n_sites, n_samples, device=0):
+        self._h = None
+        self.n_sites, self.n_samples = int(n_sites), int(n_samples)
+        if self.n_sites < 0 or self.n_samples < 0:
+            raise ValueError("GenotypeMatrix: negative size")
+        h = C.c_void_p()
+        check(lib().vg_gmatrix_create(int(device), self.n_sites, min(self.n_samples, 2 ** 32 - 1), C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if self._h:
+            lib().vg_gmatrix_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def device_bytes(self):
+        return int(lib().vg_gmatrix_device_bytes(self._h))
+
+    def set(self, sample, gt, gq, min_gq=0):
+        """One sample's final calls (as GenoIndex.calls() returns them); a call counts iff gt != 0 and gq >= min_gq."""
+        gt = np.ascontiguousarray(gt, dtype=np.uint8)
+        gq = np.ascontiguousarray(gq, dtype=np.int32)
+        if gt.shape != (self.n_sites,) or gq.shape != (self.n_sites,):
+            raise ValueError("GenotypeMatrix.set: gt and gq hold one entry per site")
+        if not 0 <= int(sample) < 2 ** 32:
+            raise ValueError("GenotypeMatrix.set: sample out of range")
+        check(lib().vg_gmatrix_set(self._h, int(sample), _ptr(gt), _ptr(gq), int(min_gq)))
+
+    def pairs(self, words_per_block=0):
+        """uint64[N, N, 5]: (n, ibs0, ibs2, hethet, het_i) of every ordered pair of samples."""
+        out = np.empty((self.n_samples, self.n_samples, PAIR_COUNTERS), dtype=np.uint64)
+        check(lib().vg_gmatrix_pairs(self._h, int(words_per_block), _ptr(out)))
+        return out
+
+
+def pairs_host(gt, gq, min_gq=0, threads=1):
+    """The same table by the host loop (vg_pairs_host; no device): gt, gq are [n_samples, n_sites]."""
+    gt = np.ascontiguousarray(gt, dtype=np.uint8)
+    gq = np.ascontiguousarray(gq, dtype=np.int32)
+    if gt.ndim != 2 or gt.shape != gq.shape:
+        raise ValueError("pairs_host: gt and gq are [n_samples, n_sites]")
+    out = np.empty((gt.shape[0], gt.shape[0], PAIR_COUNTERS), dtype=np.uint64)
+    check(lib().vg_pairs_host(_ptr(gt), _ptr(gq), gt.shape[1], gt.shape[0], int(min_gq), int(threads), _ptr(out)))
+    return out
+
+
 def pinned_buffer(nbytes):
     """Page-locked host memory: (numpy uint8 view, owner).  Keep `owner` alive as long as the view is used."""
     p = lib().vg_host_alloc_pinned(int(nbytes))

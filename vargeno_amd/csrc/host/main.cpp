@@ -33,13 +33,21 @@
 //   VARGENO_CALLER=device|host  geno, cohort: where the genotypes are called -- `device`: by the caller kernel, where the counters live
 //                         (vg_sample_calls_fetch: 2 bytes per site cross the link; no device memory for it: the host loop after all, one
 //                         line under VARGENO_VERBOSE); `host` (the default): the host loop over the fetched counters.  `joint` always asks the device
+//   VARGENO_JOINT_PAIRS=path  joint: after the joint VCF, and only if no sample failed, the pairwise sample table of the cohort (same individual?
+//                         swapped? related?) goes to <path>: the samples' calls are packed into a genotype matrix on replica 0's device and
+//                         counted pair by pair there (vg_gmatrix_*); no device memory for it: the host loop (vg_pairs_host) on
+//                         VARGENO_THREADS threads, one line under VARGENO_VERBOSE.  The joint VCF is the same bytes with or without it.
+//                         Tab-separated: ##sites, ##min_gq, one ##sample line each (called = counted sites, het = counted hets), then per
+//                         pair a < b in manifest order n, ibs0, ibs2, hethet, het_a, het_b (csrc/vg_pairs.h), concordance = ibs2 / n and
+//                         relatedness = (hethet - 2 ibs0) / min(het_a, het_b), `nan` over a zero denominator
+//   VARGENO_PAIRS_MIN_GQ=n  the table counts a call iff it is called and its GQ is at least n (default 0)
 //   VARGENO_VERBOSE=1     stderr: the index plan and start-up report, one "ingest, replica g:" line per route taken, the "reads:" line with
 //                         the wall time phase by phase; index: the "cuts:" line
 //   VARGENO_STATS=1       the kernel's counting build: events per read (vg_set_stats; off by default here, it carries ~50 more registers per lane)
 //   VARGENO_FORCE_RCCL=1  send the counters of a single replica through the RCCL all-reduce too (the identity)
 //   VARGENO_FQPIPE_QUIET=1  the hidden `fqpipe` command counts the reads and prints a rate instead of one line per record
 //   VARGENO_NO_LITE=1     index: skip <prefix>.ref.bf.lite.bf (2.3 GB, read by nothing in geno)
-//   VARGENO_THREADS=n     index: threads (default: all)
+//   VARGENO_THREADS=n     index: threads (default: all); joint: threads of the pair table's host loop
 // Where `index` cuts its work (host/index_build.cpp; numbers clamped to >= 1, defaults unchanged when unset -- tests make them
 // tiny so that every boundary falls inside sequences, N runs and repeat copies; VARGENO_VERBOSE=1 prints one "cuts:" line
 // with what the build actually did; every chunk costs 48 KiB of bucket counters, so tiny chunks are for small inputs):
@@ -153,6 +161,10 @@ struct GenoOptions {
 	const bool gzip_host = gzip_route() != GzipRoute::Refuse;
 	const bool gzip_device = gzip_route() == GzipRoute::Device;
 	const bool caller_device = std::string(env_str("VARGENO_CALLER")) == "device";      // genotypes from the caller kernel (default: the host loop)
+	// joint: the pairwise sample table (empty: none), the GQ from which a call counts in it, the threads of its host loop
+	const std::string joint_pairs = env_str("VARGENO_JOINT_PAIRS");
+	const int pairs_min_gq = env_int("VARGENO_PAIRS_MIN_GQ", 0);
+	const int pairs_threads = std::max(1, env_int("VARGENO_THREADS", usable_cpus()));
 	explicit GenoOptions(int devices) : have(devices)
 	{
 		if (ngpu > have && !share) ngpu = have;
@@ -1209,6 +1221,53 @@ static bool read_manifest(const std::string &path, std::vector<CohortSample> &sa
 	return true;
 }
 
+// The pairwise sample table of VARGENO_JOINT_PAIRS and the hidden `pairstsv` command (format: the comment block at the top);
+// counts = [N][N][5] as vg_gmatrix_pairs / vg_pairs_host fill it.
+static void write_pairs_table(const std::string &path, const std::vector<std::string> &names, uint64_t n_sites, int min_gq, const std::vector<uint64_t> &counts)
+{
+	FILE *f = fopen(path.c_str(), "w");
+	if (!f) throw vgh::Error{"cannot write " + path};
+	const size_t N = names.size();
+	auto at = [&](size_t i, size_t j, int k) { return counts[(i * N + j) * 5 + (size_t)k]; };
+	auto ratio = [&](double num, uint64_t den) { if (den == 0) fputs("\tnan", f); else fprintf(f, "\t%.6f", num / (double)den); };
+	fprintf(f, "##sites=%lu\n##min_gq=%d\n", (unsigned long)n_sites, min_gq);
+	for (size_t i = 0; i < N; i++) fprintf(f, "##sample=%s\tcalled=%lu\thet=%lu\n", names[i].c_str(), (unsigned long)at(i, i, 0), (unsigned long)at(i, i, 3));
+	fputs("#sample_a\tsample_b\tn\tibs0\tibs2\thethet\thet_a\thet_b\tconcordance\trelatedness\n", f);
+	for (size_t i = 0; i < N; i++)
+		for (size_t j = i + 1; j < N; j++) {
+			const uint64_t n = at(i, j, 0), ibs0 = at(i, j, 1), ibs2 = at(i, j, 2), hethet = at(i, j, 3), het_a = at(i, j, 4), het_b = at(j, i, 4);
+			fprintf(f, "%s\t%s\t%lu\t%lu\t%lu\t%lu\t%lu\t%lu", names[i].c_str(), names[j].c_str(), (unsigned long)n, (unsigned long)ibs0, (unsigned long)ibs2, (unsigned long)hethet, (unsigned long)het_a, (unsigned long)het_b);
+			ratio((double)ibs2, n);
+			ratio((double)((int64_t)hethet - 2 * (int64_t)ibs0), std::min(het_a, het_b));
+			fputc('\n', f);
+		}
+	const bool bad = ferror(f) != 0;
+	if (fclose(f) != 0 || bad) throw vgh::Error{"cannot write " + path};
+}
+
+// joint: the samples' columns into a genotype matrix on `device`, the table counted there; VG_ENOMEM from the matrix: the host loop
+static void joint_pairs_table(const GenoOptions &o, int device, const std::vector<vgh::JointSample> &columns, uint64_t n_sites)
+{
+	const size_t N = columns.size();
+	std::vector<uint64_t> counts(N * N * 5);
+	vg_gmatrix *gm = nullptr;
+	int rc = vg_gmatrix_create(device, n_sites, (uint32_t)N, &gm);
+	for (size_t i = 0; rc == VG_OK && i < N; i++) rc = vg_gmatrix_set(gm, (uint32_t)i, columns[i].calls.gt.data(), columns[i].calls.gq.data(), o.pairs_min_gq);
+	if (rc == VG_OK) rc = vg_gmatrix_pairs(gm, 0, counts.data());
+	vg_gmatrix_destroy(gm);
+	if (rc == VG_ENOMEM) {
+		if (o.verbose) fprintf(stderr, "pairs: no device memory for the genotype matrix (%s): the host loop on %d threads\n", vg_last_error(), o.pairs_threads);
+		std::vector<uint8_t> gt(N * n_sites);
+		std::vector<int32_t> gq(N * n_sites);
+		for (size_t i = 0; i < N; i++) { std::copy(columns[i].calls.gt.begin(), columns[i].calls.gt.end(), gt.begin() + i * n_sites); std::copy(columns[i].calls.gq.begin(), columns[i].calls.gq.end(), gq.begin() + i * n_sites); }
+		rc = vg_pairs_host(gt.data(), gq.data(), n_sites, (uint32_t)N, o.pairs_min_gq, o.pairs_threads, counts.data());
+	}
+	if (rc != VG_OK) throw vgh::Error{std::string("the pair table failed: ") + vg_last_error()};
+	std::vector<std::string> names;
+	for (const auto &c : columns) names.push_back(c.name);
+	write_pairs_table(o.joint_pairs, names, n_sites, o.pairs_min_gq, counts);
+}
+
 // joint_out: `vargeno joint` -- the same workers, but a finished sample's calls are kept as a column (from the caller kernel; the
 // host loop when the device has no memory for it) and ONE file is written after the last sample, if every sample succeeded.
 static int run_cohort(const std::string &prefix, const std::string &manifest, const std::string &vcf_in, const std::string *joint_out = nullptr)
@@ -1335,7 +1394,10 @@ static int run_cohort(const std::string &prefix, const std::string &manifest, co
 	for (int w = 0; w < K; w++) th.emplace_back(worker, (uint32_t)w);
 	for (auto &t : th) t.join();
 	if (joint && !failed.load()) {
-		try { vgh::write_joint_vcf(sites.pos, chrlens, columns, vcf_in, *joint_out, &vcf_text); }
+		try {
+			vgh::write_joint_vcf(sites.pos, chrlens, columns, vcf_in, *joint_out, &vcf_text);
+			if (!o.joint_pairs.empty()) joint_pairs_table(o, 0, columns, sites.pos.size());      // (replica 0 sits on device 0)
+		}
 		catch (const vgh::Error &e) { fprintf(stderr, "vargeno: %s\n", e.msg.c_str()); failed.store(1); }
 	}
 	struct timespec t2; clock_gettime(CLOCK_MONOTONIC, &t2);
@@ -1545,6 +1607,33 @@ int main(int argc, const char *argv[])
 				columns.push_back(std::move(js));
 			}
 			vgh::write_joint_vcf(pos, vgh::read_chrlens(argv[2]), columns, argv[3], argv[4]);
+			return EXIT_SUCCESS;
+		} else if (opt == "pairstsv") {
+			// hidden: the pair table alone, by the host loop, from one calls file per sample ("gt gq" per line; all of one length):
+			// <out.tsv> <min_gq> <name>=<calls.txt> ...  (no device needed; tests/test_pairs_cpu.py)
+			if (argc < 5) { print_help(); return EXIT_FAILURE; }
+			const int min_gq = atoi(argv[3]);
+			std::vector<std::string> names;
+			std::vector<uint8_t> gt;
+			std::vector<int32_t> gq;
+			uint64_t n_sites = 0;
+			for (int a = 4; a < argc; a++) {
+				const std::string arg = argv[a];
+				const size_t eq = arg.find('=');
+				if (eq == std::string::npos || eq == 0 || eq + 1 >= arg.size()) { print_help(); return EXIT_FAILURE; }
+				FILE *f = fopen(arg.substr(eq + 1).c_str(), "r");
+				if (!f) throw vgh::Error{"cannot open " + arg.substr(eq + 1)};
+				const size_t before = gt.size();
+				unsigned g; long q;
+				while (fscanf(f, "%u %ld", &g, &q) == 2) { gt.push_back((uint8_t)g); gq.push_back((int32_t)q); }
+				fclose(f);
+				if (a == 4) n_sites = gt.size();
+				else if (gt.size() - before != n_sites) throw vgh::Error{arg.substr(eq + 1) + " lists another number of sites than " + std::string(argv[4]).substr(std::string(argv[4]).find('=') + 1)};
+				names.push_back(arg.substr(0, eq));
+			}
+			std::vector<uint64_t> counts(names.size() * names.size() * 5);
+			if (vg_pairs_host(gt.data(), gq.data(), n_sites, (uint32_t)names.size(), min_gq, std::max(1, env_int("VARGENO_THREADS", 1)), counts.data()) != VG_OK) throw vgh::Error{std::string("vg_pairs_host failed: ") + vg_last_error()};
+			write_pairs_table(argv[2], names, n_sites, min_gq, counts);
 			return EXIT_SUCCESS;
 		} else if (opt == "version") {
 			// hidden: the build ids (sha256 prefixes of the sources) of this binary and of the HIP library it loaded

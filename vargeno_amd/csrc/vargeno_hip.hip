@@ -16,6 +16,7 @@
 #include "vg_bam.h"
 #include "vg_gunzip.h"
 #include "vg_caller.h"
+#include "vg_pairs.h"
 
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -4966,6 +4967,231 @@ extern "C" int vg_counts_allreduce_devices(vg_index **handles, int n)
 		const char *where = "";
 		const int rc = run_allreduce(B, n, &where);
 		if (rc) return fail(rc, "RCCL exchange of the site counters failed at: %s (%s)", where, B.last != ncclSuccess ? R.error_string(B.last) : "HIP error");
+		return VG_OK;
+	});
+}
+
+// ---- the genotype matrix and the pairwise sample table (vg_pairs.h; no reference counterpart) -----------------------------------
+// A vg_gmatrix holds, on one device, the class planes of n_samples samples -- planes[(sample * 3 + plane) * n_words + word] -- and
+// the n_samples x n_samples x 5 result.  It is no part of a vg_index.
+//
+// vg_pairs_pack_kernel: one wave per 64-site word, three ballots of the lanes' classes; a lane beyond n_sites votes for nothing, so
+// the tail bits of the last word are zero.
+//
+// vg_pairs_kernel, the hot path: a workgroup -- one wave -- owns a VG_PAIR_TILE x VG_PAIR_TILE tile of sample pairs (tiles with
+// tile_j >= tile_i; blockIdx.x) and words_per_block consecutive site words (blockIdx.y).  For VG_PAIR_RUN words at a time it stages
+// the planes of the tile's row samples and of its column samples in LDS, image word (plane, w, s) at (plane * RUN + w) * PITCH + s:
+// the samples of one word lie side by side.  64 lanes as 8 x 8; a lane owns rows {ty + 8a} x columns {tx + 8b}, a, b < 4: 16 pairs,
+// 80 u32 term counters in registers (vg_pairs.h: five terms give the five counters of [i][j] and het_j for [j][i]).  Per word a
+// lane reads 4 x 3 row words and 4 x 3 column words, 8 bytes each: among the 32 lanes of a read group (4 ty x 8 tx) the row reads
+// are four adjacent words, each broadcast to eight lanes, and the column reads eight consecutive words, each read by four lanes --
+// no bank is asked for two words.  The staging stores run over w fastest, 8 lanes PITCH words apart: PITCH is odd, so their 16
+// dwords fall on 16 different banks.  At the end the counters go to the result with 64-bit vector atomics (the result is zeroed
+// by a memset ahead of the launch): five to [i][j], and off the diagonal tiles het_j to [j][i][4]; a diagonal tile computes both
+// (i, j) and (j, i) itself.  vg_pairs_mirror_kernel then copies the four symmetric counters of the off-diagonal tiles to [j][i].
+constexpr unsigned VG_PAIR_TILE = 32, VG_PAIR_THREADS = 64, VG_PAIR_RUN = 8, VG_PAIR_PITCH = VG_PAIR_TILE + 1;
+constexpr uint64_t VG_PAIR_WORDS_DEFAULT = 1024;              // site words per block: 65 536 sites, far inside a u32 counter
+constexpr uint64_t VG_PAIR_WORDS_MAX = 1ull << 24;            // 2^30 sites per block: the u32 counters cannot wrap
+constexpr uint32_t VG_GMATRIX_MAX_SAMPLES = 16384;
+
+__global__ __launch_bounds__(256) void vg_pairs_pack_kernel(const uint8_t *__restrict__ gt, const int32_t *__restrict__ gq, uint64_t n_sites, uint64_t n_words, int32_t min_gq,
+                                                            uint64_t *__restrict__ r, uint64_t *__restrict__ h, uint64_t *__restrict__ a)
+{
+	const unsigned lane = threadIdx.x & 63;
+	const uint64_t n_waves = (uint64_t)gridDim.x * 4;
+	for (uint64_t w = ((uint64_t)blockIdx.x * 256 + threadIdx.x) >> 6; w < n_words; w += n_waves) {      // (w is the same for a wave's lanes)
+		const uint64_t s = w * 64 + lane;
+		const int c = s < n_sites ? vg_pair_class(gt[s], gq[s], min_gq) : -1;
+		const uint64_t br = __ballot(c == VGP_R), bh = __ballot(c == VGP_H), ba = __ballot(c == VGP_A);
+		if (lane == 0) { r[w] = br; h[w] = bh; a[w] = ba; }
+	}
+}
+
+__global__ __launch_bounds__(VG_PAIR_THREADS) void vg_pairs_kernel(const uint64_t *__restrict__ planes, uint64_t n_words, uint32_t n_samples, uint32_t n_tiles, uint64_t words_per_block,
+                                                                   unsigned long long *__restrict__ counts)
+{
+	constexpr unsigned T = VG_PAIR_TILE, RUN = VG_PAIR_RUN, PITCH = VG_PAIR_PITCH;
+	__shared__ uint64_t img[2][VGP_PLANES * RUN * PITCH];                 // [0] the row samples, [1] the column samples
+	uint32_t ti = 0, rem = blockIdx.x;
+	while (rem >= n_tiles - ti) { rem -= n_tiles - ti; ti++; }            // blockIdx.x counts the tiles (ti, tj >= ti) row by row
+	const uint32_t tj = ti + rem;
+	const uint64_t wbeg = (uint64_t)blockIdx.y * words_per_block, wend = wbeg + words_per_block < n_words ? wbeg + words_per_block : n_words;
+	const unsigned tx = threadIdx.x & 7, ty = threadIdx.x >> 3;
+	uint32_t acc[4][4][VGP_TERMS] = {};
+	for (uint64_t w0 = wbeg; w0 < wend; w0 += RUN) {
+		const uint64_t cnt = wend - w0;                                   // words of this run that exist (RUN or more: all)
+		for (unsigned e = threadIdx.x; e < 2 * T * VGP_PLANES * RUN; e += VG_PAIR_THREADS) {
+			const unsigned w = e % RUN, p = (e / RUN) % VGP_PLANES, s = (e / (RUN * VGP_PLANES)) % T, side = e / (RUN * VGP_PLANES * T);
+			const uint32_t sample = (side ? tj : ti) * T + s;
+			uint64_t v = 0;                                               // a sample beyond the matrix or a word beyond the block counts nothing
+			if (sample < n_samples && w < cnt) v = planes[((uint64_t)sample * VGP_PLANES + p) * n_words + w0 + w];
+			img[side][(p * RUN + w) * PITCH + s] = v;
+		}
+		__syncthreads();
+#pragma unroll 1
+		for (unsigned w = 0; w < RUN; w++) {
+			uint64_t row[4][VGP_PLANES], col[4][VGP_PLANES];
+#pragma unroll
+			for (unsigned p = 0; p < VGP_PLANES; p++) {
+#pragma unroll
+				for (unsigned a = 0; a < 4; a++) { row[a][p] = img[0][(p * RUN + w) * PITCH + ty + 8 * a]; col[a][p] = img[1][(p * RUN + w) * PITCH + tx + 8 * a]; }
+			}
+#pragma unroll
+			for (unsigned a = 0; a < 4; a++) {
+#pragma unroll
+				for (unsigned b = 0; b < 4; b++) {
+					vg_pair_word_add(acc[a][b], row[a][VGP_R], row[a][VGP_H], row[a][VGP_A], col[b][VGP_R], col[b][VGP_H], col[b][VGP_A]);
+					// one pair after the other: left alone the scheduler forms all 160 ANDs of the word first and needs 237 registers for them
+					__builtin_amdgcn_sched_barrier(0);
+				}
+			}
+		}
+		__syncthreads();
+	}
+#pragma unroll
+	for (unsigned a = 0; a < 4; a++) {
+#pragma unroll
+		for (unsigned b = 0; b < 4; b++) {
+			const uint32_t i = ti * T + ty + 8 * a, j = tj * T + tx + 8 * b;
+			if (i >= n_samples || j >= n_samples) continue;
+			uint64_t c[VGP_COUNTERS];
+			const uint64_t het_j = vg_pair_counters(acc[a][b], c);
+			unsigned long long *ij = counts + ((uint64_t)i * n_samples + j) * VGP_COUNTERS;
+#pragma unroll
+			for (unsigned k = 0; k < VGP_COUNTERS; k++) if (c[k]) atomicAdd(ij + k, (unsigned long long)c[k]);
+			if (ti != tj && het_j) atomicAdd(counts + ((uint64_t)j * n_samples + i) * VGP_COUNTERS + VGP_HET_I, (unsigned long long)het_j);
+		}
+	}
+}
+
+// [j][i][n, ibs0, ibs2, hethet] = [i][j][..] for the pairs of the off-diagonal tiles (tile of j above tile of i); [j][i][het_i] is
+// already there.  One lane per (i, j): blockIdx.y = i
+__global__ __launch_bounds__(256) void vg_pairs_mirror_kernel(unsigned long long *__restrict__ counts, uint32_t n_samples)
+{
+	const uint32_t i = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
+	if (j >= n_samples || i / VG_PAIR_TILE >= j / VG_PAIR_TILE) return;
+	const unsigned long long *ij = counts + ((uint64_t)i * n_samples + j) * VGP_COUNTERS;
+	unsigned long long *ji = counts + ((uint64_t)j * n_samples + i) * VGP_COUNTERS;
+	for (unsigned k = 0; k < VGP_HET_I; k++) ji[k] = ij[k];
+}
+
+struct vg_gmatrix {
+	int device = 0;
+	uint64_t n_sites = 0, n_words = 0, dev_bytes = 0;
+	uint32_t n_samples = 0;
+	uint64_t *d_planes = nullptr;                    // [n_samples][3][n_words]: zero = every call missing
+	unsigned long long *d_counts = nullptr;          // [n_samples][n_samples][5]
+	uint8_t *d_gt = nullptr;                         // one sample's columns on their way to the pack kernel
+	int32_t *d_gq = nullptr;
+	hipStream_t stream = nullptr;
+	hipEvent_t ev0 = nullptr, ev1 = nullptr;         // around the pair kernels (VG_VERBOSE prints the time)
+};
+
+static void gmatrix_free(vg_gmatrix *gm)
+{
+	if (!gm) return;
+	(void)hipSetDevice(gm->device);
+	if (gm->ev0) (void)hipEventDestroy(gm->ev0);
+	if (gm->ev1) (void)hipEventDestroy(gm->ev1);
+	if (gm->stream) (void)hipStreamDestroy(gm->stream);
+	for (void *p : {(void *)gm->d_planes, (void *)gm->d_counts, (void *)gm->d_gt, (void *)gm->d_gq}) if (p) (void)hipFree(p);
+	(void)hipGetLastError();
+	delete gm;
+}
+
+extern "C" int vg_gmatrix_create(int device, uint64_t n_sites, uint32_t n_samples, vg_gmatrix **out)
+{
+	if (!out) return fail(VG_EINVAL, "null argument");
+	*out = nullptr;
+	if (n_samples == 0) return fail(VG_EINVAL, "vg_gmatrix_create: no samples");
+	if (n_sites >= (1ull << 32)) return fail(VG_EINVAL, "vg_gmatrix_create: 2^32 sites or more");
+	if (n_samples > VG_GMATRIX_MAX_SAMPLES) return fail(VG_ETOOBIG, "vg_gmatrix_create: more than %s samples", std::to_string(VG_GMATRIX_MAX_SAMPLES).c_str());
+	return guarded([&]() -> int {
+		HIP_TRY(hipSetDevice(device));
+		vg_gmatrix *gm = new vg_gmatrix;
+		gm->device = device; gm->n_sites = n_sites; gm->n_words = (n_sites + 63) / 64; gm->n_samples = n_samples;
+		const size_t plane_bytes = (size_t)n_samples * VGP_PLANES * gm->n_words * 8, count_bytes = (size_t)n_samples * n_samples * VGP_COUNTERS * 8;
+		struct { void **p; size_t bytes; const char *what; } want[] = {
+			{(void **)&gm->d_planes, plane_bytes, "the samples' planes"}, {(void **)&gm->d_counts, count_bytes, "the pair table"},
+			{(void **)&gm->d_gt, (size_t)n_sites, "a gt column"}, {(void **)&gm->d_gq, (size_t)n_sites * 4, "a gq column"}};
+		for (auto &w : want) {
+			if (vg_malloc_patient(w.p, w.bytes ? w.bytes : 8) != hipSuccess) {
+				(void)hipGetLastError();
+				*w.p = nullptr;
+				gmatrix_free(gm);
+				return fail(VG_ENOMEM, "vg_gmatrix_create: no device memory for %s (%s bytes)", w.what, std::to_string(w.bytes).c_str());
+			}
+			gm->dev_bytes += w.bytes ? w.bytes : 8;
+		}
+		hipError_t e = hipStreamCreateWithFlags(&gm->stream, hipStreamNonBlocking);
+		if (e == hipSuccess) e = hipEventCreate(&gm->ev0);
+		if (e == hipSuccess) e = hipEventCreate(&gm->ev1);
+		if (e == hipSuccess && plane_bytes) e = hipMemsetAsync(gm->d_planes, 0, plane_bytes, gm->stream);
+		if (e == hipSuccess) e = hipStreamSynchronize(gm->stream);
+		if (e != hipSuccess) { gmatrix_free(gm); return fail(VG_ENODEV, "vg_gmatrix_create: %s", hipGetErrorString(e)); }
+		*out = gm;
+		return VG_OK;
+	});
+}
+
+extern "C" void vg_gmatrix_destroy(vg_gmatrix *gm) { gmatrix_free(gm); }
+extern "C" uint64_t vg_gmatrix_device_bytes(const vg_gmatrix *gm) { return gm ? gm->dev_bytes : 0; }
+
+extern "C" int vg_gmatrix_set(vg_gmatrix *gm, uint32_t sample, const uint8_t *gt, const int32_t *gq, int32_t min_gq)
+{
+	if (!gm || !gt || !gq) return fail(VG_EINVAL, "null argument");
+	if (sample >= gm->n_samples) return fail(VG_EINVAL, "vg_gmatrix_set: sample %s is out of range", std::to_string(sample).c_str());
+	if (gm->n_sites == 0) return VG_OK;
+	HIP_TRY(hipSetDevice(gm->device));
+	HIP_TRY(hipMemcpyAsync(gm->d_gt, gt, gm->n_sites, hipMemcpyHostToDevice, gm->stream));
+	HIP_TRY(hipMemcpyAsync(gm->d_gq, gq, gm->n_sites * 4, hipMemcpyHostToDevice, gm->stream));
+	uint64_t *r = gm->d_planes + (uint64_t)sample * VGP_PLANES * gm->n_words;
+	const unsigned grid = (unsigned)std::min<uint64_t>((gm->n_words + 3) / 4, 4096);
+	vg_pairs_pack_kernel<<<grid, 256, 0, gm->stream>>>(gm->d_gt, gm->d_gq, gm->n_sites, gm->n_words, min_gq, r + VGP_R * gm->n_words, r + VGP_H * gm->n_words, r + VGP_A * gm->n_words);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipStreamSynchronize(gm->stream));                    // (the host arrays are the caller's again)
+	return VG_OK;
+}
+
+extern "C" int vg_gmatrix_pairs(vg_gmatrix *gm, uint64_t words_per_block, uint64_t *counts)
+{
+	if (!gm || !counts) return fail(VG_EINVAL, "null argument");
+	HIP_TRY(hipSetDevice(gm->device));
+	const uint32_t N = gm->n_samples, n_tiles = (N + VG_PAIR_TILE - 1) / VG_PAIR_TILE;
+	const size_t count_bytes = (size_t)N * N * VGP_COUNTERS * 8;
+	uint64_t wpb = words_per_block ? words_per_block : VG_PAIR_WORDS_DEFAULT;
+	if (wpb > VG_PAIR_WORDS_MAX) wpb = VG_PAIR_WORDS_MAX;
+	if ((gm->n_words + wpb - 1) / wpb > 65535) wpb = (gm->n_words + 65534) / 65535;        // (a grid's second dimension ends there)
+	const unsigned n_blocks = (unsigned)((gm->n_words + wpb - 1) / wpb);
+	HIP_TRY(hipEventRecord(gm->ev0, gm->stream));
+	HIP_TRY(hipMemsetAsync(gm->d_counts, 0, count_bytes, gm->stream));
+	if (n_blocks) {
+		vg_pairs_kernel<<<dim3(n_tiles * (n_tiles + 1) / 2, n_blocks), VG_PAIR_THREADS, 0, gm->stream>>>(gm->d_planes, gm->n_words, N, n_tiles, wpb, gm->d_counts);
+		HIP_TRY(hipGetLastError());
+		if (n_tiles > 1) {
+			vg_pairs_mirror_kernel<<<dim3((N + 255) / 256, N), 256, 0, gm->stream>>>(gm->d_counts, N);
+			HIP_TRY(hipGetLastError());
+		}
+	}
+	HIP_TRY(hipEventRecord(gm->ev1, gm->stream));
+	HIP_TRY(hipMemcpyAsync(counts, gm->d_counts, count_bytes, hipMemcpyDeviceToHost, gm->stream));
+	HIP_TRY(hipStreamSynchronize(gm->stream));
+	if (getenv("VG_VERBOSE")) {
+		float ms = 0;
+		HIP_TRY(hipEventElapsedTime(&ms, gm->ev0, gm->ev1));
+		const double pw = (double)N * (N + 1) / 2 * (double)gm->n_words;
+		fprintf(stderr, "[vargeno_hip] vg_gmatrix_pairs: %u samples, %lu site words in %u blocks of %lu: kernels %.3f ms, %.3e pair-words/s\n", N, (unsigned long)gm->n_words, n_blocks, (unsigned long)wpb, ms, ms > 0 ? pw / (ms * 1e-3) : 0.0);
+	}
+	return VG_OK;
+}
+
+extern "C" int vg_pairs_host(const uint8_t *gt, const int32_t *gq, uint64_t n_sites, uint32_t n_samples, int32_t min_gq, int threads, uint64_t *counts)
+{
+	if (!counts || ((!gt || !gq) && n_sites)) return fail(VG_EINVAL, "null argument");
+	if (n_samples == 0) return fail(VG_EINVAL, "vg_pairs_host: no samples");
+	if (n_sites >= (1ull << 32)) return fail(VG_EINVAL, "vg_pairs_host: 2^32 sites or more");
+	return guarded([&]() -> int {
+		vg_pairs_host_run(gt, gq, n_sites, n_samples, min_gq, threads, counts);
 		return VG_OK;
 	});
 }
