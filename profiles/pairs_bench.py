@@ -9,7 +9,8 @@ VG_VERBOSE).  vg_pairs_host is timed on 16 threads at N = 64 only; its pair-word
 A pair-word is one 64-site word of one unordered pair, diagonal included: N (N + 1) / 2 x ceil(sites / 64) per table.
 The kernel's VALU instructions per pair-word are read from the library's gfx950 code (the body of the word loop, 16 pairs per lane
 and pass); with a wave64 VALU instruction issuing in 2 cycles on each of the 4 SIMDs of the 256 CUs that gives the issue-rate bound
-at the clock the device reports after the timed calls."""
+at the device's peak clock of 2.4 GHz.  The shader clock level the device reports after the timed calls is printed beside it and is
+no part of the bound: the first run showed 2 402, 217 and 158 MHz there -- by the time it is read the device has idled down."""
 import argparse
 import ctypes as C
 import os
@@ -25,6 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 LLVM = "/opt/rocm/lib/llvm/bin"
 CUS, SIMDS, CYCLES_PER_VALU, LANES, PAIRS_PER_LANE = 256, 4, 2, 64, 16
+PEAK_HZ = 2.4e9
 
 
 def valu_per_pair_word(lib_path):
@@ -56,7 +58,7 @@ def valu_per_pair_word(lib_path):
 
 
 def device_clock_hz():
-    """The shader clock the device reports now (its current DPM level), or None."""
+    """The shader clock the device reports now (its current DPM level, which after a short kernel is an idle one), or None."""
     import glob
 
     for f in sorted(glob.glob("/sys/class/drm/card*/device/pp_dpm_sclk")):
@@ -125,10 +127,9 @@ def main():
             med = float(np.median(ms))
             pw = n * (n + 1) / 2 * words
             rates[n] = pw / (med * 1e-3)
-            hz = clock or 2.4e9
-            bound = CUS * SIMDS * LANES / CYCLES_PER_VALU * hz / per_pw
-            lines.append("N = %4d: kernels %.3f ms (median of 5: %s), %.3e pair-words/s; issue-rate bound at %.0f MHz (%s) %.3e: %.1f %% of it; matrix %.2f GB"
-                         % (n, med, " ".join("%.3f" % v for v in ms), rates[n], hz / 1e6, "reported" if clock else "peak, none reported", bound, 100 * rates[n] / bound, gm.device_bytes / 1e9))
+            bound = CUS * SIMDS * LANES / CYCLES_PER_VALU * PEAK_HZ / per_pw
+            lines.append("N = %4d: kernels %.3f ms (median of 5: %s), %.3e pair-words/s; issue-rate bound at the peak %.0f MHz %.3e: %.1f %% of it (clock level read afterwards: %s); matrix %.2f GB"
+                         % (n, med, " ".join("%.3f" % v for v in ms), rates[n], PEAK_HZ / 1e6, bound, 100 * rates[n] / bound, "%.0f MHz" % (clock / 1e6) if clock else "none reported", gm.device_bytes / 1e9))
     # the host loop: N = 64 only, 16 threads
     n = 64
     gt = np.stack([np.roll(base_gt, 9973 * s) for s in range(n)])

@@ -38,6 +38,53 @@ def test_int_min_is_never_counted_and_the_default_threshold_is_zero():
     assert api.pairs_host(gt, gq, min_gq=PC.INT_MIN)[0, 0].tolist() == [5, 0, 5, 2, 2]
 
 
+def both_thread_counts(gt, gq, min_gq):
+    """The host table, which one and three threads agree on and which is the oracle's."""
+    got = api.pairs_host(gt, gq, min_gq=min_gq, threads=1)
+    assert np.array_equal(got, PC.oracle(gt, gq, min_gq))
+    assert np.array_equal(api.pairs_host(gt, gq, min_gq=min_gq, threads=3), got)
+    PC.check_identities(got)
+    return got
+
+
+@pytest.mark.parametrize("n_samples,n_sites", [(2, 321), (5, 449), (33, 1000)])
+def test_gt_values_above_three_are_not_counted(n_samples, n_sites):
+    """make_case(wild_gt=True): 4, 5, 7, 128 .. 131 and 255 are no calls, whatever their low bits and their gq."""
+    min_gq, seed = 20, 31 * n_samples + n_sites
+    gt, gq = PC.make_case(n_samples, n_sites, min_gq, seed, wild_gt=True)
+    plain_gt, plain_gq = PC.make_case(n_samples, n_sites, min_gq, seed)
+    wild = np.isin(gt, PC.WILD_GT)
+    assert wild.any(axis=1).all() and np.array_equal(plain_gt[~wild], gt[~wild]) and np.array_equal(plain_gq, gq)
+    assert ((gt[wild] & 3 != 0) & (gq[wild] >= min_gq)).any()                   # some would count if only the low bits were read
+    got = both_thread_counts(gt, gq, min_gq)
+    PC.check_adversaries(got, gt, gq, min_gq)
+    plain = both_thread_counts(plain_gt, plain_gq, min_gq)
+    assert got[0, 0, 0] < plain[0, 0, 0] and (got <= plain)[:, :, 0].all()
+    # no wild value is in any plane: with every other entry missing the table is empty, and alone they take nothing away
+    assert not both_thread_counts(np.where(wild, gt, 0).astype(np.uint8), gq, min_gq).any()
+    assert np.array_equal(both_thread_counts(np.where(wild, 0, gt).astype(np.uint8), gq, min_gq), got)
+
+
+@pytest.mark.parametrize("n_samples,n_sites", [(37, 577), (5, 64)])
+def test_the_residue_case_equals_its_closed_form(n_samples, n_sites):
+    """The table counted by hand from the residues of the sites (residue_table: no oracle, no matrix product) is the oracle's and
+    the host loop's."""
+    gt, gq = PC.residue_case(n_samples, n_sites)
+    want = PC.residue_table(n_samples, n_sites)
+    assert want.dtype == np.uint64 and want[0, 1, 0] > 0 and want[0, 1, 1] > 0 and want[2, 2, 3] > 0
+    assert np.array_equal(want, PC.oracle(gt, gq, 0))
+    assert np.array_equal(both_thread_counts(gt, gq, 0), want)
+
+
+@pytest.mark.parametrize("n_sites", [1, 2, 63, 64, 65, 512, 513])
+def test_saturated_planes(n_sites):
+    """Whole words of one class: every counter is n_sites, n_sites - 1, n_sites - 2 or 0."""
+    gt, gq = PC.saturated_case(n_sites, min_gq=20)
+    got = both_thread_counts(gt, gq, 20)
+    PC.check_saturated(got, n_sites)
+    assert not api.pairs_host(gt, gq, min_gq=21).any()                           # every gq is exactly at the threshold
+
+
 def test_pairs_host_refuses_bad_arguments():
     L = api.lib()
     out = np.zeros(5, np.uint64)
@@ -86,7 +133,8 @@ def test_pairstsv_writes_the_table_the_oracle_formats(tmp_path):
 
 def test_pair_header_is_clean_under_address_and_undefined_behaviour_sanitizers(tmp_path):
     """tests/pairs_asan.cpp: the header's host pack + count on exact-size heap arrays against a naive per-site loop, S in
-    {0, 1, 63, 64, 65, 129}, one and three threads -- compiled with -fsanitize=address,undefined and run on its own."""
+    {0, 1, 63, 64, 65, 129}, one and three threads, gt drawn from 0 .. 3, with values above 3 mixed in, and saturated (a sample all
+    of one class at the threshold) -- compiled with -fsanitize=address,undefined and run on its own."""
     here = os.path.dirname(os.path.abspath(__file__))
     csrc = os.path.join(here, "..", "vargeno_amd", "csrc")
     exe = str(tmp_path / "pairs_asan")
