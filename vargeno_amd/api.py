@@ -12,6 +12,7 @@ from __future__ import annotations
 import collections
 import ctypes as C
 import os
+import re
 
 import numpy as np
 
@@ -55,6 +56,14 @@ class GenoIndex:
             return lib().vg_index_plan(self._h).decode()
         except AttributeError:                                   # an older build loaded for an A/B run (VARGENO_HIP_LIB)
             return ""
+
+    @property
+    def quiet_bits(self):
+        """How many entries of the merged view carry the quiet bits that let a read's pile-up walk be skipped (vg_quiet.h): a dict
+        a / b / both / entries as the plan line states them, or None for a handle without direct table (nothing reads the bits).
+        VG_NO_QUIET=1 leaves every bit clear: all three counts are 0."""
+        m = re.search(r"quiet bits: A (\d+), B (\d+), both (\d+) of (\d+) mx entries", self.plan)
+        return dict(zip(("a", "b", "both", "entries"), map(int, m.groups()))) if m else None
 
     @property
     def open_report(self):

@@ -264,9 +264,14 @@ __global__ void vg_canon_keys(uint64_t *__restrict__ key, uint64_t n, uint32_t *
 // as little alive as it can, vg_arena.h).  The entry's last word carries HI32 of its key, i.e. its bucket, until the direct
 // table has been built from it (vg_make_direct; vg_inline_pairs then puts the word to its real use).
 // dx_bits < 32 (DevIndex::dx_bits): bits 16-31 of the flags word carry field F, the key's high-word bits below the bucket, left-aligned.
+// Quiet bits (vg_quiet.h; srank_words != nullptr): a reference entry with a single position says whether the site bits to the left
+// and to the right of its k-mer are all clear -- flags 64 (A) and 128 (B), which vg_make_direct copies into the dx record.  SNP
+// entries, ambiguous entries (PAIR or not) and POS_AMBIGUOUS get neither.  quiet_cnt: entries with A, with B, with both.
 __global__ void vg_make_mx_entries(const uint64_t *__restrict__ key, const uint32_t *__restrict__ val, uint64_t n, uint64_t n_ref,
-                                   const RefEnt *__restrict__ ref, const SnpEnt *__restrict__ snp, uint4 *__restrict__ out, const uint32_t *__restrict__ strand_bits, const uint32_t dx_bits)
+                                   const RefEnt *__restrict__ ref, const SnpEnt *__restrict__ snp, uint4 *__restrict__ out, const uint32_t *__restrict__ strand_bits, const uint32_t dx_bits,
+                                   const unsigned long long *__restrict__ srank_words, const uint64_t pile_len, unsigned long long *__restrict__ quiet_cnt)
 {
+	uint32_t na = 0, nb = 0, nab = 0;
 	for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
 		const uint32_t v = val[i];
 		const bool is_snp = v >= n_ref;
@@ -275,7 +280,17 @@ __global__ void vg_make_mx_entries(const uint64_t *__restrict__ key, const uint3
 		else { const RefEnt e = ref[v]; pos = e.pos; amb = e.amb; }
 		const uint32_t strand = (strand_bits[v >> 5] >> (v & 31)) & 1u;                          // flag 8: the dictionary's k-mer is the reverse complement of its canonical form
 		const uint32_t hi = (uint32_t)(key[i] >> 32), F = dx_bits < 32u ? (hi << dx_bits) & 0xFFFF0000u : 0u;
-		out[i] = make_uint4((uint32_t)key[i], pos, (is_snp ? 1u : 0u) | ((amb & 1u) << 1) | (strand << 3) | F, hi);
+		uint32_t quiet = 0;
+		if (srank_words && !is_snp && !(amb & 1u) && pos != POS_AMBIGUOUS) {
+			quiet = vg_quiet_bits(srank_words, pile_len, pos);
+			na += (quiet & VG_QUIET_A) != 0u; nb += (quiet & VG_QUIET_B) != 0u; nab += quiet == VG_QUIET_MASK;
+		}
+		out[i] = make_uint4((uint32_t)key[i], pos, (is_snp ? 1u : 0u) | ((amb & 1u) << 1) | (strand << 3) | quiet | F, hi);
+	}
+	if (quiet_cnt) {
+		if (na) atomicAdd(&quiet_cnt[0], (unsigned long long)na);
+		if (nb) atomicAdd(&quiet_cnt[1], (unsigned long long)nb);
+		if (nab) atomicAdd(&quiet_cnt[2], (unsigned long long)nab);
 	}
 }
 // An ambiguous k-mer (2-10 copies) points at an auxiliary row; when the row holds exactly two positions -- the usual case --
@@ -308,10 +323,10 @@ __global__ void vg_make_direct(const uint4 *__restrict__ mx, uint64_t n, uint4 *
 		while (hi < n && hi - i <= cmax && (mx[hi].w >> sh) == bkt) hi++;
 		uint32_t cnt = (uint32_t)(hi - i);
 		if (cnt > cmax) { atomicOr(too_big, 1u); cnt = (uint32_t)cmax; }        // the count field is 24 (8) bits wide: the host keeps the jump-table form (drops the view)
-		uint4 r = make_uint4(e.x, e.y, 1u | ((e.z & 1u) << 1) | (((e.z >> 1) & 1u) << 2) | (((e.z >> 3) & 1u) << 5) | (cnt << 8) | (e.z & 0xFFFF0000u), (uint32_t)i);   // (flag 32: strand)
+		uint4 r = make_uint4(e.x, e.y, 1u | ((e.z & 1u) << 1) | (((e.z >> 1) & 1u) << 2) | (((e.z >> 3) & 1u) << 5) | (e.z & VG_QUIET_MASK) | (cnt << 8) | (e.z & 0xFFFF0000u), (uint32_t)i);   // (flag 32: strand; 64, 128: quiet bits)
 		if (cnt > 1u && mx[i + 1].x == e.x && mx[i + 1].w == e.w) r.z |= 16u;            // TIE: the second entry carries the same k-mer (reference + SNP dictionary)
 		uint32_t p0, p1;
-		if (cnt == 1u && (e.z & 2u) && aux_pair((e.z & 1u) ? snp_aux_pos : ref_aux, e.y, p0, p1)) { r.y = p0; r.w = p1; r.z |= 8u; }
+		if (cnt == 1u && (e.z & 2u) && aux_pair((e.z & 1u) ? snp_aux_pos : ref_aux, e.y, p0, p1)) { r.y = p0; r.w = p1; r.z = (r.z | 8u) & ~VG_QUIET_MASK; }   // (an ambiguous entry has no quiet bit; a PAIR must not)
 		dx[bkt] = r;
 	}
 }
@@ -330,7 +345,7 @@ __global__ void vg_inline_pairs(uint4 *__restrict__ mx, uint64_t n, const uint32
 		uint4 e = mx[i];
 		uint32_t p0, p1;
 		e.w = 0u;                                                   // (the bucket word has done its job)
-		if ((e.z & 2u) && aux_pair((e.z & 1u) ? snp_aux_pos : ref_aux, e.y, p0, p1)) { e.y = p0; e.w = p1; e.z |= 4u; }
+		if ((e.z & 2u) && aux_pair((e.z & 1u) ? snp_aux_pos : ref_aux, e.y, p0, p1)) { e.y = p0; e.w = p1; e.z = (e.z | 4u) & ~VG_QUIET_MASK; }   // (a PAIR carries no quiet bit)
 		mx[i] = e;
 	}
 }
@@ -2534,6 +2549,7 @@ static int build_on_device(vg_index *ix, DevCols &c, const ViewPlan &plan, uint6
 	}
 	// ---- merged exact-match view (both dictionaries behind one HI32 table); its indices are 32 bits wide
 	const uint64_t nm = c.n_ref + c.n_snp;
+	unsigned long long quiet_cnt[3] = {0, 0, 0};
 	if (want_mx) {
 		TempDev<uint64_t> ka, kb; TempDev<uint32_t> va, vb;
 		if ((rc = ka.alloc(nm))) return rc;
@@ -2555,8 +2571,17 @@ static int build_on_device(vg_index *ix, DevCols &c, const ViewPlan &plan, uint6
 		}
 		if ((rc = dev_alloc(ix, &mx, nm))) return rc;
 		const uint32_t dxb = plan.dx ? plan.dx_bits : 32u;
-		vg_make_mx_entries<<<2048, 256, 0, st>>>(ka.p, va.p, nm, c.n_ref, d.ref, d.snp, mx, strand_bits.p, dxb);
+		// quiet bits (vg_quiet.h): only the direct-table look-up reads them; VG_NO_QUIET=1 leaves every bit clear (A/B runs, parity tests)
+		const bool want_quiet = plan.dx && !getenv("VG_NO_QUIET");
+		TempDev<unsigned long long> qcnt;
+		if (want_quiet) { if ((rc = qcnt.alloc(3))) return rc; HIP_TRY(hipMemsetAsync(qcnt.p, 0, 24, st)); }
+		vg_make_mx_entries<<<2048, 256, 0, st>>>(ka.p, va.p, nm, c.n_ref, d.ref, d.snp, mx, strand_bits.p, dxb,
+		                                         want_quiet ? reinterpret_cast<const unsigned long long *>(d.srank) : nullptr, d.pile_len, want_quiet ? qcnt.p : nullptr);
 		HIP_TRY(hipGetLastError());
+		if (want_quiet) {
+			HIP_TRY(hipStreamSynchronize(st));
+			HIP_TRY(hipMemcpy(quiet_cnt, qcnt.p, 24, hipMemcpyDeviceToHost));
+		}
 		ka.release(); va.release(); strand_bits.release();
 		d.mx_jg = mjg; d.mx = mx;
 		// direct table (64 GiB) in place of the merged jump table (16 GiB) when the plan has the room, from the entries' bucket
@@ -2594,6 +2619,13 @@ static int build_on_device(vg_index *ix, DevCols &c, const ViewPlan &plan, uint6
 		// jump-table look-up expands rows itself -- and their bucket words, which nothing reads)
 		if (d.dx) vg_inline_pairs<<<2048, 256, 0, st>>>(mx, nm, d.ref_aux, d.snp_aux_pos);
 		HIP_TRY(hipGetLastError());
+		if (d.dx) {
+			// how many entries can vouch for a site-free window (tests read this to know that the bits were really set)
+			char line[160];
+			snprintf(line, sizeof line, "; quiet bits: A %llu, B %llu, both %llu of %llu mx entries", quiet_cnt[0], quiet_cnt[1], quiet_cnt[2], (unsigned long long)nm);
+			ix->plan_text += line;
+			if (getenv("VG_VERBOSE")) fprintf(stderr, "[vargeno_hip] %s\n", line + 2);
+		}
 		pc.lap("merged view, direct table");
 	}
 	// ---- scratch of the lane tier, overflow counters, stats

@@ -11,6 +11,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "vg_quiet.h"
+
 namespace vg {
 
 constexpr uint32_t POS_AMBIGUOUS = 0xFFFFFFFFu;   // src/vartype.h:38
@@ -57,13 +59,16 @@ struct DevIndex {
 	// of that form -- behind ONE jump table over HI32 of the key, so the two exact look-ups of a chunk (qv.cc:840-841) cost one
 	// jump-table gather + at most one bucket line instead of two of each.  mx entry: {lo32, pos, flags, pos2} with
 	// flags bit 0 = SNP-dictionary entry, bit 1 = ambig_flag, bit 2 = PAIR (set once the direct table exists: the k-mer's
-	// auxiliary row holds exactly two positions and they are pos, pos2 -- no row gather in stage A).
+	// auxiliary row holds exactly two positions and they are pos, pos2 -- no row gather in stage A), bit 3 = strand, bits 6 and 7 =
+	// the quiet bits A and B of vg_quiet.h (reference entries with a single position only, written once when the handle is opened:
+	// no site within [pos - 96, pos + 32) / [pos, pos + 128); VG_NO_QUIET=1 leaves them clear), bits 16-31 = field F (below).
 	const uint32_t *mx_jg;         // [2^32 + 1]   (dropped when the direct table below could be allocated)
 	const uint4 *mx;               // [n_ref + n_snp]
 	// direct table over HI32: one 16-byte record per bucket = the bucket's FIRST merged entry inline {lo32, pos, flags,
 	// index of that entry in mx}, flags bit 0 = bucket non-empty, bit 1 = SNP entry, bit 2 = ambig_flag, bit 5 = strand, bit 4 = TIE (the second
 	// entry has the same k-mer), bit 3 = PAIR (single-
-	// entry buckets only: then the last word is the second position), bits 8.. = entries in the bucket.  A bucket with one entry -- the common case -- is settled, hit or miss, by ONE gather.  64 GiB.
+	// entry buckets only: then the last word is the second position), bits 6 and 7 = the first entry's quiet bits A and B (copied from
+	// the entry; clear on a PAIR), bits 8.. = entries in the bucket.  A bucket with one entry -- the common case -- is settled, hit or miss, by ONE gather.  64 GiB.
 	const uint4 *dx;
 	// dx_bits = 32: the table above.  dx_bits < 32 (r06: an index of n + m k-mers gets ~2 (n + m) buckets instead of 2^32 -- chr22-scale
 	// 2 GB instead of 64 GiB --, and an hg38-scale index under a budget can take 2^31 or 2^30): buckets = the TOP dx_bits bits of the

@@ -152,8 +152,17 @@ __device__ __forceinline__ void vg_wave_body(const DevIndex &d, const uint64_t *
 	// distinct (`vargeno index` skips ALT = REF records, dictgen.c:745), so a chunk cannot vote twice for a key with exact contexts;
 	// should a hand-made index do it anyway the read is passed on, down to the lane machine, which keeps contexts one by one.
 	// The main tier's masks are 16 bits wide (reads of more than 16 chunks -- 543 bases -- start in the next tier).
+	// QUIET KEYS: for a read of n <= 4 chunks the TOP bit of a key's mask (KQUIET; a chunk bit only for reads of 16 / 32 chunks) says
+	// that the key's whole window [key, key + 32 n) is known to hold no SNP site, so the fast walk of stage C, which would fire no
+	// atomic, is skipped when such a key wins.  The proof comes with the records stage A fetches anyway: a single-position
+	// reference entry of the direct table / merged view carries two bits (vg_quiet.h), and an exact context of chunk c proves its
+	// key quiet iff (c == 0 || A) && (c == n - 1 || B); one proof from any of the key's exact contexts is enough, so the bit is
+	// ORed into the mask where the chunk's bit is.  Kept in the mask because that costs no register and no LDS, in both tiers; the
+	// bit rides along where masks are copied or have chunk bits ORed in, and is masked out where the mask is counted or scanned
+	// (the vote: chunk bits of a read of n <= 4 chunks are bits 0-3).
 	using kmask_t = typename KMask<(WPB > 1)>::type;
 	constexpr uint32_t KMASK_CHUNKS = WPB > 1 ? 16u : 32u;
+	constexpr uint32_t KQUIET = 1u << (KMASK_CHUNKS - 1u);
 	__shared__ uint32_t K_idx[W_ECAP][64 * WPB], N_kpos[W_NCAP][64 * WPB];
 	__shared__ kmask_t K_mask[W_ECAP][64 * WPB];
 	__shared__ uint16_t N_meta[W_NCAP][64 * WPB];
@@ -376,7 +385,7 @@ __device__ __forceinline__ void vg_wave_body(const DevIndex &d, const uint64_t *
 			// or W_ECAP when the key is new (the caller inserts it: the forward list grows up from 0, the reverse-strand block down
 			// from the top).  A chunk that has voted for the key already: dup = true (see above).
 			uint32_t hint = 0;
-			auto key_find = [&](uint32_t q, uint32_t c, uint32_t lo, uint32_t hi, bool &dup) -> uint32_t {
+			auto key_find = [&](uint32_t q, uint32_t c, uint32_t lo, uint32_t hi, bool &dup, uint32_t qb = 0u) -> uint32_t {
 				uint32_t e = (uint32_t)W_ECAP;
 				const uint32_t cnt = hi - lo;
 				if (cnt) {
@@ -391,18 +400,20 @@ __device__ __forceinline__ void vg_wave_body(const DevIndex &d, const uint64_t *
 				}
 				if (e != (uint32_t)W_ECAP) {
 					const uint32_t m = K_mask[e][col];
-					if ((m >> c) & 1u) dup = true; else K_mask[e][col] = (kmask_t)(m | (1u << c));
+					if ((m >> c) & 1u) dup = true; else K_mask[e][col] = (kmask_t)(m | (1u << c) | qb);
 					hint = e + 1u;
 				}
 				return e;
 			};
-			auto push_exact = [&](uint32_t p, uint32_t c) {
+			// hf: the hit's flags as the direct-table look-up has them (1 hit, 2 ambiguous, 4 PAIR, 64 / 128 the entry's quiet bits); 0 elsewhere
+			auto quiet_bit = [&](uint32_t hf, uint32_t c) -> uint32_t { return (hf & 6u) == 0u && vg_quiet_key(hf, c, n) ? KQUIET : 0u; };
+			auto push_exact = [&](uint32_t p, uint32_t c, uint32_t hf = 0u) {
 				cur.add(S_CTX, 1);
 				if (ovf) return;
 				bool dup = false;
-				const uint32_t q = p - 32u * c;
-				if (key_find(q, c, 0u, kcnt, dup) == (uint32_t)W_ECAP) {
-					if (kcnt < (uint32_t)W_ECAP) { K_idx[kcnt][col] = q; K_mask[kcnt][col] = (kmask_t)(1u << c); kcnt++; hint = kcnt; } else { VG_OVF(0); ovf = true; }
+				const uint32_t q = p - 32u * c, qb = quiet_bit(hf, c);
+				if (key_find(q, c, 0u, kcnt, dup, qb) == (uint32_t)W_ECAP) {
+					if (kcnt < (uint32_t)W_ECAP) { K_idx[kcnt][col] = q; K_mask[kcnt][col] = (kmask_t)((1u << c) | qb); kcnt++; hint = kcnt; } else { VG_OVF(0); ovf = true; }
 				} else if (dup) { VG_OVF(2); ovf = true; }
 			};
 			auto push_row = [&](const uint32_t *row, uint32_t c) {               // a row ends at its first 0
@@ -602,8 +613,8 @@ __device__ __forceinline__ void vg_wave_body(const DevIndex &d, const uint64_t *
 								cur.add(S_CHUNKS, 1);
 								const uint4 b = bq[z];
 								const xkey_t key = kx[z];                               // (lo32, or (F, lo32) under SDX)
-								// hit state: position (or row index), second position of a PAIR, flags 1 hit, 2 ambiguous, 4 PAIR -- for this pass's
-								// strand, and (x...) for the other strand
+								// hit state: position (or row index), second position of a PAIR, flags 1 hit, 2 ambiguous, 4 PAIR, 64 / 128 the entry's
+								// quiet bits (vg_quiet.h) -- for this pass's strand, and (x...) for the other strand
 								uint32_t rp = 0, rp2 = 0, rf = 0, sp = 0, sp2 = 0, sf = 0;
 								const uint32_t ks = (sbits >> z) & 1u;
 								const bool pal = (sbits >> (4u + z)) & 1u;
@@ -615,21 +626,21 @@ __device__ __forceinline__ void vg_wave_body(const DevIndex &d, const uint64_t *
 									if ((pal || es != ks) && rc_top != RC_BAD) {
 										if (f & 2u) rc_top = RC_BAD;
 										else if (p1 != POS_AMBIGUOUS) {
-											const uint32_t c1 = n - 1u - (c + z), q1 = p1 - 32u * c1;
+											const uint32_t c1 = n - 1u - (c + z), q1 = p1 - 32u * c1, qb1 = quiet_bit(f, c1);
 											bool dup = false;
-											if (key_find(q1, c1, rc_top, (uint32_t)W_ECAP, dup) == (uint32_t)W_ECAP) {
+											if (key_find(q1, c1, rc_top, (uint32_t)W_ECAP, dup, qb1) == (uint32_t)W_ECAP) {
 												if (rc_top <= kcnt) rc_top = RC_BAD;
-												else { rc_top--; K_idx[rc_top][col] = q1; K_mask[rc_top][col] = (kmask_t)(1u << c1); }
+												else { rc_top--; K_idx[rc_top][col] = q1; K_mask[rc_top][col] = (kmask_t)((1u << c1) | qb1); }
 											} else if (dup) rc_top = RC_BAD;
 										}
 									}
 								};
-								if ((b.z & 1u) && ekey(b) == key)                      // the inline first entry (dx flags: 2 SNP, 4 ambiguous, 8 PAIR, 32 strand)
-									note((b.z & 2u) != 0u, (b.z >> 5) & 1u, b.y, b.w, 1u | (((b.z >> 2) & 1u) << 1) | (((b.z >> 3) & 1u) << 2));
+								if ((b.z & 1u) && ekey(b) == key)                      // the inline first entry (dx flags: 2 SNP, 4 ambiguous, 8 PAIR, 32 strand, 64 / 128 quiet)
+									note((b.z & 2u) != 0u, (b.z >> 5) & 1u, b.y, b.w, 1u | (((b.z >> 2) & 1u) << 1) | (((b.z >> 3) & 1u) << 2) | (b.z & VG_QUIET_MASK));
 								if (more[z]) {
 									const uint32_t cnt = ecnt(b), lo = b.w, hi = lo + cnt;
-									auto take = [&](const uint4 v) {                     // mx flags: 1 SNP, 2 ambiguous, 4 PAIR, 8 strand
-										note((v.z & 1u) != 0u, (v.z >> 3) & 1u, v.y, v.w, 1u | (v.z & 2u) | (v.z & 4u));
+									auto take = [&](const uint4 v) {                     // mx flags: 1 SNP, 2 ambiguous, 4 PAIR, 8 strand, 64 / 128 quiet
+										note((v.z & 1u) != 0u, (v.z >> 3) & 1u, v.y, v.w, 1u | (v.z & 2u) | (v.z & 4u) | (v.z & VG_QUIET_MASK));
 									};
 									#pragma unroll
 									for (uint32_t x = 0; x < SW; x++) if (x + 1u < cnt && ekey(sv[y][x]) == key) take(sv[y][x]);
@@ -649,7 +660,7 @@ __device__ __forceinline__ void vg_wave_body(const DevIndex &d, const uint64_t *
 								if (r_ok) {
 									if (rf & 2u) cur.add(S_AUX_REF, 1);
 									if (r_ax) queue_row(d.ref_aux, rp, c + z, 0u);
-									else { push_exact(rp, c + z); if (rf & 4u) push_exact(rp2, c + z); }
+									else { push_exact(rp, c + z, rf); if (rf & 4u) push_exact(rp2, c + z); }
 								}
 								if (s_ok) {
 									if (sf & 2u) cur.add(S_AUX_SNP, 1);
@@ -1340,8 +1351,9 @@ __device__ __forceinline__ void vg_wave_body(const DevIndex &d, const uint64_t *
 				// the reference's uint8_t wrap (at most one exact context per chunk and W_NCAP neighbour contexts).
 				int best = -1; bool amb = false;
 				uint32_t bestf = 0, target = 0, bmask = 0;
+				bool bquiet = false;                                         // the winning key's window holds no SNP site (see the key table's description)
 				for (uint32_t e = 0; e < kcnt; e++) {
-					const uint32_t idx = K_idx[e][col], m = K_mask[e][col];
+					const uint32_t idx = K_idx[e][col], mq = K_mask[e][col], m = n <= 4u ? mq & 15u : mq;   // (n <= 4: the top bit is KQUIET, no chunk)
 					uint32_t f = (uint32_t)__popc(m), chunks = m;
 					if (ncnt) {
 						const uint32_t first = (uint32_t)__ffs((int)m) - 1u;
@@ -1351,7 +1363,7 @@ __device__ __forceinline__ void vg_wave_body(const DevIndex &d, const uint64_t *
 						}
 					}
 					if (!(chunks & (chunks - 1u))) continue;
-					if (f > bestf) { best = (int)e; bestf = f; amb = false; target = idx; bmask = m; }
+					if (f > bestf) { best = (int)e; bestf = f; amb = false; target = idx; bmask = m; bquiet = n <= 4u && (mq & KQUIET) != 0u; }
 					else if (f == bestf) amb = true;
 				}
 				VG_CLK(4);
@@ -1368,58 +1380,61 @@ __device__ __forceinline__ void vg_wave_body(const DevIndex &d, const uint64_t *
 						bool fast = false;
 						if constexpr (!STATS) fast = n <= 4u && (uint64_t)target + 32u * n <= d.pile_len;
 						if (fast) {
-							const uint32_t blk0 = target >> 6, blk_last = (target + 32u * n - 1u) >> 6;
-							// named scalars, not arrays: an array the compiler cannot keep in registers ends up in scratch memory
-							const ulonglong2 zz = make_ulonglong2(0ull, 0ull);
-							VG_VC_AS(VC_READS, pk_kmer + (uint64_t)slot0, 8u * n);
-							const ulonglong2 r0 = gather_walk<ulonglong2>(d.srank + blk0);
-							const ulonglong2 r1 = blk0 + 1u <= blk_last ? gather_walk<ulonglong2>(d.srank + (blk0 + 1u)) : zz;
-							const ulonglong2 r2 = blk0 + 2u <= blk_last ? gather_walk<ulonglong2>(d.srank + (blk0 + 2u)) : zz;
-							uint64_t f0, f1, f2 = 0, f3 = 0;                     // the read's k-mers in file order
-							{
-								ulonglong2 v;
-								__builtin_memcpy(&v, pk_kmer + (uint64_t)slot0, 16); f0 = v.x; f1 = v.y;   // n >= 2: one chunk cannot win a vote
-								if (n == 4u) { __builtin_memcpy(&v, pk_kmer + ((uint64_t)slot0 + 2), 16); f2 = v.x; f3 = v.y; }
-								else if (n == 3u) f2 = pk_kmer[(uint64_t)slot0 + 2];
-							}
-							VG_CLKW(6);
-							// one loop over both lists and no lambda: a select over variables captured by reference becomes a select of
-							// addresses, which parks the whole closure in scratch memory
-							// the supporting contexts: the winning key's exact contexts (one per chunk of its mask, at target + 32 chunk), then
-							// the neighbour contexts with its implied position (whether or not they voted, qv.cc:1386-1502)
-							uint32_t em = bmask, ni = 0;
-							for (;;) {
-								uint32_t c, mod = NOMOD;
-								if (em) { c = (uint32_t)__ffs((int)em) - 1u; em &= em - 1u; }
-								else {
-									if (ni >= ncnt) break;
-									const uint32_t mt = N_meta[ni][col], p = N_kpos[ni][col];
-									ni++;
-									c = mt & 31u; mod = (mt >> 5) & 31u;
-									if (p - 32u * c != target) continue;
+							// a quiet winner: every site mask below would be zero -- no rank-block gather, no k-mer re-read, no loop
+							if (!bquiet) {
+								const uint32_t blk0 = target >> 6, blk_last = (target + 32u * n - 1u) >> 6;
+								// named scalars, not arrays: an array the compiler cannot keep in registers ends up in scratch memory
+								const ulonglong2 zz = make_ulonglong2(0ull, 0ull);
+								VG_VC_AS(VC_READS, pk_kmer + (uint64_t)slot0, 8u * n);
+								const ulonglong2 r0 = gather_walk<ulonglong2>(d.srank + blk0);
+								const ulonglong2 r1 = blk0 + 1u <= blk_last ? gather_walk<ulonglong2>(d.srank + (blk0 + 1u)) : zz;
+								const ulonglong2 r2 = blk0 + 2u <= blk_last ? gather_walk<ulonglong2>(d.srank + (blk0 + 2u)) : zz;
+								uint64_t f0, f1, f2 = 0, f3 = 0;                     // the read's k-mers in file order
+								{
+									ulonglong2 v;
+									__builtin_memcpy(&v, pk_kmer + (uint64_t)slot0, 16); f0 = v.x; f1 = v.y;   // n >= 2: one chunk cannot win a vote
+									if (n == 4u) { __builtin_memcpy(&v, pk_kmer + ((uint64_t)slot0 + 2), 16); f2 = v.x; f3 = v.y; }
+									else if (n == 3u) f2 = pk_kmer[(uint64_t)slot0 + 2];
 								}
-								const uint32_t fi = pass ? n - 1u - c : c;
-								uint64_t kk = fi == 0 ? f0 : fi == 1 ? f1 : fi == 2 ? f2 : f3;
-								if (pass) kk = revcomp64(kk);
-								const uint32_t o = (target & 63u) + 32u * c;         // bit offset of the window in the blocks
-								const uint32_t z = o >> 6, sh = o & 63u;
-								const uint64_t w0 = z == 0 ? r0.x : z == 1 ? r1.x : r2.x;
-								const uint64_t w1 = z == 0 ? r1.x : r2.x;           // only read when the window crosses into it (then z <= 1)
-								uint32_t sites = (uint32_t)(w0 >> sh);
-								if (sh > 32u) sites |= (uint32_t)(w1 << (64u - sh));
-								if (mod < 32u) sites &= ~(1u << mod);
-								while (sites) {
-									const uint32_t b = (uint32_t)__ffs((int)sites) - 1;
-									sites &= sites - 1;
-									const uint32_t ob = o + b, zb = ob >> 6;
-									const uint64_t mx_ = zb == 0 ? r0.x : zb == 1 ? r1.x : r2.x, my_ = zb == 0 ? r0.y : zb == 1 ? r1.y : r2.y;
-									const uint32_t sid = (uint32_t)my_ + (uint32_t)__popcll(mx_ & ((1ull << (ob & 63u)) - 1ull));
-									VG_VC(&d.cnt4[4ull * sid + ((uint32_t)(kk >> (2 * b)) & 3u)], 4);
-									atomicAdd(&d.cnt4[4ull * sid + ((uint32_t)(kk >> (2 * b)) & 3u)], 1u);
+								VG_CLKW(6);
+								// one loop over both lists and no lambda: a select over variables captured by reference becomes a select of
+								// addresses, which parks the whole closure in scratch memory
+								// the supporting contexts: the winning key's exact contexts (one per chunk of its mask, at target + 32 chunk), then
+								// the neighbour contexts with its implied position (whether or not they voted, qv.cc:1386-1502)
+								uint32_t em = bmask, ni = 0;
+								for (;;) {
+									uint32_t c, mod = NOMOD;
+									if (em) { c = (uint32_t)__ffs((int)em) - 1u; em &= em - 1u; }
+									else {
+										if (ni >= ncnt) break;
+										const uint32_t mt = N_meta[ni][col], p = N_kpos[ni][col];
+										ni++;
+										c = mt & 31u; mod = (mt >> 5) & 31u;
+										if (p - 32u * c != target) continue;
+									}
+									const uint32_t fi = pass ? n - 1u - c : c;
+									uint64_t kk = fi == 0 ? f0 : fi == 1 ? f1 : fi == 2 ? f2 : f3;
+									if (pass) kk = revcomp64(kk);
+									const uint32_t o = (target & 63u) + 32u * c;         // bit offset of the window in the blocks
+									const uint32_t z = o >> 6, sh = o & 63u;
+									const uint64_t w0 = z == 0 ? r0.x : z == 1 ? r1.x : r2.x;
+									const uint64_t w1 = z == 0 ? r1.x : r2.x;           // only read when the window crosses into it (then z <= 1)
+									uint32_t sites = (uint32_t)(w0 >> sh);
+									if (sh > 32u) sites |= (uint32_t)(w1 << (64u - sh));
+									if (mod < 32u) sites &= ~(1u << mod);
+									while (sites) {
+										const uint32_t b = (uint32_t)__ffs((int)sites) - 1;
+										sites &= sites - 1;
+										const uint32_t ob = o + b, zb = ob >> 6;
+										const uint64_t mx_ = zb == 0 ? r0.x : zb == 1 ? r1.x : r2.x, my_ = zb == 0 ? r0.y : zb == 1 ? r1.y : r2.y;
+										const uint32_t sid = (uint32_t)my_ + (uint32_t)__popcll(mx_ & ((1ull << (ob & 63u)) - 1ull));
+										VG_VC(&d.cnt4[4ull * sid + ((uint32_t)(kk >> (2 * b)) & 3u)], 4);
+										atomicAdd(&d.cnt4[4ull * sid + ((uint32_t)(kk >> (2 * b)) & 3u)], 1u);
+									}
 								}
+								VG_CLK(7);
+								VG_CLKW(8);
 							}
-							VG_CLK(7);
-							VG_CLKW(8);
 						} else if (!STATS && n <= 8u && (uint64_t)target + 32u * n <= d.pile_len) {
 							// Reads of five to eight chunks (250 bp: seven) the same way (r06): their supporting contexts lie in [target, target + 256),
 							// which five rank blocks cover -- one or two lines for the whole read, where the byte-per-position walk below costs a pile
