@@ -289,6 +289,19 @@ int  vg_bgzf_inflate_host(const uint8_t *bgzf, uint64_t nbytes, uint8_t *text, u
  * payload offset, payload length, ISIZE, CRC32.  *consumed / *bad_block_offset as above (header errors only). */
 int  vg_bgzf_scan_host(const uint8_t *bgzf, uint64_t nbytes, uint64_t *blocks, uint64_t blocks_cap, uint64_t *n_blocks, uint64_t *consumed, uint64_t *bad_block_offset);
 
+/* The other direction: text[0, nbytes) in host memory written as BGZF into bgzf[0, cap), *bgzf_len = its bytes.  `block` = text bytes
+ * per block: 0 means 65 280 (htslib's), 1 ... 65 280 are allowed, anything above is VG_EINVAL.  eof != 0 appends htslib's 28-byte
+ * empty block (empty text with eof gives exactly that marker).  A block is fixed-Huffman DEFLATE with matches of 4 ... 258 bytes, or
+ * stored when that would not be smaller than its text; its header is bgzip's (MTIME 0, XFL 0, OS ff, one BC subfield).  The bytes
+ * are a function of the text and `block` alone: the same from the host form on any number of `threads` and from the device form,
+ * and the concatenation of calls over pieces cut at multiples of `block` (all but the last with eof = 0) is the one call's output.
+ * vg_bgzf_deflate_bound: what always fits (every block stored, plus the marker; 0 for a `block` that is refused).  VG_ETOOBIG: cap
+ * is too small, nothing is written.  VG_EINVAL: a null pointer.  The device form never falls back: VG_ENODEV without a device,
+ * VG_ENOMEM without device memory (nothing is left behind); with VG_VERBOSE set it prints the kernels' own time and rate. */
+uint64_t vg_bgzf_deflate_bound(uint64_t nbytes, uint32_t block);
+int  vg_bgzf_deflate_host(const uint8_t *text, uint64_t nbytes, uint32_t block, int eof, int threads, uint8_t *bgzf, uint64_t cap, uint64_t *bgzf_len);
+int  vg_bgzf_deflate_device(int device, const uint8_t *text, uint64_t nbytes, uint32_t block, int eof, uint8_t *bgzf, uint64_t cap, uint64_t *bgzf_len);
+
 /* Plain gzip (RFC 1952 members around one DEFLATE stream: what gzip, pigz and sequencers write; no block table) without a handle.
  * gz[0, nbytes) is inflated member after member into text[0, text_cap) in host memory; *text_len = bytes of text, *consumed =
  * compressed bytes used, both at the end of the last member that was decoded whole with its CRC32 and ISIZE (mod 2^32) verified.

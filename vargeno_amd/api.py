@@ -466,6 +466,23 @@ def bgzf_inflate(data, device=0, out=None, text_cap=None):
     return out[:int(n.value)].tobytes(), int(used.value), (None if bad.value == 2 ** 64 - 1 else int(bad.value))
 
 
+def bgzf_deflate(text, device=None, block=0, eof=True, threads=None):
+    """`text` written as BGZF (vg_bgzf_deflate_*): on `device` by the deflate kernel, or (device=None) by the host build of the same
+    compressor on `threads` threads (default: the CPUs of this process, at most 16).  block: text bytes per block, 0 = 65 280;
+    eof: append the empty end-of-file block.  The bytes depend on the text and `block` alone.  Returns bytes."""
+    a = _u8(text)
+    cap = int(lib().vg_bgzf_deflate_bound(len(a), int(block)))
+    out = np.zeros(max(1, cap), dtype=np.uint8)
+    n = C.c_uint64()
+    if device is None:
+        if threads is None:
+            threads = min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1))
+        check(lib().vg_bgzf_deflate_host(_ptr(a), len(a), int(block), int(bool(eof)), int(threads), _ptr(out), cap, C.byref(n)))
+    else:
+        check(lib().vg_bgzf_deflate_device(int(device), _ptr(a), len(a), int(block), int(bool(eof)), _ptr(out), cap, C.byref(n)))
+    return out[:int(n.value)].tobytes()
+
+
 class GunzipResult(collections.namedtuple("GunzipResult", "text consumed bad_offset stats error")):
     """text: the bytes of the members decoded whole and verified; consumed: compressed bytes up to there; bad_offset / error: the
     compressed offset and the library's message when the data is bad (None otherwise); stats: vg_gzip_stats as a dict (chunked

@@ -19,11 +19,15 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <condition_variable>
+#include <deque>
 #include <map>
+#include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
 
+#include "../../../include/vargeno_hip.h"
 #include "vg_host.h"
 #include "../vg_caller.h"
 
@@ -358,6 +362,141 @@ bool read_whole_file(const std::string &path, std::string &text)
 	return ok;
 }
 
+// ------------------------------------------------------------------------------------------------
+// where the text goes (vg_host.h: VcfSink)
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+class PlainSink : public VcfSink {
+public:
+	PlainSink(const std::string &path) : path_(path), f_(fopen(path.c_str(), "wb")) { if (!f_) throw Error{"cannot write " + path}; }
+	~PlainSink() override { if (f_) fclose(f_); }
+	void write(const char *p, size_t n) override { fwrite(p, 1, n, f_); }
+	void close() override
+	{
+		FILE *f = f_;
+		f_ = nullptr;
+		if (fclose(f) != 0) throw Error{"cannot write " + path_};
+	}
+private:
+	const std::string path_;
+	FILE *f_;
+};
+
+// Spans of span_ bytes (a multiple of the block: the blocks of the file are those of one call over the whole text) go to a worker
+// thread, which compresses and writes them in order; the producer waits while two are queued.
+class BgzfSink : public VcfSink {
+public:
+	BgzfSink(const std::string &path, const VcfOutput &how) : path_(path), how_(how), f_(fopen(path.c_str(), "wb"))
+	{
+		if (!f_) throw Error{"cannot write " + path};
+		const uint64_t block = how.block ? how.block : 65280;
+		span_ = (size_t)(block * std::max<uint64_t>(1, (16ull << 20) / block));
+		device_ = how.bgzf == VcfBgzf::Device;
+		worker_ = std::thread([this] { work(); });
+	}
+	~BgzfSink() override
+	{
+		stop(true);
+		if (f_) fclose(f_);
+	}
+	void write(const char *p, size_t n) override
+	{
+		while (n) {                                                   // one span at most per step
+			const size_t take = std::min(n, span_ - cur_.size());
+			cur_.insert(cur_.end(), p, p + take);
+			p += take; n -= take;
+			if (cur_.size() == span_) push(false);
+		}
+	}
+	void close() override
+	{
+		push(true);                                                   // the rest of the text (or none), and the end-of-file marker behind it
+		stop(false);
+		FILE *f = f_;
+		f_ = nullptr;
+		const bool closed = fclose(f) == 0;
+		if (!error_.empty()) throw Error{error_};
+		if (!closed) throw Error{"cannot write " + path_};
+	}
+private:
+	struct Span { std::vector<uint8_t> text; bool last; };
+	void push(bool last)
+	{
+		std::unique_lock<std::mutex> g(mu_);
+		cv_.wait(g, [&] { return q_.size() < 2; });
+		q_.push_back(Span{std::move(cur_), last});
+		cur_ = std::vector<uint8_t>();
+		if (!last) cur_.reserve(span_);
+		cv_.notify_all();
+	}
+	void stop(bool abandon)
+	{
+		{ std::lock_guard<std::mutex> g(mu_); done_ = true; if (abandon) { abandon_ = true; q_.clear(); } }
+		cv_.notify_all();
+		if (worker_.joinable()) worker_.join();
+	}
+	// one span -> its BGZF bytes in out; "" or what went wrong
+	std::string compress(const Span &s, std::vector<uint8_t> &out)
+	{
+		const uint64_t cap = vg_bgzf_deflate_bound(s.text.size(), how_.block);
+		out.resize((size_t)cap);
+		uint64_t len = 0;
+		const uint8_t *text = s.text.empty() ? out.data() : s.text.data();      // (no text: any pointer that is not null)
+		if (device_) {
+			const int rc = vg_bgzf_deflate_device(how_.device, text, s.text.size(), how_.block, s.last, out.data(), cap, &len);
+			if (rc == VG_ENOMEM) {
+				if (how_.verbose) fprintf(stderr, "vcf: no device memory for the deflate kernel (%s): the rest of %s is compressed on the host\n", vg_last_error(), path_.c_str());
+				device_ = false;
+			} else if (rc != VG_OK) return std::string("vg_bgzf_deflate_device failed: ") + vg_last_error();
+		}
+		if (!device_ && vg_bgzf_deflate_host(text, s.text.size(), how_.block, s.last, how_.threads, out.data(), cap, &len) != VG_OK)
+			return std::string("vg_bgzf_deflate_host failed: ") + vg_last_error();
+		out.resize((size_t)len);
+		return std::string();
+	}
+	void work()
+	{
+		std::vector<uint8_t> out;
+		for (;;) {                                                    // one span per step
+			Span s;
+			{
+				std::unique_lock<std::mutex> g(mu_);
+				cv_.wait(g, [&] { return !q_.empty() || done_; });
+				if (q_.empty() || abandon_) return;
+				s = std::move(q_.front());                            // (it stays queued while it is compressed: two spans are in flight, not three)
+			}
+			if (error_.empty()) {
+				std::string e = compress(s, out);
+				if (e.empty() && fwrite(out.data(), 1, out.size(), f_) != out.size()) e = "cannot write " + path_;
+				if (!e.empty()) error_ = e;                           // (read by close(), after the join)
+			}
+			{ std::lock_guard<std::mutex> g(mu_); if (!q_.empty()) q_.pop_front(); }
+			cv_.notify_all();
+			if (s.last) return;
+		}
+	}
+	const std::string path_;
+	const VcfOutput how_;
+	FILE *f_;
+	size_t span_ = 0;
+	bool device_ = false;
+	std::vector<uint8_t> cur_;
+	std::thread worker_;
+	std::mutex mu_; std::condition_variable cv_;
+	std::deque<Span> q_;
+	bool done_ = false, abandon_ = false;
+	std::string error_;
+};
+
+}  // namespace
+
+std::unique_ptr<VcfSink> open_vcf_sink(const std::string &path, const VcfOutput &how)
+{
+	if (how.bgzf == VcfBgzf::Off) return std::unique_ptr<VcfSink>(new PlainSink(path));
+	return std::unique_ptr<VcfSink>(new BgzfSink(path, how));
+}
+
 namespace {
 
 unsigned vcf_threads()
@@ -369,9 +508,9 @@ unsigned vcf_threads()
 
 // The pass over the SNP list's bytes, shared by the single-sample and the joint writer.  header(p, end, dst) takes the lines that
 // one thread reads in file order and stops in front of the first data line that can be annotated independently of its
-// neighbours; line(ln, dst, scratch) annotates one such line.  Returns the seconds spent in fwrite.
+// neighbours; line(ln, dst, scratch) annotates one such line.  Returns the seconds spent handing text to the sink.
 template <class Header, class Line>
-double vcf_pass(const std::string &text, FILE *out, unsigned threads, Header header, Line line)
+double vcf_pass(const std::string &text, VcfSink &out, unsigned threads, Header header, Line line)
 {
 	double t_write = 0;
 	auto lap = [](const timespec &a, const timespec &b) { return (double)(b.tv_sec - a.tv_sec) + 1e-9 * (double)(b.tv_nsec - a.tv_nsec); };
@@ -379,7 +518,7 @@ double vcf_pass(const std::string &text, FILE *out, unsigned threads, Header hea
 	while (p < end) {
 		std::string seq;
 		header(p, end, seq);
-		fwrite(seq.data(), 1, seq.size(), out);
+		out.write(seq.data(), seq.size());
 		// a run of data lines: up to the next line that starts with '#' (the reference re-reads header lines wherever they
 		// stand, so they fence the run), cut at line starts into one piece per thread
 		const char *stop = end;
@@ -413,9 +552,9 @@ double vcf_pass(const std::string &text, FILE *out, unsigned threads, Header hea
 			for (unsigned t = 0; t < nt; t++) th.emplace_back(work, t);
 			for (auto &x : th) x.join();
 		}
-		for (unsigned t = 0; t < nt; t++) if (!err[t].empty()) { fclose(out); throw Error{err[t]}; }
+		for (unsigned t = 0; t < nt; t++) if (!err[t].empty()) throw Error{err[t]};
 		struct timespec c2, c3; clock_gettime(CLOCK_MONOTONIC, &c2);
-		for (unsigned t = 0; t < nt; t++) fwrite(piece[t].data(), 1, piece[t].size(), out);          // (positioned writes by several threads are slower: one inode lock)
+		for (unsigned t = 0; t < nt; t++) out.write(piece[t].data(), piece[t].size());          // (positioned writes by several threads are slower: one inode lock)
 		clock_gettime(CLOCK_MONOTONIC, &c3);
 		t_write += lap(c2, c3);
 		p = stop;
@@ -425,7 +564,7 @@ double vcf_pass(const std::string &text, FILE *out, unsigned threads, Header hea
 
 }  // namespace
 
-CallSummary write_genotyped_vcf(const SiteCounts &s, const std::vector<ChrLen> &chrlens, const std::string &vcf_in, const std::string &vcf_out, const std::string *vcf_text, const SiteCalls *calls)
+CallSummary write_genotyped_vcf(const SiteCounts &s, const std::vector<ChrLen> &chrlens, const std::string &vcf_in, const std::string &vcf_out, const std::string *vcf_text, const SiteCalls *calls, const VcfOutput &how)
 {
 	CallSummary sum;
 	const bool clocks = getenv("VARGENO_VCF_CLOCKS") != nullptr;
@@ -439,14 +578,13 @@ CallSummary write_genotyped_vcf(const SiteCounts &s, const std::vector<ChrLen> &
 	const std::string &text = vcf_text ? *vcf_text : own;
 	struct timespec c1b; clock_gettime(CLOCK_MONOTONIC, &c1b);
 	if (!ok) { fprintf(stderr, "Error opening: %s . You have failed.\n", vcf_in.c_str()); return sum; }
-	FILE *out = fopen(vcf_out.c_str(), "wb");
-	if (!out) throw Error{"cannot write " + vcf_out};
+	const std::unique_ptr<VcfSink> out = open_vcf_sink(vcf_out, how);
 
 	Layout lay;
-	const double t_write = vcf_pass(text, out, vcf_threads(),
+	const double t_write = vcf_pass(text, *out, vcf_threads(),
 	                                [&](const char *&p, const char *end, std::string &dst) { ordered_lines(p, end, lay, book, dst); },
 	                                [&](Span ln, std::string &dst, Scratch &sc) { annotate(ln, book, lay, false, nullptr, dst, sc); });
-	if (fclose(out) != 0) throw Error{"cannot write " + vcf_out};
+	out->close();
 	if (clocks) { struct timespec c4; clock_gettime(CLOCK_MONOTONIC, &c4); fprintf(stderr, "vcf: calls + book %.3f s, SNP list read %.3f s, lines %.3f s, write %.3f s\n", lap(c0, c1), lap(c1, c1b), lap(c1b, c4) - t_write, t_write); }
 	return sum;
 }
@@ -457,7 +595,7 @@ CallSummary write_genotyped_vcf(const SiteCounts &s, const std::vector<ChrLen> &
 // A data line is written iff at least one sample's own VCF would contain it: its first eight fields, GT:GQ, then per sample what
 // that sample's own VCF shows for the record -- the call of the LAST site of the record's key, in genome order, that the sample
 // has called -- or ./.:. if its VCF drops the record.
-void write_joint_vcf(const std::vector<uint32_t> &pos, const std::vector<ChrLen> &chrlens, const std::vector<JointSample> &samples, const std::string &vcf_in, const std::string &vcf_out, const std::string *vcf_text)
+void write_joint_vcf(const std::vector<uint32_t> &pos, const std::vector<ChrLen> &chrlens, const std::vector<JointSample> &samples, const std::string &vcf_in, const std::string &vcf_out, const std::string *vcf_text, const VcfOutput &how)
 {
 	for (const JointSample &js : samples)
 		if (js.calls.gt.size() != pos.size() || js.calls.gq.size() != pos.size()) throw Error{"sample " + js.name + " has calls for another number of sites than the index has"};
@@ -467,8 +605,7 @@ void write_joint_vcf(const std::vector<uint32_t> &pos, const std::vector<ChrLen>
 	if (!vcf_text) own = slurp(vcf_in, ok);
 	const std::string &text = vcf_text ? *vcf_text : own;
 	if (!ok) throw Error{"Error opening: " + vcf_in + " . You have failed."};
-	FILE *out = fopen(vcf_out.c_str(), "wb");
-	if (!out) throw Error{"cannot write " + vcf_out};
+	const std::unique_ptr<VcfSink> out = open_vcf_sink(vcf_out, how);
 
 	const size_t n = samples.size();
 	bool declares_gt = false, declares_gq = false;
@@ -528,8 +665,8 @@ void write_joint_vcf(const std::vector<uint32_t> &pos, const std::vector<ChrLen>
 		dst.append(head.b, head.e) += "\tGT:GQ";
 		dst.append(cols).push_back('\n');
 	};
-	vcf_pass(text, out, vcf_threads(), header, line);
-	if (fclose(out) != 0) throw Error{"cannot write " + vcf_out};
+	vcf_pass(text, *out, vcf_threads(), header, line);
+	out->close();
 }
 
 }  // namespace vgh

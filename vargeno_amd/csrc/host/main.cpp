@@ -40,6 +40,12 @@
 //                         Tab-separated: ##sites, ##min_gq, one ##sample line each (called = counted sites, het = counted hets), then per
 //                         pair a < b in manifest order n, ibs0, ibs2, hethet, het_a, het_b (csrc/vg_pairs.h), concordance = ibs2 / n and
 //                         relatedness = (hethet - 2 ibs0) / min(het_a, het_b), `nan` over a zero denominator
+//   VARGENO_VCF_BGZF=device|host  geno, cohort, joint: the VCF (every sample's, the joint one; not the pair table) is written as BGZF, the
+//                         `.vcf.gz` that bcftools / tabix / htslib read: exactly vg_bgzf_deflate_host(the whole VCF text, blocks of 65 280
+//                         bytes, the end-of-file marker) on either route.  `device`: spans of the text are deflated by the deflate kernel on
+//                         replica 0's device while the next span is being made (no device memory for a span: the host loop takes the rest
+//                         of the file, one line under VARGENO_VERBOSE); `host`: by VARGENO_BGZF_THREADS host threads.  Unset or empty:
+//                         plain text, as the reference writes it.  Any other value is refused before a device is touched
 //   VARGENO_PAIRS_MIN_GQ=n  the table counts a call iff it is called and its GQ is at least n (default 0)
 //   VARGENO_VERBOSE=1     stderr: the index plan and start-up report, one "ingest, replica g:" line per route taken, the "reads:" line with
 //                         the wall time phase by phase; index: the "cuts:" line
@@ -48,6 +54,10 @@
 //   VARGENO_FQPIPE_QUIET=1  the hidden `fqpipe` command counts the reads and prints a rate instead of one line per record
 //   VARGENO_NO_LITE=1     index: skip <prefix>.ref.bf.lite.bf (2.3 GB, read by nothing in geno)
 //   VARGENO_THREADS=n     index: threads (default: all); joint: threads of the pair table's host loop
+// Hidden commands of the BGZF routes (tests and measurements; main() has the others):
+//   bgzfcat <in>         a BGZF file's text on stdout (the host threads of the BGZF input route)
+//   bgzfzip <in> <out> [block]  <in> written as BGZF to <out>, `block` text bytes per block (default 65 280), by the route
+//                         VARGENO_VCF_BGZF names (default `host`; `device` needs one): the sink the three commands write their VCF through
 // Where `index` cuts its work (host/index_build.cpp; numbers clamped to >= 1, defaults unchanged when unset -- tests make them
 // tiny so that every boundary falls inside sequences, N runs and repeat copies; VARGENO_VERBOSE=1 prints one "cuts:" line
 // with what the build actually did; every chunk costs 48 KiB of bucket counters, so tiny chunks are for small inputs):
@@ -113,6 +123,15 @@ static GzipRoute gzip_route()
 	static const GzipRoute r = [] { const std::string v = env_str("VARGENO_GZIP"); return v == "host" ? GzipRoute::Host : v == "device" ? GzipRoute::Device : GzipRoute::Refuse; }();
 	return r;
 }
+// VARGENO_VCF_BGZF, read once: Off (unset or empty), Host, Device.  false: another value -- said on stderr, in one line
+static bool vcf_bgzf_route(vgh::VcfBgzf *route)
+{
+	const std::string v = env_str("VARGENO_VCF_BGZF");
+	*route = v == "host" ? vgh::VcfBgzf::Host : v == "device" ? vgh::VcfBgzf::Device : vgh::VcfBgzf::Off;
+	if (v.empty() || *route != vgh::VcfBgzf::Off) return true;
+	fprintf(stderr, "vargeno: VARGENO_VCF_BGZF=%s is not understood: `device` or `host` writes the VCF as BGZF, unset writes plain text\n", v.c_str());
+	return false;
+}
 // CPUs this process may use: the hardware threads, capped by a cgroup CPU quota (cpu.max: "<quota> <period>"; this pool's GPU boxes
 // give a container 16 CPUs' worth of time on a 256-thread host)
 static int usable_cpus()
@@ -165,6 +184,9 @@ struct GenoOptions {
 	const std::string joint_pairs = env_str("VARGENO_JOINT_PAIRS");
 	const int pairs_min_gq = env_int("VARGENO_PAIRS_MIN_GQ", 0);
 	const int pairs_threads = std::max(1, env_int("VARGENO_THREADS", usable_cpus()));
+	// how the VCF is written (VARGENO_VCF_BGZF; main() has refused a value that is neither `device` nor `host`): on replica 0's
+	// device, which is device 0, or on the BGZF threads
+	const vgh::VcfOutput vcf_out = [this] { vgh::VcfOutput w; (void)vcf_bgzf_route(&w.bgzf); w.device = 0; w.threads = bgzf_threads; w.verbose = verbose; return w; }();
 	explicit GenoOptions(int devices) : have(devices)
 	{
 		if (ngpu > have && !share) ngpu = have;
@@ -1167,7 +1189,7 @@ static int run_geno(const std::string &prefix, const std::string &fastq, const s
 	bool have_calls = false;
 	if (!fetch_counts(o, ix, sc, calls, have_calls)) return EXIT_FAILURE;
 	if (vcf_reader.joinable()) vcf_reader.join();
-	vgh::write_genotyped_vcf(sc, chrlens, vcf_in, vcf_out, vcf_ok ? &vcf_text : nullptr, have_calls ? &calls : nullptr);
+	vgh::write_genotyped_vcf(sc, chrlens, vcf_in, vcf_out, vcf_ok ? &vcf_text : nullptr, have_calls ? &calls : nullptr, o.vcf_out);
 	clock_gettime(CLOCK_MONOTONIC, &t[3]);
 	// The output is complete and closed.  What is left is giving back ~240 GB of device memory and the page-locked buffers, which the
 	// operating system does for a process that ends anyway: an orderly vg_index_close + runtime shut-down took 0.7 + 0.9 s of an
@@ -1314,7 +1336,7 @@ static int run_cohort(const std::string &prefix, const std::string &manifest, co
 			return true;
 		}
 		sc.pos = sites.pos; sc.ref_freq = sites.ref_freq; sc.alt_freq = sites.alt_freq;
-		try { vgh::write_genotyped_vcf(sc, chrlens, vcf_in, s.out, &vcf_text, have_calls ? &calls : nullptr); }
+		try { vgh::write_genotyped_vcf(sc, chrlens, vcf_in, s.out, &vcf_text, have_calls ? &calls : nullptr, o.vcf_out); }
 		catch (const vgh::Error &e) { fprintf(stderr, "vargeno: %s line %d: %s\n", manifest.c_str(), s.line, e.msg.c_str()); return false; }
 		return true;
 	};
@@ -1395,7 +1417,7 @@ static int run_cohort(const std::string &prefix, const std::string &manifest, co
 	for (auto &t : th) t.join();
 	if (joint && !failed.load()) {
 		try {
-			vgh::write_joint_vcf(sites.pos, chrlens, columns, vcf_in, *joint_out, &vcf_text);
+			vgh::write_joint_vcf(sites.pos, chrlens, columns, vcf_in, *joint_out, &vcf_text, o.vcf_out);
 			if (!o.joint_pairs.empty()) joint_pairs_table(o, 0, columns, sites.pos.size());      // (replica 0 sits on device 0)
 		}
 		catch (const vgh::Error &e) { fprintf(stderr, "vargeno: %s\n", e.msg.c_str()); failed.store(1); }
@@ -1426,6 +1448,8 @@ int main(int argc, const char *argv[])
 	if (argc < 2) { print_help(); return 0; }
 	const std::string opt = argv[1];
 	try {
+		vgh::VcfBgzf vcf_bgzf;
+		if ((opt == "geno" || opt == "cohort" || opt == "joint" || opt == "bgzfzip") && !vcf_bgzf_route(&vcf_bgzf)) return EXIT_FAILURE;      // (before anything else is looked at)
 		if (opt == "index") {
 			arg_check(argc, 3);
 			vgh::IndexOptions io;
@@ -1460,6 +1484,37 @@ int main(int argc, const char *argv[])
 			}
 			bp.finish();
 			if (!bp.error.empty()) throw vgh::Error{bp.error};
+			return EXIT_SUCCESS;
+		} else if (opt == "bgzfzip") {
+			// hidden: a file written as BGZF through the sink that `geno`, `cohort` and `joint` write their VCF through (the host route
+			// needs no device; tests/test_deflate_cpu.py)
+			if (argc != 4 && argc != 5) { print_help(); return EXIT_FAILURE; }
+			vgh::VcfOutput how;
+			how.bgzf = vcf_bgzf == vgh::VcfBgzf::Device ? vgh::VcfBgzf::Device : vgh::VcfBgzf::Host;
+			how.threads = std::max(1, std::min(env_int("VARGENO_BGZF_THREADS", vgh::bgzf_threads_default(usable_cpus())), 256));
+			how.verbose = env_int("VARGENO_VERBOSE", 0) != 0;
+			const long block = argc == 5 ? atol(argv[4]) : 0;
+			if (block < 0 || block > 65280) throw vgh::Error{"bgzfzip: a block holds 1 to 65280 bytes of text (0: 65280)"};
+			how.block = (uint32_t)block;
+			if (how.bgzf == vgh::VcfBgzf::Device && vg_device_count() <= 0) { fprintf(stderr, "vargeno: no HIP device found (VARGENO_VCF_BGZF=host compresses on the host)\n"); return EXIT_FAILURE; }
+			const int fd = open(argv[2], O_RDONLY);
+			if (fd < 0) throw vgh::Error{std::string("cannot open ") + argv[2]};
+			struct timespec a, b; clock_gettime(CLOCK_MONOTONIC, &a);
+			const std::unique_ptr<vgh::VcfSink> sink = vgh::open_vcf_sink(argv[3], how);
+			std::vector<char> buf(8 << 20);
+			uint64_t total = 0;
+			for (;;) {                                                    // 8 MiB of the file per step
+				const ssize_t n = read(fd, buf.data(), buf.size());
+				if (n < 0 && errno == EINTR) continue;
+				if (n < 0) throw vgh::Error{std::string("error reading ") + argv[2]};
+				if (n == 0) break;
+				sink->write(buf.data(), (size_t)n);
+				total += (uint64_t)n;
+			}
+			close(fd);
+			sink->close();
+			clock_gettime(CLOCK_MONOTONIC, &b);
+			if (how.verbose) fprintf(stderr, "bgzfzip: %s route, %.3f GB of text in %.3f s (%.2f GB/s)\n", how.bgzf == vgh::VcfBgzf::Device ? "device" : "host", (double)total / 1e9, secs(a, b), (double)total / 1e9 / std::max(1e-9, secs(a, b)));
 			return EXIT_SUCCESS;
 		} else if (opt == "gzcat") {
 			// hidden: a plain gzip file's text on stdout, by the host build of the decoder alone (no device needed; tests/test_gzip_cpu.py)

@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <memory>
 #include <string>
 #include <utility>
 #include <vector>
@@ -164,6 +165,27 @@ struct SiteCounts {
 	std::vector<uint32_t> pos;                     // 1-based over the concatenated genome, ascending
 	std::vector<uint8_t> ref_freq, alt_freq, ref_cnt, alt_cnt;
 };
+// ---- where VCF text goes: a plain file, or a BGZF file (VARGENO_VCF_BGZF) ----
+// The BGZF file is vg_bgzf_deflate_host(the whole text, block, eof 1), byte for byte, on either route: the text is gathered into
+// spans that are multiples of the block (the last one shorter), and a thread of the sink compresses one span -- on `device`
+// (vg_bgzf_deflate_device: upload, kernels, read-back) or on `threads` host threads -- and writes it while the next is being
+// made; two spans wait at most.  A device without memory for a span (VG_ENOMEM) hands the rest of the file to the host loop, one
+// line under `verbose`.
+enum class VcfBgzf { Off, Host, Device };
+struct VcfOutput {
+	VcfBgzf bgzf = VcfBgzf::Off;
+	int device = 0, threads = 1;
+	uint32_t block = 0;                            // text bytes per BGZF block; 0: 65 280
+	bool verbose = false;
+};
+class VcfSink {
+public:
+	virtual ~VcfSink() {}                          // a sink that is destroyed unclosed leaves its file without the end-of-file marker
+	virtual void write(const char *p, size_t n) = 0;
+	virtual void close() = 0;                      // the last bytes (BGZF: and the marker) are in the file; throws Error when it could not be written
+};
+std::unique_ptr<VcfSink> open_vcf_sink(const std::string &path, const VcfOutput &how);      // throws Error when the file cannot be created
+
 // returns {ref calls, alt calls, het calls}
 struct CallSummary { uint64_t ref = 0, alt = 0, het = 0; };
 // one call per site: gt = GT_*, gq as the reference prints it (0 where gt is GT_NONE)
@@ -172,12 +194,13 @@ void call_sites(const SiteCounts &s, SiteCalls &out);                           
 // vcf_text: the SNP list's bytes if the caller has read them already (the command line reads them while the index is being opened)
 // calls: the sites' calls if the caller has them already (vg_sample_calls_fetch); the counters of `s` are not looked at then
 CallSummary write_genotyped_vcf(const SiteCounts &s, const std::vector<ChrLen> &chrlens,
-                                const std::string &vcf_in, const std::string &vcf_out, const std::string *vcf_text = nullptr, const SiteCalls *calls = nullptr);
+                                const std::string &vcf_in, const std::string &vcf_out, const std::string *vcf_text = nullptr, const SiteCalls *calls = nullptr,
+                                const VcfOutput &how = VcfOutput());
 // One multi-sample VCF: a line per record that at least one sample's own VCF would contain, a column per sample in the given order.
 // Throws when the SNP list cannot be read or the file cannot be written.
 struct JointSample { std::string name; SiteCalls calls; };
 void write_joint_vcf(const std::vector<uint32_t> &pos, const std::vector<ChrLen> &chrlens, const std::vector<JointSample> &samples,
-                     const std::string &vcf_in, const std::string &vcf_out, const std::string *vcf_text = nullptr);
+                     const std::string &vcf_in, const std::string &vcf_out, const std::string *vcf_text = nullptr, const VcfOutput &how = VcfOutput());
 bool read_whole_file(const std::string &path, std::string &text);
 
 }  // namespace vgh

@@ -13,6 +13,7 @@
 #include "vg_allreduce_plan.h"
 #include "vg_arena.h"
 #include "vg_inflate.h"
+#include "vg_deflate.h"
 #include "vg_bam.h"
 #include "vg_gunzip.h"
 #include "vg_caller.h"
@@ -1049,6 +1050,95 @@ __global__ __launch_bounds__(64) void vg_bgzf_inflate_kernel(const uint8_t *__re
 	if (io.ln == 0) {
 		status[b] = (uint32_t)rc;
 		if (rc != VG_INF_OK) atomicMin(bad_key, (unsigned long long)blk.comp_off << 4 | (unsigned long long)rc);
+	}
+}
+
+// ------------------------------------------------------------------------------------------------
+// kernels: text deflated into BGZF blocks on the device (vg_deflate.h is the compressor; this is its wave policy)
+//
+// ONE WAVE PER BGZF BLOCK, one-wave workgroups, as above: blocks share no window, so a chunk of text is some thousand independent
+// waves.  A lane owns one position of each group of 64: it hashes the four bytes there, measures the match against the table's
+// candidate, forms the position's code if the group's scan emits it, and ORs the code's bits into the staging window at the
+// offset the wave's prefix sum of the bit lengths gives it.  The text is read where it was uploaded (a block's 64 KiB stay in
+// the caches for the few hundred groups that look back into them); only the tables live in LDS.
+//
+// LDS per workgroup (DfShared, 20 872 B: seven blocks per CU of 160 KiB):
+//   hash  16 384        one word per hash value: position + 1 of the greatest position entered before the group (ds_max_u32)
+//   stage    264        the group's bits (ds_or_b32); whole words leave for the block's slot in global memory, the rest is carried
+//   mlen     128        the group's match lengths, read by the scan
+//   crc    4 096        slicing-by-4 table (each lane a slice of the text, combined by x^(8n) mod P)
+// The payload's length is known only when the block is done, so a block writes into a slot of its own (text bytes + VG_DEF_SLACK)
+// and reports (payload bytes or 0 = stored, CRC32); the host sums the lengths and vg_bgzf_frame_kernel moves header, payload (or
+// the stored text) and trailer to the block's place in the file.
+// ------------------------------------------------------------------------------------------------
+struct DfShared {
+	VgDefShared d;
+	VgCrcTab crc;
+};
+
+struct DefWaveIO {
+	static constexpr uint32_t LANES = 64;
+	uint32_t ln;
+	__device__ __forceinline__ uint32_t lane() const { return ln; }
+	__device__ __forceinline__ static uint32_t lanes() { return 64; }
+	__device__ __forceinline__ static void sync() { __syncthreads(); }
+	__device__ __forceinline__ static uint32_t u(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
+	__device__ __forceinline__ static uint64_t ballot(uint64_t mine) { return __ballot(mine != 0); }       // (a lane's own bit is bit `lane`)
+	__device__ __forceinline__ uint32_t scan(const uint32_t *v, uint32_t *off) const
+	{
+		uint32_t x = v[0];
+		for (uint32_t d = 1; d < 64; d <<= 1) { const uint32_t y = (uint32_t)__shfl_up((int)x, d); if (ln >= d) x += y; }     // 6 steps
+		off[0] = x - v[0];
+		return u((uint32_t)__shfl((int)x, 63));
+	}
+	__device__ __forceinline__ static void max32(uint32_t *p, uint32_t v) { atomicMax(p, v); }
+	__device__ __forceinline__ static void or32(uint32_t *p, uint32_t v) { atomicOr(p, v); }
+};
+
+// text [0, nbytes) in blocks of `block` bytes (the last one shorter).  grid = blocks.  meta[b] = (payload bytes in the block's slot,
+// or 0: store the block; CRC32 of its text).  A slot has slot_words words: at least (block + VG_DEF_SLACK) / 4.
+__global__ __launch_bounds__(64) void vg_bgzf_deflate_kernel(const uint8_t *__restrict__ text, uint64_t nbytes, uint32_t block, uint32_t n_blocks,
+                                                            uint32_t *__restrict__ slots, uint32_t slot_words, uint2 *__restrict__ meta)
+{
+	__shared__ DfShared sh;
+	const uint32_t b = blockIdx.x;
+	if (b >= n_blocks) return;
+	const uint64_t at = (uint64_t)b * block;
+	const uint32_t n = (uint32_t)min((uint64_t)block, nbytes - at);
+	const uint8_t *t = text + at;
+	DefWaveIO io;
+	io.ln = threadIdx.x;
+	vg_crc_tab_build(io, sh.crc);
+	const uint32_t coded = vg_deflate_block(io, sh.d, t, n, slots + (uint64_t)b * slot_words);
+	uint32_t x = vg_crc32_share(sh.crc, t, n, io.ln, 64);
+	for (int o = 32; o > 0; o >>= 1) x ^= __shfl_xor(x, o);
+	if (io.ln == 0) meta[b] = make_uint2(coded, x);
+}
+
+// grid = blocks.  Block b of the file goes to out + offs[b]: header, payload from its slot (or 01 LEN NLEN and the text), CRC32, ISIZE.
+__global__ __launch_bounds__(64) void vg_bgzf_frame_kernel(const uint8_t *__restrict__ text, uint64_t nbytes, uint32_t block, uint32_t n_blocks,
+                                                          const uint32_t *__restrict__ slots, uint32_t slot_words, const uint2 *__restrict__ meta,
+                                                          const uint64_t *__restrict__ offs, uint8_t *__restrict__ out)
+{
+	const uint32_t b = blockIdx.x, ln = threadIdx.x;
+	if (b >= n_blocks) return;
+	const uint64_t at = (uint64_t)b * block;
+	const uint32_t n = (uint32_t)min((uint64_t)block, nbytes - at);
+	const uint8_t *t = text + at, *slot = (const uint8_t *)(slots + (uint64_t)b * slot_words);
+	const uint32_t coded = meta[b].x, crc = meta[b].y;
+	const uint32_t payload = coded ? coded : n + 5u, total = VG_BGZF_HEADER + payload + VG_BGZF_TRAILER;
+	uint8_t *dst = out + offs[b];
+	for (uint32_t i = ln; i < total; i += 64) {                       // 64 bytes of the block per iteration
+		uint8_t v;
+		if (i < VG_BGZF_HEADER) v = vg_bgzf_header_byte(i, payload);
+		else if (i < VG_BGZF_HEADER + payload) {
+			const uint32_t j = i - VG_BGZF_HEADER;
+			v = coded ? slot[j] : j < 5 ? vg_def_stored_byte(j, n) : t[j - 5];
+		} else {
+			const uint32_t j = i - VG_BGZF_HEADER - payload;
+			v = (uint8_t)((j < 4 ? crc : n) >> (8u * (j & 3u)));
+		}
+		dst[i] = v;
 	}
 }
 
@@ -3904,6 +3994,145 @@ extern "C" int vg_bgzf_inflate_device(int device, const uint8_t *bgzf, uint64_t 
 		if (key != ~0ull) { *bad_block_offset = key >> 4; *consumed = key >> 4; (void)fail(VG_EIO, "%s", bz_describe(key).c_str()); }
 		else if (hdr_rc) { *bad_block_offset = bad; (void)fail(VG_EIO, "BGZF block at compressed offset %s: not a BGZF block header", std::to_string(bad).c_str()); }
 		return VG_OK;
+	});
+}
+
+// ---- text -> BGZF without a handle (vg_deflate.h: the same compressor on host threads and on the device; the same bytes) ----------
+static int bz_deflate_args(const uint8_t *text, uint64_t nbytes, uint32_t block, const uint8_t *bgzf, const uint64_t *bgzf_len)
+{
+	if ((!text && nbytes) || !bgzf || !bgzf_len) return fail(VG_EINVAL, "null argument");
+	if (block > VG_BGZF_TEXT_BLOCK) return fail(VG_EINVAL, "a BGZF block holds at most 65280 bytes of text here");
+	return VG_OK;
+}
+// The blocks are made in `work`: the caller's buffer when it holds the worst case, else a buffer of our own -- so that a capacity
+// that turns out too small leaves the caller's bytes alone.
+struct BzDeflateOut {
+	uint8_t *bgzf; uint64_t cap, bound;
+	std::vector<uint8_t> own;
+	uint8_t *work = nullptr;
+	BzDeflateOut(uint8_t *bgzf_, uint64_t cap_, uint64_t bound_) : bgzf(bgzf_), cap(cap_), bound(bound_)
+	{
+		if (cap >= bound) work = bgzf;
+		else { own.resize((size_t)bound); work = own.data(); }
+	}
+	int deliver(uint64_t len, int eof, uint64_t *bgzf_len)
+	{
+		if (eof) { memcpy(work + len, vg_bgzf_eof_marker(), VG_BGZF_EOF_BYTES); len += VG_BGZF_EOF_BYTES; }
+		if (work != bgzf) {
+			if (len > cap) return fail(VG_ETOOBIG, "the BGZF blocks do not fit the caller's buffer (vg_bgzf_deflate_bound says what always does)");
+			memcpy(bgzf, work, (size_t)len);
+		}
+		*bgzf_len = len;
+		return VG_OK;
+	}
+};
+
+extern "C" uint64_t vg_bgzf_deflate_bound(uint64_t nbytes, uint32_t block)
+{
+	return block > VG_BGZF_TEXT_BLOCK ? 0 : vg_bgzf_bound(nbytes, block ? block : VG_BGZF_TEXT_BLOCK);
+}
+
+extern "C" int vg_bgzf_deflate_host(const uint8_t *text, uint64_t nbytes, uint32_t block, int eof, int threads, uint8_t *bgzf, uint64_t cap, uint64_t *bgzf_len)
+{
+	const int rc = bz_deflate_args(text, nbytes, block, bgzf, bgzf_len);
+	if (rc) return rc;
+	return guarded([&]() -> int {
+		const uint32_t B = block ? block : VG_BGZF_TEXT_BLOCK;
+		const uint64_t nb = vg_bgzf_blocks_of(nbytes, B), stride = (uint64_t)B + 5 + VG_BGZF_HEADER + VG_BGZF_TRAILER;
+		BzDeflateOut out(bgzf, cap, vg_bgzf_bound(nbytes, B));
+		std::vector<uint32_t> size((size_t)nb);
+		// every block at its worst-case place (they are independent: any thread, any order), then moved down into a file
+		std::atomic<uint64_t> next{0};
+		std::atomic<bool> no_memory{false};
+		auto work = [&] {
+			try {
+				std::unique_ptr<VgDefShared> sh(new VgDefShared);
+				std::vector<uint32_t> slot((B + VG_DEF_SLACK) / 4 + 1);
+				for (;;) {                                                // 16 blocks per step
+					const uint64_t b0 = next.fetch_add(16);
+					if (b0 >= nb) break;
+					for (uint64_t b = b0; b < std::min(nb, b0 + 16); b++) {
+						const uint32_t n = (uint32_t)std::min<uint64_t>(B, nbytes - b * B);
+						size[(size_t)b] = vg_bgzf_deflate_block_host(text + b * B, n, out.work + b * stride, *sh, slot.data());
+					}
+				}
+			} catch (const std::bad_alloc &) { no_memory = true; }
+		};
+		const int nt = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)std::max(1, std::min(threads, 256)), (nb + 15) / 16));
+		if (nt == 1) work();
+		else {
+			std::vector<std::thread> th;
+			for (int t = 0; t < nt; t++) th.emplace_back(work);
+			for (auto &x : th) x.join();
+		}
+		if (no_memory) return fail(VG_ENOMEM, "host allocation failed");
+		uint64_t len = 0;
+		for (uint64_t b = 0; b < nb; b++) { if (b) memmove(out.work + len, out.work + b * stride, size[(size_t)b]); len += size[(size_t)b]; }
+		return out.deliver(len, eof, bgzf_len);
+	});
+}
+
+extern "C" int vg_bgzf_deflate_device(int device, const uint8_t *text, uint64_t nbytes, uint32_t block, int eof, uint8_t *bgzf, uint64_t cap, uint64_t *bgzf_len)
+{
+	int rc = bz_deflate_args(text, nbytes, block, bgzf, bgzf_len);
+	if (rc) return rc;
+	int ndev = 0;
+	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(VG_ENODEV, "no HIP device available (vg_bgzf_deflate_host is the host's compressor)");
+	return guarded([&]() -> int {
+		const uint32_t B = block ? block : VG_BGZF_TEXT_BLOCK;
+		const uint64_t nb = vg_bgzf_blocks_of(nbytes, B);
+		HIP_TRY(hipSetDevice(device));
+		// chunks of at most 64 MiB of text and 65 536 blocks: the device buffers are sized by a chunk, not by the text
+		const uint64_t chunk_blocks = std::min<uint64_t>(std::max<uint64_t>(1, nb), std::min<uint64_t>(65536, std::max<uint64_t>(1, (64ull << 20) / B)));
+		const uint32_t slot_words = ((B + VG_DEF_SLACK + 15u) & ~15u) / 4;
+		const uint64_t chunk_out = vg_bgzf_bound(chunk_blocks * B, B);
+		DevBuf<uint8_t> d_text, d_out; DevBuf<uint32_t> d_slots; DevBuf<uint2> d_meta; DevBuf<uint64_t> d_offs;
+		if (nb && ((rc = d_text.reserve(chunk_blocks * B + 16, "text")) || (rc = d_slots.reserve(chunk_blocks * slot_words, "deflate slots")) || (rc = d_meta.reserve(chunk_blocks, "block results"))
+		           || (rc = d_offs.reserve(chunk_blocks, "block offsets")) || (rc = d_out.reserve(chunk_out, "BGZF bytes")))) return rc;
+		BzDeflateOut out(bgzf, cap, vg_bgzf_bound(nbytes, B));
+		std::vector<uint2> meta((size_t)chunk_blocks);
+		std::vector<uint64_t> offs((size_t)chunk_blocks);
+		const bool timed = getenv("VG_VERBOSE") != nullptr;
+		hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
+		if (timed) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); HIP_TRY(hipEventCreate(&e2)); }
+		float ms_deflate = 0, ms_frame = 0;
+		uint64_t len = 0;
+		for (uint64_t b0 = 0; b0 < nb; b0 += chunk_blocks) {                   // one chunk per step
+			const uint32_t k = (uint32_t)std::min(chunk_blocks, nb - b0);
+			const uint64_t t0 = b0 * B, tn = std::min<uint64_t>((uint64_t)k * B, nbytes - t0);
+			HIP_TRY(hipMemcpy(d_text.p, text + t0, tn, hipMemcpyHostToDevice));
+			if (timed) HIP_TRY(hipEventRecord(e0, nullptr));
+			vg_bgzf_deflate_kernel<<<k, 64>>>(d_text.p, tn, B, k, d_slots.p, slot_words, d_meta.p);
+			HIP_TRY(hipGetLastError());
+			if (timed) HIP_TRY(hipEventRecord(e1, nullptr));
+			HIP_TRY(hipMemcpy(meta.data(), d_meta.p, (size_t)k * sizeof(uint2), hipMemcpyDeviceToHost));
+			uint64_t sum = 0;
+			bool sane = true;
+			for (uint32_t i = 0; i < k; i++) {
+				const uint32_t n = (uint32_t)std::min<uint64_t>(B, tn - (uint64_t)i * B);
+				sane = sane && meta[i].x < n;                                  // (the core stores a block that would not shrink)
+				offs[i] = sum;
+				sum += VG_BGZF_HEADER + (meta[i].x ? meta[i].x : n + 5u) + VG_BGZF_TRAILER;
+			}
+			if (!sane || sum > chunk_out) return fail(VG_EIO, "the deflate kernel reported a block that is not shorter than its text");
+			HIP_TRY(hipMemcpy(d_offs.p, offs.data(), (size_t)k * sizeof(uint64_t), hipMemcpyHostToDevice));
+			vg_bgzf_frame_kernel<<<k, 64>>>(d_text.p, tn, B, k, d_slots.p, slot_words, d_meta.p, d_offs.p, d_out.p);
+			HIP_TRY(hipGetLastError());
+			if (timed) {
+				HIP_TRY(hipEventRecord(e2, nullptr)); HIP_TRY(hipEventSynchronize(e2));
+				float a = 0, c = 0;
+				HIP_TRY(hipEventElapsedTime(&a, e0, e1)); HIP_TRY(hipEventElapsedTime(&c, e1, e2));
+				ms_deflate += a; ms_frame += c;
+			}
+			HIP_TRY(hipMemcpy(out.work + len, d_out.p, sum, hipMemcpyDeviceToHost));
+			len += sum;
+		}
+		if (timed) {
+			fprintf(stderr, "[vargeno_hip] bgzf deflate: %llu blocks, %.3f ms deflate kernel (%.2f GB/s text), %.3f ms framing (incl. the lengths' round trip), ratio %.3f\n", (unsigned long long)nb, ms_deflate,
+			        ms_deflate > 0 ? nbytes / 1e6 / ms_deflate : 0.0, ms_frame, nbytes ? (double)len / (double)nbytes : 0.0);
+			(void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipEventDestroy(e2);
+		}
+		return out.deliver(len, eof, bgzf_len);
 	});
 }
 
