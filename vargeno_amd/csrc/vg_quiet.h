@@ -50,3 +50,14 @@ VG_QUIET_HD inline bool vg_quiet_key(uint32_t bits, uint32_t c, uint32_t n)
 {
 	return n >= 2u && n <= 4u && c < n && (c == 0u || (bits & VG_QUIET_A)) && (c == n - 1u || (bits & VG_QUIET_B));
 }
+
+// The same proof chunk by chunk: bit j of the result = the window [key + 32 j, key + 32 j + 32) of chunk j of that read, key = kpos - 32 c,
+// is known to be free of sites.  A covers [kpos - 96, kpos + 32), which holds the windows of chunks 0 .. c (c <= 3); B covers
+// [kpos, kpos + 128), which holds those of chunks c .. n - 1.  Neither bit, or a read of another length: 0.  Masks of several exact
+// contexts of one key may be ORed; vg_quiet_key(bits, c, n) is vg_quiet_chunks(bits, c, n) == (1 << n) - 1.
+VG_QUIET_HD inline uint32_t vg_quiet_chunks(uint32_t bits, uint32_t c, uint32_t n)
+{
+	if (n < 2u || n > 4u || c >= n) return 0u;
+	const uint32_t upto_c = (2u << c) - 1u, all = (1u << n) - 1u;
+	return ((bits & VG_QUIET_A) ? upto_c : 0u) | ((bits & VG_QUIET_B) ? all & ~(upto_c >> 1) : 0u);
+}

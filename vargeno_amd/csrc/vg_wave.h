@@ -152,17 +152,21 @@ __device__ __forceinline__ void vg_wave_body(const DevIndex &d, const uint64_t *
 	// distinct (`vargeno index` skips ALT = REF records, dictgen.c:745), so a chunk cannot vote twice for a key with exact contexts;
 	// should a hand-made index do it anyway the read is passed on, down to the lane machine, which keeps contexts one by one.
 	// The main tier's masks are 16 bits wide (reads of more than 16 chunks -- 543 bases -- start in the next tier).
-	// QUIET KEYS: for a read of n <= 4 chunks the TOP bit of a key's mask (KQUIET; a chunk bit only for reads of 16 / 32 chunks) says
-	// that the key's whole window [key, key + 32 n) is known to hold no SNP site, so the fast walk of stage C, which would fire no
-	// atomic, is skipped when such a key wins.  The proof comes with the records stage A fetches anyway: a single-position
-	// reference entry of the direct table / merged view carries two bits (vg_quiet.h), and an exact context of chunk c proves its
-	// key quiet iff (c == 0 || A) && (c == n - 1 || B); one proof from any of the key's exact contexts is enough, so the bit is
-	// ORed into the mask where the chunk's bit is.  Kept in the mask because that costs no register and no LDS, in both tiers; the
-	// bit rides along where masks are copied or have chunk bits ORed in, and is masked out where the mask is counted or scanned
-	// (the vote: chunk bits of a read of n <= 4 chunks are bits 0-3).
+	// FREE CHUNKS: for a read of n <= 4 chunks bits 4-7 of a key's mask (KFREE; chunk bits only for longer reads, which never set them
+	// this way) say, chunk by chunk, that the window [key + 32 j, key + 32 j + 32) of chunk j is known to hold no SNP site.  The proof
+	// comes with the records stage A fetches anyway: a single-position reference entry of the direct table / merged view carries two
+	// bits (vg_quiet.h), and an exact context of chunk c proves chunks 0 .. c free with A and chunks c .. n - 1 with B
+	// (vg_quiet_chunks); the proofs of all of a key's exact contexts are ORed into the mask where the chunk's bit is.  Two readers:
+	//   * stage C: a winner whose n chunks are all free has a window without a site, so the fast walk, which would fire no atomic,
+	//     is skipped (the "quiet key"; two contexts may share the proof);
+	//   * stage B: a gate-open pair that can neither change the vote's outcome nor lie over a window that may hold a site is not
+	//     expanded at all (the rule where `pend` is formed).
+	// Kept in the mask because that costs no register and no LDS, in both tiers; the bits ride along where masks are copied or have
+	// chunk bits ORed in, and are masked out where the mask is counted or scanned (the vote: chunk bits of a read of n <= 4 chunks
+	// are bits 0-3).
 	using kmask_t = typename KMask<(WPB > 1)>::type;
 	constexpr uint32_t KMASK_CHUNKS = WPB > 1 ? 16u : 32u;
-	constexpr uint32_t KQUIET = 1u << (KMASK_CHUNKS - 1u);
+	constexpr uint32_t KFREE = 4u;                       // shift of the free-chunk bits of a read of n <= 4 chunks
 	__shared__ uint32_t K_idx[W_ECAP][64 * WPB], N_kpos[W_NCAP][64 * WPB];
 	__shared__ kmask_t K_mask[W_ECAP][64 * WPB];
 	__shared__ uint16_t N_meta[W_NCAP][64 * WPB];
@@ -406,7 +410,7 @@ __device__ __forceinline__ void vg_wave_body(const DevIndex &d, const uint64_t *
 				return e;
 			};
 			// hf: the hit's flags as the direct-table look-up has them (1 hit, 2 ambiguous, 4 PAIR, 64 / 128 the entry's quiet bits); 0 elsewhere
-			auto quiet_bit = [&](uint32_t hf, uint32_t c) -> uint32_t { return (hf & 6u) == 0u && vg_quiet_key(hf, c, n) ? KQUIET : 0u; };
+			auto quiet_bit = [&](uint32_t hf, uint32_t c) -> uint32_t { return (hf & 6u) == 0u ? vg_quiet_chunks(hf, c, n) << KFREE : 0u; };
 			auto push_exact = [&](uint32_t p, uint32_t c, uint32_t hf = 0u) {
 				cur.add(S_CTX, 1);
 				if (ovf) return;
@@ -815,7 +819,28 @@ __device__ __forceinline__ void vg_wave_body(const DevIndex &d, const uint64_t *
 #else
 			const bool hopeless = !STATS && kcnt == 0;
 #endif
-			const uint32_t pend = (active && !ovf && !hopeless) ? (n >= 32 ? gates : (gates & ((1u << n) - 1u))) : 0u;
+			uint32_t pend = (active && !ovf && !hopeless) ? (n >= 32 ? gates : (gates & ((1u << n) - 1u))) : 0u;
+			// Pairs that cannot change a counter (timed build, reads of n <= 4 chunks; F = a key's free-chunk bits, see the key table):
+			//   R1  pass 1 and every key has all n chunks free: the read ends after this pass whatever the vote does, a winner is one of
+			//       the keys (neighbours open none), and its window holds no site -- no pair is expanded;
+			//   R2  one key, with exact contexts of two chunks: it is live and nothing can tie with it, so the pass is processed with it
+			//       whatever stage B finds; a neighbour context of chunk c is walked over [key + 32 c, key + 32 c + 32) only -- the pairs of
+			//       the chunks in F are not expanded.
+			// Not pruned: one key with one exact chunk (neighbours decide whether it becomes live), several keys in pass 0 (neighbours
+			// decide ties and thereby the retry).  A pruned pair cannot overflow a list either: every tier is exact.
+#ifndef VG_NO_PAIR_PRUNE
+			if constexpr (!STATS && !NOMX) if (pend && n <= 4u) {
+				const uint32_t full = (1u << n) - 1u;
+				if (kcnt == 1u) {
+					const uint32_t mq = K_mask[0][col], m = mq & 15u, F = (mq >> KFREE) & full;
+					if ((pass == 1u && F == full) || (m & (m - 1u))) pend &= ~F;
+				} else if (pass == 1u) {
+					uint32_t F = full;
+					for (uint32_t e = 0; e < kcnt; e++) F &= (uint32_t)K_mask[e][col] >> KFREE;
+					if (F == full) pend = 0u;
+				}
+			}
+#endif
 			const uint32_t my_np = (uint32_t)__popc(pend);
 			uint32_t pincl = my_np;
 			for (int o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(pincl, o); if ((int)lane >= o) pincl += y; }
@@ -1353,7 +1378,7 @@ __device__ __forceinline__ void vg_wave_body(const DevIndex &d, const uint64_t *
 				uint32_t bestf = 0, target = 0, bmask = 0;
 				bool bquiet = false;                                         // the winning key's window holds no SNP site (see the key table's description)
 				for (uint32_t e = 0; e < kcnt; e++) {
-					const uint32_t idx = K_idx[e][col], mq = K_mask[e][col], m = n <= 4u ? mq & 15u : mq;   // (n <= 4: the top bit is KQUIET, no chunk)
+					const uint32_t idx = K_idx[e][col], mq = K_mask[e][col], m = n <= 4u ? mq & 15u : mq;   // (n <= 4: bits 4-7 are the free-chunk bits, no chunks)
 					uint32_t f = (uint32_t)__popc(m), chunks = m;
 					if (ncnt) {
 						const uint32_t first = (uint32_t)__ffs((int)m) - 1u;
@@ -1363,7 +1388,7 @@ __device__ __forceinline__ void vg_wave_body(const DevIndex &d, const uint64_t *
 						}
 					}
 					if (!(chunks & (chunks - 1u))) continue;
-					if (f > bestf) { best = (int)e; bestf = f; amb = false; target = idx; bmask = m; bquiet = n <= 4u && (mq & KQUIET) != 0u; }
+					if (f > bestf) { best = (int)e; bestf = f; amb = false; target = idx; bmask = m; bquiet = !NOMX && n <= 4u && ((~mq >> KFREE) & ((1u << n) - 1u)) == 0u; }
 					else if (f == bestf) amb = true;
 				}
 				VG_CLK(4);
