@@ -301,6 +301,22 @@ int  vg_bgzf_scan_host(const uint8_t *bgzf, uint64_t nbytes, uint64_t *blocks, u
 uint64_t vg_bgzf_deflate_bound(uint64_t nbytes, uint32_t block);
 int  vg_bgzf_deflate_host(const uint8_t *text, uint64_t nbytes, uint32_t block, int eof, int threads, uint8_t *bgzf, uint64_t cap, uint64_t *bgzf_len);
 int  vg_bgzf_deflate_device(int device, const uint8_t *text, uint64_t nbytes, uint32_t block, int eof, uint8_t *bgzf, uint64_t cap, uint64_t *bgzf_len);
+/* The same with the coding mode named.  VG_DEFLATE_FIXED: the two calls above, byte for byte.  VG_DEFLATE_DYNAMIC: the same match
+ * finder; every block is one DEFLATE block in the smallest of three forms -- stored, fixed codes, or dynamic codes (BTYPE 2) built
+ * for the block from its own symbol counts, lengths limited to 15 (7 for the code-length code) -- so no block is larger than in
+ * the fixed mode, and one that takes the stored or the fixed form is that mode's block.  Everything said above about the bytes
+ * (host = device, threads, cuts at block boundaries), the bound and the errors holds in either mode.  Another `codes`: VG_EINVAL. */
+enum { VG_DEFLATE_FIXED = 0, VG_DEFLATE_DYNAMIC = 1 };
+int  vg_bgzf_deflate_host_coded(const uint8_t *text, uint64_t nbytes, uint32_t block, int eof, int threads, int codes, uint8_t *bgzf, uint64_t cap, uint64_t *bgzf_len);
+int  vg_bgzf_deflate_device_coded(int device, const uint8_t *text, uint64_t nbytes, uint32_t block, int eof, int codes, uint8_t *bgzf, uint64_t cap, uint64_t *bgzf_len);
+/* The code-length builder of the dynamic mode, for callers who build their own streams: n_sets independent histograms
+ * freq[set * n_sym + symbol] of 2 <= n_sym <= 288 counters each -> lens[set * n_sym + symbol], a Huffman code's lengths, none above
+ * `limit` (1 <= limit <= 15, n_sym <= 2^limit).  Integers only, ties broken by symbol number; a symbol with count 0 gets length 0,
+ * except that a set with fewer than two symbols in use has its lowest unused symbols join them at length 1; the Kraft sum of every
+ * set is exactly 1.  The device form runs one wave per histogram and returns the host form's bytes.  VG_EINVAL: a null pointer,
+ * sizes outside the above, or a histogram whose counts sum to 2^32 or more. */
+int  vg_deflate_code_lengths_host(const uint32_t *freq, uint32_t n_sets, uint32_t n_sym, uint32_t limit, uint8_t *lens);
+int  vg_deflate_code_lengths_device(int device, const uint32_t *freq, uint32_t n_sets, uint32_t n_sym, uint32_t limit, uint8_t *lens);
 
 /* Plain gzip (RFC 1952 members around one DEFLATE stream: what gzip, pigz and sequencers write; no block table) without a handle.
  * gz[0, nbytes) is inflated member after member into text[0, text_cap) in host memory; *text_len = bytes of text, *consumed =

@@ -25,6 +25,7 @@ SYMBOLS = ["vg_last_error", "vg_build_id", "vg_device_count", "vg_device_memory"
            "vg_samples_reserve", "vg_num_samples", "vg_sample_select", "vg_sample_selected", "vg_sample_reset", "vg_sample_invalid_reads",
            "vg_fastq_stream_begin_bgzf", "vg_fastq_stream_bgzf_locate", "vg_bgzf_inflate_device", "vg_bgzf_inflate_host", "vg_bgzf_scan_host",
            "vg_bgzf_deflate_bound", "vg_bgzf_deflate_host", "vg_bgzf_deflate_device",
+           "vg_bgzf_deflate_host_coded", "vg_bgzf_deflate_device_coded", "vg_deflate_code_lengths_host", "vg_deflate_code_lengths_device",
            "vg_sample_calls_fetch", "vg_call_device",
            "vg_fastq_stream_begin_bam", "vg_bam_stream_stats", "vg_bam_frame_device", "vg_bam_to_fastq_host",
            "vg_gunzip_host", "vg_gunzip_device", "vg_gunzip_chunked_host", "vg_gunzip_pushed_host",
@@ -191,6 +192,10 @@ def lib():
         L.vg_bgzf_deflate_bound.restype = C.c_uint64
         L.vg_bgzf_deflate_host.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_int, C.c_int, vp, C.c_uint64, C.POINTER(C.c_uint64)]
         L.vg_bgzf_deflate_device.argtypes = [C.c_int, vp, C.c_uint64, C.c_uint32, C.c_int, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.vg_bgzf_deflate_host_coded.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_int, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.vg_bgzf_deflate_device_coded.argtypes = [C.c_int, vp, C.c_uint64, C.c_uint32, C.c_int, C.c_int, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.vg_deflate_code_lengths_host.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]
+        L.vg_deflate_code_lengths_device.argtypes = [C.c_int, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]
         L.vg_fastq_stream_begin_bam.argtypes = [vp]
         L.vg_bam_stream_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.vg_bam_frame_device.argtypes = [C.c_int, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, C.POINTER(C.c_uint64), vp, C.POINTER(C.c_uint64)]

@@ -466,10 +466,17 @@ def bgzf_inflate(data, device=0, out=None, text_cap=None):
     return out[:int(n.value)].tobytes(), int(used.value), (None if bad.value == 2 ** 64 - 1 else int(bad.value))
 
 
-def bgzf_deflate(text, device=None, block=0, eof=True, threads=None):
-    """`text` written as BGZF (vg_bgzf_deflate_*): on `device` by the deflate kernel, or (device=None) by the host build of the same
-    compressor on `threads` threads (default: the CPUs of this process, at most 16).  block: text bytes per block, 0 = 65 280;
-    eof: append the empty end-of-file block.  The bytes depend on the text and `block` alone.  Returns bytes."""
+DEFLATE_CODES = {"fixed": 0, "dynamic": 1}                     # VG_DEFLATE_FIXED, VG_DEFLATE_DYNAMIC
+
+
+def bgzf_deflate(text, device=None, block=0, eof=True, threads=None, codes="fixed"):
+    """`text` written as BGZF (vg_bgzf_deflate_*_coded): on `device` by the deflate kernel, or (device=None) by the host build of the
+    same compressor on `threads` threads (default: the CPUs of this process, at most 16).  block: text bytes per block, 0 = 65 280;
+    eof: append the empty end-of-file block.  codes: "fixed" (fixed Huffman codes) or "dynamic" (per block the smallest of stored,
+    fixed and dynamic codes); anything else is a ValueError.  The bytes depend on the text, `block` and `codes` alone.  Returns bytes."""
+    if not isinstance(codes, str) or codes not in DEFLATE_CODES:
+        raise ValueError("codes is \"fixed\" or \"dynamic\", not %r" % (codes,))
+    mode = DEFLATE_CODES[codes]
     a = _u8(text)
     cap = int(lib().vg_bgzf_deflate_bound(len(a), int(block)))
     out = np.zeros(max(1, cap), dtype=np.uint8)
@@ -477,10 +484,26 @@ def bgzf_deflate(text, device=None, block=0, eof=True, threads=None):
     if device is None:
         if threads is None:
             threads = min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1))
-        check(lib().vg_bgzf_deflate_host(_ptr(a), len(a), int(block), int(bool(eof)), int(threads), _ptr(out), cap, C.byref(n)))
+        check(lib().vg_bgzf_deflate_host_coded(_ptr(a), len(a), int(block), int(bool(eof)), int(threads), mode, _ptr(out), cap, C.byref(n)))
     else:
-        check(lib().vg_bgzf_deflate_device(int(device), _ptr(a), len(a), int(block), int(bool(eof)), _ptr(out), cap, C.byref(n)))
+        check(lib().vg_bgzf_deflate_device_coded(int(device), _ptr(a), len(a), int(block), int(bool(eof)), mode, _ptr(out), cap, C.byref(n)))
     return out[:int(n.value)].tobytes()
+
+
+def deflate_code_lengths(freq, limit=15, device=None):
+    """Huffman code lengths, none above `limit`, of the histograms freq[n_sets, n_sym] (or one histogram freq[n_sym]) of unsigned
+    counts (vg_deflate_code_lengths_*): on `device` one wave per histogram, or (device=None) on the host; the same lengths either
+    way.  2 <= n_sym <= 288, n_sym <= 2 ** limit <= 2 ** 15.  Returns a uint8 array of freq's shape."""
+    f = np.ascontiguousarray(freq, dtype=np.uint32)
+    if f.ndim not in (1, 2):
+        raise ValueError("freq is [n_sym] or [n_sets, n_sym]")
+    f2 = f.reshape(-1, f.shape[-1])
+    lens = np.zeros(f2.shape, dtype=np.uint8)
+    if device is None:
+        check(lib().vg_deflate_code_lengths_host(_ptr(f2), f2.shape[0], f2.shape[1], int(limit), _ptr(lens)))
+    else:
+        check(lib().vg_deflate_code_lengths_device(int(device), _ptr(f2), f2.shape[0], f2.shape[1], int(limit), _ptr(lens)))
+    return lens.reshape(f.shape)
 
 
 class GunzipResult(collections.namedtuple("GunzipResult", "text consumed bad_offset stats error")):

@@ -444,14 +444,14 @@ private:
 		uint64_t len = 0;
 		const uint8_t *text = s.text.empty() ? out.data() : s.text.data();      // (no text: any pointer that is not null)
 		if (device_) {
-			const int rc = vg_bgzf_deflate_device(how_.device, text, s.text.size(), how_.block, s.last, out.data(), cap, &len);
+			const int rc = vg_bgzf_deflate_device_coded(how_.device, text, s.text.size(), how_.block, s.last, how_.codes, out.data(), cap, &len);
 			if (rc == VG_ENOMEM) {
 				if (how_.verbose) fprintf(stderr, "vcf: no device memory for the deflate kernel (%s): the rest of %s is compressed on the host\n", vg_last_error(), path_.c_str());
 				device_ = false;
-			} else if (rc != VG_OK) return std::string("vg_bgzf_deflate_device failed: ") + vg_last_error();
+			} else if (rc != VG_OK) return std::string("vg_bgzf_deflate_device_coded failed: ") + vg_last_error();
 		}
-		if (!device_ && vg_bgzf_deflate_host(text, s.text.size(), how_.block, s.last, how_.threads, out.data(), cap, &len) != VG_OK)
-			return std::string("vg_bgzf_deflate_host failed: ") + vg_last_error();
+		if (!device_ && vg_bgzf_deflate_host_coded(text, s.text.size(), how_.block, s.last, how_.threads, how_.codes, out.data(), cap, &len) != VG_OK)
+			return std::string("vg_bgzf_deflate_host_coded failed: ") + vg_last_error();
 		out.resize((size_t)len);
 		return std::string();
 	}

@@ -46,6 +46,11 @@
 //                         replica 0's device while the next span is being made (no device memory for a span: the host loop takes the rest
 //                         of the file, one line under VARGENO_VERBOSE); `host`: by VARGENO_BGZF_THREADS host threads.  Unset or empty:
 //                         plain text, as the reference writes it.  Any other value is refused before a device is touched
+//   VARGENO_VCF_CODES=fixed|dynamic  geno, cohort, joint: how the blocks of a BGZF VCF are coded (no effect on plain text).  `fixed`, also
+//                         unset or empty: fixed Huffman codes.  `dynamic`: per block the smallest of stored, fixed codes and dynamic
+//                         codes built for the block on the route that compresses it -- the same match finder, smaller files, exactly
+//                         vg_bgzf_deflate_host_coded(..., VG_DEFLATE_DYNAMIC, ...) on either route.  Any other value is refused before
+//                         a device is touched
 //   VARGENO_PAIRS_MIN_GQ=n  the table counts a call iff it is called and its GQ is at least n (default 0)
 //   VARGENO_VERBOSE=1     stderr: the index plan and start-up report, one "ingest, replica g:" line per route taken, the "reads:" line with
 //                         the wall time phase by phase; index: the "cuts:" line
@@ -57,7 +62,8 @@
 // Hidden commands of the BGZF routes (tests and measurements; main() has the others):
 //   bgzfcat <in>         a BGZF file's text on stdout (the host threads of the BGZF input route)
 //   bgzfzip <in> <out> [block]  <in> written as BGZF to <out>, `block` text bytes per block (default 65 280), by the route
-//                         VARGENO_VCF_BGZF names (default `host`; `device` needs one): the sink the three commands write their VCF through
+//                         VARGENO_VCF_BGZF names (default `host`; `device` needs one) in the coding mode VARGENO_VCF_CODES names: the sink
+//                         the three commands write their VCF through
 // Where `index` cuts its work (host/index_build.cpp; numbers clamped to >= 1, defaults unchanged when unset -- tests make them
 // tiny so that every boundary falls inside sequences, N runs and repeat copies; VARGENO_VERBOSE=1 prints one "cuts:" line
 // with what the build actually did; every chunk costs 48 KiB of bucket counters, so tiny chunks are for small inputs):
@@ -132,6 +138,16 @@ static bool vcf_bgzf_route(vgh::VcfBgzf *route)
 	fprintf(stderr, "vargeno: VARGENO_VCF_BGZF=%s is not understood: `device` or `host` writes the VCF as BGZF, unset writes plain text\n", v.c_str());
 	return false;
 }
+// VARGENO_VCF_CODES, read once: VG_DEFLATE_FIXED (unset, empty or `fixed`) or VG_DEFLATE_DYNAMIC.  false: another value -- said on
+// stderr, in one line
+static bool vcf_bgzf_codes(int *codes)
+{
+	const std::string v = env_str("VARGENO_VCF_CODES");
+	*codes = v == "dynamic" ? VG_DEFLATE_DYNAMIC : VG_DEFLATE_FIXED;
+	if (v.empty() || v == "fixed" || v == "dynamic") return true;
+	fprintf(stderr, "vargeno: VARGENO_VCF_CODES=%s is not understood: `fixed` or `dynamic` names the Huffman codes of a BGZF VCF, unset is `fixed`\n", v.c_str());
+	return false;
+}
 // CPUs this process may use: the hardware threads, capped by a cgroup CPU quota (cpu.max: "<quota> <period>"; this pool's GPU boxes
 // give a container 16 CPUs' worth of time on a 256-thread host)
 static int usable_cpus()
@@ -184,9 +200,9 @@ struct GenoOptions {
 	const std::string joint_pairs = env_str("VARGENO_JOINT_PAIRS");
 	const int pairs_min_gq = env_int("VARGENO_PAIRS_MIN_GQ", 0);
 	const int pairs_threads = std::max(1, env_int("VARGENO_THREADS", usable_cpus()));
-	// how the VCF is written (VARGENO_VCF_BGZF; main() has refused a value that is neither `device` nor `host`): on replica 0's
+	// how the VCF is written (VARGENO_VCF_BGZF and VARGENO_VCF_CODES; main() has refused a value that is neither of its two words): on replica 0's
 	// device, which is device 0, or on the BGZF threads
-	const vgh::VcfOutput vcf_out = [this] { vgh::VcfOutput w; (void)vcf_bgzf_route(&w.bgzf); w.device = 0; w.threads = bgzf_threads; w.verbose = verbose; return w; }();
+	const vgh::VcfOutput vcf_out = [this] { vgh::VcfOutput w; (void)vcf_bgzf_route(&w.bgzf); (void)vcf_bgzf_codes(&w.codes); w.device = 0; w.threads = bgzf_threads; w.verbose = verbose; return w; }();
 	explicit GenoOptions(int devices) : have(devices)
 	{
 		if (ngpu > have && !share) ngpu = have;
@@ -1449,7 +1465,8 @@ int main(int argc, const char *argv[])
 	const std::string opt = argv[1];
 	try {
 		vgh::VcfBgzf vcf_bgzf;
-		if ((opt == "geno" || opt == "cohort" || opt == "joint" || opt == "bgzfzip") && !vcf_bgzf_route(&vcf_bgzf)) return EXIT_FAILURE;      // (before anything else is looked at)
+		int vcf_codes = VG_DEFLATE_FIXED;
+		if ((opt == "geno" || opt == "cohort" || opt == "joint" || opt == "bgzfzip") && (!vcf_bgzf_route(&vcf_bgzf) || !vcf_bgzf_codes(&vcf_codes))) return EXIT_FAILURE;      // (before anything else is looked at)
 		if (opt == "index") {
 			arg_check(argc, 3);
 			vgh::IndexOptions io;
@@ -1491,6 +1508,7 @@ int main(int argc, const char *argv[])
 			if (argc != 4 && argc != 5) { print_help(); return EXIT_FAILURE; }
 			vgh::VcfOutput how;
 			how.bgzf = vcf_bgzf == vgh::VcfBgzf::Device ? vgh::VcfBgzf::Device : vgh::VcfBgzf::Host;
+			how.codes = vcf_codes;
 			how.threads = std::max(1, std::min(env_int("VARGENO_BGZF_THREADS", vgh::bgzf_threads_default(usable_cpus())), 256));
 			how.verbose = env_int("VARGENO_VERBOSE", 0) != 0;
 			const long block = argc == 5 ? atol(argv[4]) : 0;
@@ -1514,7 +1532,7 @@ int main(int argc, const char *argv[])
 			close(fd);
 			sink->close();
 			clock_gettime(CLOCK_MONOTONIC, &b);
-			if (how.verbose) fprintf(stderr, "bgzfzip: %s route, %.3f GB of text in %.3f s (%.2f GB/s)\n", how.bgzf == vgh::VcfBgzf::Device ? "device" : "host", (double)total / 1e9, secs(a, b), (double)total / 1e9 / std::max(1e-9, secs(a, b)));
+			if (how.verbose) fprintf(stderr, "bgzfzip: %s route, %s codes, %.3f GB of text in %.3f s (%.2f GB/s)\n", how.bgzf == vgh::VcfBgzf::Device ? "device" : "host", how.codes == VG_DEFLATE_DYNAMIC ? "dynamic" : "fixed", (double)total / 1e9, secs(a, b), (double)total / 1e9 / std::max(1e-9, secs(a, b)));
 			return EXIT_SUCCESS;
 		} else if (opt == "gzcat") {
 			// hidden: a plain gzip file's text on stdout, by the host build of the decoder alone (no device needed; tests/test_gzip_cpu.py)

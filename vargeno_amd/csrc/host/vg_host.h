@@ -166,9 +166,9 @@ struct SiteCounts {
 	std::vector<uint8_t> ref_freq, alt_freq, ref_cnt, alt_cnt;
 };
 // ---- where VCF text goes: a plain file, or a BGZF file (VARGENO_VCF_BGZF) ----
-// The BGZF file is vg_bgzf_deflate_host(the whole text, block, eof 1), byte for byte, on either route: the text is gathered into
+// The BGZF file is vg_bgzf_deflate_host_coded(the whole text, block, eof 1, codes), byte for byte, on either route: the text is gathered into
 // spans that are multiples of the block (the last one shorter), and a thread of the sink compresses one span -- on `device`
-// (vg_bgzf_deflate_device: upload, kernels, read-back) or on `threads` host threads -- and writes it while the next is being
+// (vg_bgzf_deflate_device_coded: upload, kernels, read-back) or on `threads` host threads -- and writes it while the next is being
 // made; two spans wait at most.  A device without memory for a span (VG_ENOMEM) hands the rest of the file to the host loop, one
 // line under `verbose`.
 enum class VcfBgzf { Off, Host, Device };
@@ -176,6 +176,7 @@ struct VcfOutput {
 	VcfBgzf bgzf = VcfBgzf::Off;
 	int device = 0, threads = 1;
 	uint32_t block = 0;                            // text bytes per BGZF block; 0: 65 280
+	int codes = 0;                                 // VG_DEFLATE_FIXED or VG_DEFLATE_DYNAMIC (VARGENO_VCF_CODES)
 	bool verbose = false;
 };
 class VcfSink {

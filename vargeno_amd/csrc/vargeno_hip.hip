@@ -1075,6 +1075,10 @@ struct DfShared {
 	VgDefShared d;
 	VgCrcTab crc;
 };
+struct DfDynShared {
+	VgDefDynShared d;
+	VgCrcTab crc;
+};
 
 struct DefWaveIO {
 	static constexpr uint32_t LANES = 64;
@@ -1093,6 +1097,12 @@ struct DefWaveIO {
 	}
 	__device__ __forceinline__ static void max32(uint32_t *p, uint32_t v) { atomicMax(p, v); }
 	__device__ __forceinline__ static void or32(uint32_t *p, uint32_t v) { atomicOr(p, v); }
+	__device__ __forceinline__ static void add32(uint32_t *p, uint32_t v) { atomicAdd(p, v); }
+};
+// ... with the dynamic path's token buffer: the block's words of global memory
+struct DefWaveDynIO : DefWaveIO {
+	uint32_t *tok;
+	__device__ __forceinline__ uint32_t *tokens() const { return tok; }
 };
 
 // text [0, nbytes) in blocks of `block` bytes (the last one shorter).  grid = blocks.  meta[b] = (payload bytes in the block's slot,
@@ -1113,6 +1123,56 @@ __global__ __launch_bounds__(64) void vg_bgzf_deflate_kernel(const uint8_t *__re
 	uint32_t x = vg_crc32_share(sh.crc, t, n, io.ln, 64);
 	for (int o = 32; o > 0; o >>= 1) x ^= __shfl_xor(x, o);
 	if (io.ln == 0) meta[b] = make_uint2(coded, x);
+}
+
+// The same in the dynamic mode (vg_deflate_block_dyn): pass 1 leaves the block's tokens in its tok_words words of `tokens` (at least
+// the block's text bytes) and its symbol counts in LDS; the plan -- code lengths, header, the choice of the form -- is made in LDS,
+// its serial part (the Huffman tree, the run-length coding of the lengths, the canonical codes) by lane 0; pass 2 reads the tokens
+// back.  meta[b] means what it means above, so vg_bgzf_frame_kernel frames either kernel's blocks.  A kernel of its own, so that
+// vg_bgzf_deflate_kernel keeps its LDS and registers.
+//
+// LDS per workgroup (DfDynShared, 22 152 B: seven blocks per CU of 160 KiB, as above):
+//   pass 1's state 16 776   the table, window and match lengths of the kernel above; once pass 1 is done the same bytes hold
+//                           the plan's tables: the 98-word window, three code tables, the header's symbols, the builder's scratch
+//   counts          1 280   288 + 32 symbol counters (ds_add_u32)
+//   crc             4 096
+// Resources (the compiler's remarks for gfx950): 73 VGPRs, 104 SGPRs, no scratch, 2 waves per SIMD.
+__global__ __launch_bounds__(64) void vg_bgzf_deflate_dyn_kernel(const uint8_t *__restrict__ text, uint64_t nbytes, uint32_t block, uint32_t n_blocks,
+                                                                uint32_t *__restrict__ slots, uint32_t slot_words, uint32_t *tokens, uint32_t tok_words, uint2 *__restrict__ meta)
+{
+	__shared__ DfDynShared sh;
+	const uint32_t b = blockIdx.x;
+	if (b >= n_blocks) return;
+	const uint64_t at = (uint64_t)b * block;
+	const uint32_t n = (uint32_t)min((uint64_t)block, nbytes - at);
+	const uint8_t *t = text + at;
+	DefWaveDynIO io;
+	io.ln = threadIdx.x;
+	io.tok = tokens + (uint64_t)b * tok_words;
+	vg_crc_tab_build(io, sh.crc);
+	const uint32_t coded = vg_deflate_block_dyn(io, sh.d, t, n, slots + (uint64_t)b * slot_words);
+	uint32_t x = vg_crc32_share(sh.crc, t, n, io.ln, 64);
+	for (int o = 32; o > 0; o >>= 1) x ^= __shfl_xor(x, o);
+	if (io.ln == 0) meta[b] = make_uint2(coded, x);
+}
+
+// vg_def_code_lengths alone: one wave per histogram.  grid = n_sets; freq and lens are [n_sets][n_sym], 2 <= n_sym <= 288.
+struct DfLenShared {
+	uint32_t freq[VG_DEF_LL_TAB];
+	uint8_t len[VG_DEF_LL_TAB];
+	VgDefLenScratch sc;
+};
+__global__ __launch_bounds__(64) void vg_def_code_lengths_kernel(const uint32_t *__restrict__ freq, uint32_t n_sets, uint32_t n_sym, uint32_t limit, uint8_t *__restrict__ lens)
+{
+	__shared__ DfLenShared sh;
+	const uint32_t b = blockIdx.x;
+	if (b >= n_sets) return;
+	DefWaveIO io;
+	io.ln = threadIdx.x;
+	for (uint32_t s = io.ln; s < n_sym; s += 64) sh.freq[s] = freq[(uint64_t)b * n_sym + s];       // 64 counters per iteration
+	__syncthreads();
+	vg_def_code_lengths(io, sh.freq, n_sym, limit, sh.len, sh.sc);
+	for (uint32_t s = io.ln; s < n_sym; s += 64) lens[(uint64_t)b * n_sym + s] = sh.len[s];        // 64 lengths per iteration
 }
 
 // grid = blocks.  Block b of the file goes to out + offs[b]: header, payload from its slot (or 01 LEN NLEN and the text), CRC32, ISIZE.
@@ -3998,9 +4058,10 @@ extern "C" int vg_bgzf_inflate_device(int device, const uint8_t *bgzf, uint64_t 
 }
 
 // ---- text -> BGZF without a handle (vg_deflate.h: the same compressor on host threads and on the device; the same bytes) ----------
-static int bz_deflate_args(const uint8_t *text, uint64_t nbytes, uint32_t block, const uint8_t *bgzf, const uint64_t *bgzf_len)
+static int bz_deflate_args(const uint8_t *text, uint64_t nbytes, uint32_t block, int codes, const uint8_t *bgzf, const uint64_t *bgzf_len)
 {
 	if ((!text && nbytes) || !bgzf || !bgzf_len) return fail(VG_EINVAL, "null argument");
+	if (codes != VG_DEFLATE_FIXED && codes != VG_DEFLATE_DYNAMIC) return fail(VG_EINVAL, "codes is VG_DEFLATE_FIXED or VG_DEFLATE_DYNAMIC");
 	if (block > VG_BGZF_TEXT_BLOCK) return fail(VG_EINVAL, "a BGZF block holds at most 65280 bytes of text here");
 	return VG_OK;
 }
@@ -4032,9 +4093,9 @@ extern "C" uint64_t vg_bgzf_deflate_bound(uint64_t nbytes, uint32_t block)
 	return block > VG_BGZF_TEXT_BLOCK ? 0 : vg_bgzf_bound(nbytes, block ? block : VG_BGZF_TEXT_BLOCK);
 }
 
-extern "C" int vg_bgzf_deflate_host(const uint8_t *text, uint64_t nbytes, uint32_t block, int eof, int threads, uint8_t *bgzf, uint64_t cap, uint64_t *bgzf_len)
+extern "C" int vg_bgzf_deflate_host_coded(const uint8_t *text, uint64_t nbytes, uint32_t block, int eof, int threads, int codes, uint8_t *bgzf, uint64_t cap, uint64_t *bgzf_len)
 {
-	const int rc = bz_deflate_args(text, nbytes, block, bgzf, bgzf_len);
+	const int rc = bz_deflate_args(text, nbytes, block, codes, bgzf, bgzf_len);
 	if (rc) return rc;
 	return guarded([&]() -> int {
 		const uint32_t B = block ? block : VG_BGZF_TEXT_BLOCK;
@@ -4046,14 +4107,17 @@ extern "C" int vg_bgzf_deflate_host(const uint8_t *text, uint64_t nbytes, uint32
 		std::atomic<bool> no_memory{false};
 		auto work = [&] {
 			try {
-				std::unique_ptr<VgDefShared> sh(new VgDefShared);
-				std::vector<uint32_t> slot((B + VG_DEF_SLACK) / 4 + 1);
+				const bool dyn = codes == VG_DEFLATE_DYNAMIC;
+				std::unique_ptr<VgDefShared> sh(dyn ? nullptr : new VgDefShared);
+				std::unique_ptr<VgDefDynShared> shd(dyn ? new VgDefDynShared : nullptr);
+				std::vector<uint32_t> slot((B + VG_DEF_SLACK) / 4 + 1), tok(dyn ? B : 0);
 				for (;;) {                                                // 16 blocks per step
 					const uint64_t b0 = next.fetch_add(16);
 					if (b0 >= nb) break;
 					for (uint64_t b = b0; b < std::min(nb, b0 + 16); b++) {
 						const uint32_t n = (uint32_t)std::min<uint64_t>(B, nbytes - b * B);
-						size[(size_t)b] = vg_bgzf_deflate_block_host(text + b * B, n, out.work + b * stride, *sh, slot.data());
+						size[(size_t)b] = dyn ? vg_bgzf_deflate_block_host_dyn(text + b * B, n, out.work + b * stride, *shd, slot.data(), tok.data())
+						                      : vg_bgzf_deflate_block_host(text + b * B, n, out.work + b * stride, *sh, slot.data());
 					}
 				}
 			} catch (const std::bad_alloc &) { no_memory = true; }
@@ -4072,9 +4136,14 @@ extern "C" int vg_bgzf_deflate_host(const uint8_t *text, uint64_t nbytes, uint32
 	});
 }
 
-extern "C" int vg_bgzf_deflate_device(int device, const uint8_t *text, uint64_t nbytes, uint32_t block, int eof, uint8_t *bgzf, uint64_t cap, uint64_t *bgzf_len)
+extern "C" int vg_bgzf_deflate_host(const uint8_t *text, uint64_t nbytes, uint32_t block, int eof, int threads, uint8_t *bgzf, uint64_t cap, uint64_t *bgzf_len)
 {
-	int rc = bz_deflate_args(text, nbytes, block, bgzf, bgzf_len);
+	return vg_bgzf_deflate_host_coded(text, nbytes, block, eof, threads, VG_DEFLATE_FIXED, bgzf, cap, bgzf_len);
+}
+
+extern "C" int vg_bgzf_deflate_device_coded(int device, const uint8_t *text, uint64_t nbytes, uint32_t block, int eof, int codes, uint8_t *bgzf, uint64_t cap, uint64_t *bgzf_len)
+{
+	int rc = bz_deflate_args(text, nbytes, block, codes, bgzf, bgzf_len);
 	if (rc) return rc;
 	int ndev = 0;
 	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(VG_ENODEV, "no HIP device available (vg_bgzf_deflate_host is the host's compressor)");
@@ -4086,9 +4155,11 @@ extern "C" int vg_bgzf_deflate_device(int device, const uint8_t *text, uint64_t 
 		const uint64_t chunk_blocks = std::min<uint64_t>(std::max<uint64_t>(1, nb), std::min<uint64_t>(65536, std::max<uint64_t>(1, (64ull << 20) / B)));
 		const uint32_t slot_words = ((B + VG_DEF_SLACK + 15u) & ~15u) / 4;
 		const uint64_t chunk_out = vg_bgzf_bound(chunk_blocks * B, B);
-		DevBuf<uint8_t> d_text, d_out; DevBuf<uint32_t> d_slots; DevBuf<uint2> d_meta; DevBuf<uint64_t> d_offs;
+		const bool dyn = codes == VG_DEFLATE_DYNAMIC;
+		const uint32_t tok_words = (B + 15u) & ~15u;                           // the dynamic mode's tokens: a word per text byte at most
+		DevBuf<uint8_t> d_text, d_out; DevBuf<uint32_t> d_slots, d_tok; DevBuf<uint2> d_meta; DevBuf<uint64_t> d_offs;
 		if (nb && ((rc = d_text.reserve(chunk_blocks * B + 16, "text")) || (rc = d_slots.reserve(chunk_blocks * slot_words, "deflate slots")) || (rc = d_meta.reserve(chunk_blocks, "block results"))
-		           || (rc = d_offs.reserve(chunk_blocks, "block offsets")) || (rc = d_out.reserve(chunk_out, "BGZF bytes")))) return rc;
+		           || (rc = d_offs.reserve(chunk_blocks, "block offsets")) || (rc = d_out.reserve(chunk_out, "BGZF bytes")) || (dyn && (rc = d_tok.reserve(chunk_blocks * tok_words, "deflate tokens"))))) return rc;
 		BzDeflateOut out(bgzf, cap, vg_bgzf_bound(nbytes, B));
 		std::vector<uint2> meta((size_t)chunk_blocks);
 		std::vector<uint64_t> offs((size_t)chunk_blocks);
@@ -4102,7 +4173,8 @@ extern "C" int vg_bgzf_deflate_device(int device, const uint8_t *text, uint64_t 
 			const uint64_t t0 = b0 * B, tn = std::min<uint64_t>((uint64_t)k * B, nbytes - t0);
 			HIP_TRY(hipMemcpy(d_text.p, text + t0, tn, hipMemcpyHostToDevice));
 			if (timed) HIP_TRY(hipEventRecord(e0, nullptr));
-			vg_bgzf_deflate_kernel<<<k, 64>>>(d_text.p, tn, B, k, d_slots.p, slot_words, d_meta.p);
+			if (dyn) vg_bgzf_deflate_dyn_kernel<<<k, 64>>>(d_text.p, tn, B, k, d_slots.p, slot_words, d_tok.p, tok_words, d_meta.p);
+			else vg_bgzf_deflate_kernel<<<k, 64>>>(d_text.p, tn, B, k, d_slots.p, slot_words, d_meta.p);
 			HIP_TRY(hipGetLastError());
 			if (timed) HIP_TRY(hipEventRecord(e1, nullptr));
 			HIP_TRY(hipMemcpy(meta.data(), d_meta.p, (size_t)k * sizeof(uint2), hipMemcpyDeviceToHost));
@@ -4128,11 +4200,61 @@ extern "C" int vg_bgzf_deflate_device(int device, const uint8_t *text, uint64_t 
 			len += sum;
 		}
 		if (timed) {
-			fprintf(stderr, "[vargeno_hip] bgzf deflate: %llu blocks, %.3f ms deflate kernel (%.2f GB/s text), %.3f ms framing (incl. the lengths' round trip), ratio %.3f\n", (unsigned long long)nb, ms_deflate,
-			        ms_deflate > 0 ? nbytes / 1e6 / ms_deflate : 0.0, ms_frame, nbytes ? (double)len / (double)nbytes : 0.0);
+			fprintf(stderr, "[vargeno_hip] bgzf deflate: %llu blocks, %s codes, %.3f ms deflate kernel (%.2f GB/s text), %.3f ms framing (incl. the lengths' round trip), ratio %.3f\n", (unsigned long long)nb,
+			        dyn ? "dynamic" : "fixed", ms_deflate, ms_deflate > 0 ? nbytes / 1e6 / ms_deflate : 0.0, ms_frame, nbytes ? (double)len / (double)nbytes : 0.0);
 			(void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipEventDestroy(e2);
 		}
 		return out.deliver(len, eof, bgzf_len);
+	});
+}
+
+extern "C" int vg_bgzf_deflate_device(int device, const uint8_t *text, uint64_t nbytes, uint32_t block, int eof, uint8_t *bgzf, uint64_t cap, uint64_t *bgzf_len)
+{
+	return vg_bgzf_deflate_device_coded(device, text, nbytes, block, eof, VG_DEFLATE_FIXED, bgzf, cap, bgzf_len);
+}
+
+// ---- the dynamic mode's code-length builder alone (vg_def_code_lengths on the host, and one wave per histogram) ----
+static int def_lengths_args(const uint32_t *freq, uint32_t n_sets, uint32_t n_sym, uint32_t limit, const uint8_t *lens)
+{
+	if ((!freq || !lens) && n_sets) return fail(VG_EINVAL, "null argument");
+	if (n_sym < 2 || n_sym > VG_DEF_LL_TAB || limit < 1 || limit > 15 || n_sym > (1u << limit)) return fail(VG_EINVAL, "code lengths: 2 to 288 symbols, a limit of 1 to 15, and no more symbols than 2^limit");
+	for (uint64_t i = 0; i < (uint64_t)n_sets; i++) {
+		uint64_t sum = 0;
+		for (uint32_t s = 0; s < n_sym; s++) sum += freq[i * n_sym + s];
+		if (sum >> 32) return fail(VG_EINVAL, "code lengths: the counts of a histogram sum to 2^32 or more");
+	}
+	return VG_OK;
+}
+
+extern "C" int vg_deflate_code_lengths_host(const uint32_t *freq, uint32_t n_sets, uint32_t n_sym, uint32_t limit, uint8_t *lens)
+{
+	const int rc = def_lengths_args(freq, n_sets, n_sym, limit, lens);
+	if (rc) return rc;
+	return guarded([&]() -> int {
+		std::unique_ptr<VgDefLenScratch> sc(new VgDefLenScratch);
+		DefHostIO io;
+		for (uint64_t i = 0; i < (uint64_t)n_sets; i++) vg_def_code_lengths(io, freq + i * n_sym, n_sym, limit, lens + i * n_sym, *sc);
+		return VG_OK;
+	});
+}
+
+extern "C" int vg_deflate_code_lengths_device(int device, const uint32_t *freq, uint32_t n_sets, uint32_t n_sym, uint32_t limit, uint8_t *lens)
+{
+	int rc = def_lengths_args(freq, n_sets, n_sym, limit, lens);
+	if (rc) return rc;
+	int ndev = 0;
+	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(VG_ENODEV, "no HIP device available (vg_deflate_code_lengths_host is the host's builder)");
+	return guarded([&]() -> int {
+		if (!n_sets) return VG_OK;
+		HIP_TRY(hipSetDevice(device));
+		const uint64_t cells = (uint64_t)n_sets * n_sym;
+		DevBuf<uint32_t> d_freq; DevBuf<uint8_t> d_lens;
+		if ((rc = d_freq.reserve(cells, "histograms")) || (rc = d_lens.reserve(cells, "code lengths"))) return rc;
+		HIP_TRY(hipMemcpy(d_freq.p, freq, cells * sizeof(uint32_t), hipMemcpyHostToDevice));
+		vg_def_code_lengths_kernel<<<n_sets, 64>>>(d_freq.p, n_sets, n_sym, limit, d_lens.p);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpy(lens, d_lens.p, cells, hipMemcpyDeviceToHost));
+		return VG_OK;
 	});
 }
 
