@@ -462,6 +462,65 @@ uint64_t vg_gmatrix_device_bytes(const vg_gmatrix *gm);
 void vg_gmatrix_destroy(vg_gmatrix *gm);
 int  vg_pairs_host(const uint8_t *gt, const int32_t *gq, uint64_t n_sites, uint32_t n_samples, int32_t min_gq, int threads, uint64_t *counts);
 
+/* The data lines of the joint (multi-sample) VCF rendered on the device.  No reference counterpart.  The rules live in csrc/vg_jtext.h,
+ * one statement for the host loop and the kernels.  A sample's CELL for a call (gt, gq) of vg_sample_calls_fetch is "\t" + "0/0" (gt 1),
+ * "1/1" (gt 2) or "0/1" (gt 3) + ":" + gq as "%d" prints an int32 (any value: 6 to 16 bytes); a sample without a call shows "\t./.:.".
+ * A RECORD is one data line of the SNP list whose key names sites of the index: its first eight fields heads[head_off, +head_len) and
+ * the run sites[site_at, +n_sites) of site indices of that key in genome order (not necessarily consecutive).  Every sample shows the
+ * call of the LAST site of the run at which its gt != 0.  If no sample has one the record produces no bytes; otherwise its LINE is
+ * the head, "\tGT:GQ", the cells in sample order, "\n".  The text of a span of records is at most
+ * vg_jtext_text_bound = the sum of head_len + n_records * (7 + 16 * n_samples) bytes.
+ * A vg_jtext lives on one device and is tied to no vg_index; a handle is thread-compatible.
+ *   vg_jtext_create        ALL device memory the handle will ever use (later calls never allocate): the samples' columns, sample-major,
+ *                          2 bytes per site and sample (gt << 14 | gq); `wide_samples` wide columns of 4 bytes per site for samples
+ *                          that have a gq outside 0 .. 16382; one sample's columns of staging (5 bytes per site); and the buffers of a
+ *                          span of at most max_records records, max_head_bytes bytes of heads and max_site_refs site references: those,
+ *                          ceil(n_samples / 64) + 1 lengths and offsets (12 bytes) per record and the span's text bound + 80 KiB.
+ *                          with_bgzf != 0: also the work buffers of the BGZF stream below (about 110 MB).  n_samples 1 .. 16 384 (0:
+ *                          VG_EINVAL, more: VG_ETOOBIG), n_sites below 2^32.  VG_ENOMEM leaves nothing behind; VG_ENODEV without a device
+ *   vg_jtext_set           one sample's final gt / gq columns (host arrays of n_sites entries, free again on return).  A sample never
+ *                          set is all-missing; setting a sample again replaces it.  VG_EINVAL: a null pointer, a sample out of range,
+ *                          a gt above 3; VG_ETOOBIG: the sample needs a wide column and none is free -- the handle stays as it was
+ *   vg_jtext_render        the text of a span into text[0, cap) in host memory: *len bytes, *n_lines records that produced a line.
+ *                          Synchronous.  VG_ETOOBIG: cap below the span's bound, or a span beyond the limits of create; VG_EINVAL: a
+ *                          null pointer, a head or a site run outside its array, a site index >= n_sites, an open stream -- nothing is
+ *                          written.  With VG_VERBOSE set the call prints the kernels' own time and rate
+ *   vg_jtext_render_host   the same bytes by the header's host loop on `threads` threads (< 1: one), from per-sample column pointers
+ *                          gt[s], gq[s] (gt[s] NULL: never set).  Touches no device; no limits but the cap
+ *   vg_jtext_device_bytes  device memory the handle holds (0 for a null handle)
+ * The BGZF stream (with_bgzf): text is joined on the device and leaves it compressed.  After vg_jtext_bgzf_begin(block, codes) -- as
+ * vg_bgzf_deflate_host_coded's -- vg_jtext_bgzf_text joins host bytes (header lines), vg_jtext_bgzf_lines the rendered text of a span
+ * (*text_len bytes of it, *n_lines lines), vg_jtext_bgzf_end the last partial block and the end-of-file marker.  Each call hands
+ * back, in bgzf[0, *bgzf_len), the blocks it completed; text short of a block stays pending on the device.  The concatenation of
+ * everything handed back is vg_bgzf_deflate_host_coded(the whole text, block, eof 1, codes), byte for byte.  cap must be at least
+ * vg_jtext_bgzf_bound(bytes of text the call may add, block) -- for _lines the span's text bound, for _end 0 -- else VG_ETOOBIG and
+ * nothing happens.  A call without an open stream, or begin on a handle created without with_bgzf: VG_EINVAL. */
+#ifndef VG_JTEXT_RECORD_DEFINED
+#define VG_JTEXT_RECORD_DEFINED
+typedef struct vg_jtext_record {
+	uint64_t head_off;     /* the first eight fields: heads[head_off, head_off + head_len) */
+	uint64_t site_at;      /* the key's sites: sites[site_at, site_at + n_sites) */
+	uint32_t head_len;
+	uint32_t n_sites;
+} vg_jtext_record;
+#endif
+typedef struct vg_jtext vg_jtext;
+int  vg_jtext_create(int device, uint64_t n_sites, uint32_t n_samples, uint32_t wide_samples, uint64_t max_records, uint64_t max_head_bytes, uint64_t max_site_refs, int with_bgzf, vg_jtext **out);
+void vg_jtext_destroy(vg_jtext *jt);
+uint64_t vg_jtext_device_bytes(const vg_jtext *jt);
+int  vg_jtext_set(vg_jtext *jt, uint32_t sample, const uint8_t *gt, const int32_t *gq);
+uint64_t vg_jtext_text_bound(uint64_t head_bytes, uint64_t n_records, uint32_t n_samples);
+uint64_t vg_jtext_bgzf_bound(uint64_t text_bytes, uint32_t block);
+int  vg_jtext_render(vg_jtext *jt, const uint8_t *heads, uint64_t heads_len, const vg_jtext_record *records, uint64_t n_records, const uint32_t *sites, uint64_t n_site_refs,
+                     uint8_t *text, uint64_t cap, uint64_t *len, uint64_t *n_lines);
+int  vg_jtext_render_host(uint64_t n_sites, uint32_t n_samples, const uint8_t *const *gt, const int32_t *const *gq, const uint8_t *heads, uint64_t heads_len, const vg_jtext_record *records, uint64_t n_records,
+                          const uint32_t *sites, uint64_t n_site_refs, int threads, uint8_t *text, uint64_t cap, uint64_t *len, uint64_t *n_lines);
+int  vg_jtext_bgzf_begin(vg_jtext *jt, uint32_t block, int codes);
+int  vg_jtext_bgzf_text(vg_jtext *jt, const uint8_t *text, uint64_t nbytes, uint8_t *bgzf, uint64_t cap, uint64_t *bgzf_len);
+int  vg_jtext_bgzf_lines(vg_jtext *jt, const uint8_t *heads, uint64_t heads_len, const vg_jtext_record *records, uint64_t n_records, const uint32_t *sites, uint64_t n_site_refs,
+                         uint8_t *bgzf, uint64_t cap, uint64_t *bgzf_len, uint64_t *text_len, uint64_t *n_lines);
+int  vg_jtext_bgzf_end(vg_jtext *jt, uint8_t *bgzf, uint64_t cap, uint64_t *bgzf_len);
+
 /* Sample planes: several samples against ONE resident index. The reference genotypes one sample per process: the counters it hands
  * to the caller (qv.cc:1573-1626) are the only per-sample state of its read loop, the dictionaries are read-only.  A PLANE is that
  * state for one sample on the device: the exact sums (8 bytes per SNP site) and the wave kernel's base-indexed counters (16 bytes

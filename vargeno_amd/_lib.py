@@ -30,7 +30,9 @@ SYMBOLS = ["vg_last_error", "vg_build_id", "vg_device_count", "vg_device_memory"
            "vg_fastq_stream_begin_bam", "vg_bam_stream_stats", "vg_bam_frame_device", "vg_bam_to_fastq_host",
            "vg_gunzip_host", "vg_gunzip_device", "vg_gunzip_chunked_host", "vg_gunzip_pushed_host",
            "vg_fastq_stream_begin_gzip", "vg_gzip_stream_stats", "vg_fastq_stream_gzip_checkpoint",
-           "vg_gmatrix_create", "vg_gmatrix_set", "vg_gmatrix_pairs", "vg_gmatrix_device_bytes", "vg_gmatrix_destroy", "vg_pairs_host"]
+           "vg_gmatrix_create", "vg_gmatrix_set", "vg_gmatrix_pairs", "vg_gmatrix_device_bytes", "vg_gmatrix_destroy", "vg_pairs_host",
+           "vg_jtext_create", "vg_jtext_destroy", "vg_jtext_device_bytes", "vg_jtext_set", "vg_jtext_text_bound", "vg_jtext_bgzf_bound", "vg_jtext_render", "vg_jtext_render_host",
+           "vg_jtext_bgzf_begin", "vg_jtext_bgzf_text", "vg_jtext_bgzf_lines", "vg_jtext_bgzf_end"]
 
 GZIP_STAT_FIELDS = ["members", "chunks", "guessed", "confirmed", "repaired", "tested", "slots_refused", "resume_bit"]
 
@@ -210,6 +212,22 @@ def lib():
         L.vg_gmatrix_destroy.argtypes = [vp]
         L.vg_gmatrix_destroy.restype = None
         L.vg_pairs_host.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_int32, C.c_int, vp]
+        L.vg_jtext_create.argtypes = [C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(vp)]
+        L.vg_jtext_destroy.argtypes = [vp]
+        L.vg_jtext_destroy.restype = None
+        L.vg_jtext_device_bytes.argtypes = [vp]
+        L.vg_jtext_device_bytes.restype = C.c_uint64
+        L.vg_jtext_set.argtypes = [vp, C.c_uint32, vp, vp]
+        L.vg_jtext_text_bound.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32]
+        L.vg_jtext_text_bound.restype = C.c_uint64
+        L.vg_jtext_bgzf_bound.argtypes = [C.c_uint64, C.c_uint32]
+        L.vg_jtext_bgzf_bound.restype = C.c_uint64
+        L.vg_jtext_render.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.vg_jtext_render_host.argtypes = [C.c_uint64, C.c_uint32, vp, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, C.c_int, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.vg_jtext_bgzf_begin.argtypes = [vp, C.c_uint32, C.c_int]
+        L.vg_jtext_bgzf_text.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.vg_jtext_bgzf_lines.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.vg_jtext_bgzf_end.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
         # The library is a build product that travels next to its sources (not in git): refuse a stale one.  Its build id is the
         # sha256 of the sources it was compiled from (csrc/Makefile); VARGENO_HIP_LIB (A/B variants) opts out.
         if not os.environ.get("VARGENO_HIP_LIB"):

@@ -655,6 +655,148 @@ def pairs_host(gt, gq, min_gq=0, threads=1):
     return out
 
 
+# vg_jtext_record: a data line of the joint VCF -- its first eight fields in `heads` and its run of site indices in `sites`
+JTEXT_RECORD = np.dtype([("head_off", "<u8"), ("site_at", "<u8"), ("head_len", "<u4"), ("n_sites", "<u4")])
+
+
+def jtext_records(rows):
+    """[(head_off, head_len, site_at, n_sites), ...] (or an array of JTEXT_RECORD) as the array the joint text calls take."""
+    if isinstance(rows, np.ndarray) and rows.dtype == JTEXT_RECORD:
+        return np.ascontiguousarray(rows)
+    a = np.zeros(len(rows), dtype=JTEXT_RECORD)
+    for i, (head_off, head_len, site_at, n_sites) in enumerate(rows):
+        a[i] = (head_off, site_at, head_len, n_sites)
+    return a
+
+
+def _jtext_span(heads, records, sites):
+    return _u8(heads), jtext_records(records), np.ascontiguousarray(sites, dtype=np.uint32)
+
+
+def jtext_text_bound(head_bytes, n_records, n_samples):
+    """Bytes the text of a span never exceeds: head_bytes + n_records * (7 + 16 * n_samples)."""
+    return int(lib().vg_jtext_text_bound(int(head_bytes), int(n_records), int(n_samples)))
+
+
+def jtext_bgzf_bound(text_bytes, block=0):
+    """Bytes of BGZF a call of the joint text stream that adds text_bytes of text never exceeds."""
+    return int(lib().vg_jtext_bgzf_bound(int(text_bytes), int(block)))
+
+
+class JointText:
+    """The calls of a cohort in columns on a device (vg_jtext_*), and the data lines of the joint VCF rendered from them: as plain
+    bytes (render) or joined to a BGZF stream that leaves the device compressed (bgzf_begin / bgzf_text / bgzf_lines / bgzf_end; the
+    handle must be made with bgzf=True).  max_records, max_head_bytes, max_site_refs: the largest span a call may take;
+    wide_samples: samples that may hold a gq outside 0 .. 16382 (default: all)."""
+
+    def __init__(self, n_sites, n_samples, device=0, max_records=1 << 16, max_head_bytes=1 << 22, max_site_refs=1 << 18, wide_samples=None, bgzf=False):
+        self._h = None
+        self.n_sites, self.n_samples = int(n_sites), int(n_samples)
+        if self.n_sites < 0 or self.n_samples < 0:
+            raise ValueError("JointText: negative size")
+        self._block = 0
+        h = C.c_void_p()
+        wide = self.n_samples if wide_samples is None else int(wide_samples)
+        check(lib().vg_jtext_create(int(device), self.n_sites, min(self.n_samples, 2 ** 32 - 1), min(wide, 2 ** 32 - 1), int(max_records), int(max_head_bytes), int(max_site_refs), int(bool(bgzf)), C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if self._h:
+            lib().vg_jtext_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def device_bytes(self):
+        return int(lib().vg_jtext_device_bytes(self._h))
+
+    def set(self, sample, gt, gq):
+        """One sample's final calls (as GenoIndex.calls() returns them)."""
+        gt = np.ascontiguousarray(gt, dtype=np.uint8)
+        gq = np.ascontiguousarray(gq, dtype=np.int32)
+        if gt.shape != (self.n_sites,) or gq.shape != (self.n_sites,):
+            raise ValueError("JointText.set: gt and gq hold one entry per site")
+        if not 0 <= int(sample) < 2 ** 32:
+            raise ValueError("JointText.set: sample out of range")
+        check(lib().vg_jtext_set(self._h, int(sample), _ptr(gt), _ptr(gq)))
+
+    def render(self, heads, records, sites, with_lines=False):
+        """The text of a span as bytes (with_lines: and the number of records that produced a line)."""
+        h, r, s = _jtext_span(heads, records, sites)
+        cap = jtext_text_bound(int(r["head_len"].sum(dtype=np.uint64)), len(r), self.n_samples)
+        out = np.zeros(max(1, cap), dtype=np.uint8)
+        n, lines = C.c_uint64(), C.c_uint64()
+        check(lib().vg_jtext_render(self._h, _ptr(h), len(h), _ptr(r), len(r), _ptr(s), len(s), _ptr(out), cap, C.byref(n), C.byref(lines)))
+        text = out[:int(n.value)].tobytes()
+        return (text, int(lines.value)) if with_lines else text
+
+    def bgzf_begin(self, block=0, codes="fixed"):
+        if not isinstance(codes, str) or codes not in DEFLATE_CODES:
+            raise ValueError("codes is \"fixed\" or \"dynamic\", not %r" % (codes,))
+        check(lib().vg_jtext_bgzf_begin(self._h, int(block), DEFLATE_CODES[codes]))
+        self._block = int(block)
+
+    def bgzf_text(self, text):
+        """Host bytes joined to the stream; returns the BGZF blocks the call completed."""
+        a = _u8(text)
+        cap = jtext_bgzf_bound(len(a), self._block)
+        out = np.zeros(max(1, cap), dtype=np.uint8)
+        n = C.c_uint64()
+        check(lib().vg_jtext_bgzf_text(self._h, _ptr(a), len(a), _ptr(out), cap, C.byref(n)))
+        return out[:int(n.value)].tobytes()
+
+    def bgzf_lines(self, heads, records, sites, with_counts=False):
+        """A span rendered and joined without leaving the device; returns the BGZF blocks the call completed (with_counts: and the
+        bytes of text and the lines it added)."""
+        h, r, s = _jtext_span(heads, records, sites)
+        cap = jtext_bgzf_bound(jtext_text_bound(int(r["head_len"].sum(dtype=np.uint64)), len(r), self.n_samples), self._block)
+        out = np.zeros(max(1, cap), dtype=np.uint8)
+        n, tn, lines = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        check(lib().vg_jtext_bgzf_lines(self._h, _ptr(h), len(h), _ptr(r), len(r), _ptr(s), len(s), _ptr(out), cap, C.byref(n), C.byref(tn), C.byref(lines)))
+        blocks = out[:int(n.value)].tobytes()
+        return (blocks, int(tn.value), int(lines.value)) if with_counts else blocks
+
+    def bgzf_end(self):
+        """The last partial block and the end-of-file marker."""
+        cap = jtext_bgzf_bound(0, self._block)
+        out = np.zeros(max(1, cap), dtype=np.uint8)
+        n = C.c_uint64()
+        check(lib().vg_jtext_bgzf_end(self._h, _ptr(out), cap, C.byref(n)))
+        return out[:int(n.value)].tobytes()
+
+
+def joint_text_host(gt, gq, heads, records, sites, threads=1, n_sites=None, with_lines=False):
+    """The same text by the header's host loop (vg_jtext_render_host; no device).  gt, gq: [n_samples, n_sites] arrays, or lists of
+    per-sample columns in which None stands for a sample never set.  n_sites: default, the columns' length."""
+    cols_gt = [None if g is None else np.ascontiguousarray(g, dtype=np.uint8) for g in gt]
+    cols_gq = [None if g is None else np.ascontiguousarray(q, dtype=np.int32) for g, q in zip(gt, gq)]
+    n_samples = len(cols_gt)
+    h, r, s = _jtext_span(heads, records, sites)
+    if n_sites is None:                                        # (no sample set: any number of sites above the references will do)
+        n_sites = max([len(g) for g in cols_gt if g is not None] or [int(s.max()) + 1 if len(s) else 0])
+    if any(g is not None and (g.shape != (n_sites,) or q.shape != (n_sites,)) for g, q in zip(cols_gt, cols_gq)):
+        raise ValueError("joint_text_host: every sample's gt and gq hold one entry per site")
+    pg = (C.c_void_p * max(1, n_samples))(*[None if g is None else g.ctypes.data for g in cols_gt])
+    pq = (C.c_void_p * max(1, n_samples))(*[None if q is None else q.ctypes.data for q in cols_gq])
+    cap = jtext_text_bound(int(r["head_len"].sum(dtype=np.uint64)), len(r), n_samples)
+    out = np.zeros(max(1, cap), dtype=np.uint8)
+    n, lines = C.c_uint64(), C.c_uint64()
+    check(lib().vg_jtext_render_host(n_sites, n_samples, pg, pq, _ptr(h), len(h), _ptr(r), len(r), _ptr(s), len(s), int(threads), _ptr(out), cap, C.byref(n), C.byref(lines)))
+    text = out[:int(n.value)].tobytes()
+    return (text, int(lines.value)) if with_lines else text
+
+
 def pinned_buffer(nbytes):
     """Page-locked host memory: (numpy uint8 view, owner).  Keep `owner` alive as long as the view is used."""
     p = lib().vg_host_alloc_pinned(int(nbytes))

@@ -30,6 +30,7 @@
 #include "../../../include/vargeno_hip.h"
 #include "vg_host.h"
 #include "../vg_caller.h"
+#include "../vg_jtext.h"
 
 namespace vgh {
 
@@ -595,10 +596,240 @@ CallSummary write_genotyped_vcf(const SiteCounts &s, const std::vector<ChrLen> &
 // A data line is written iff at least one sample's own VCF would contain it: its first eight fields, GT:GQ, then per sample what
 // that sample's own VCF shows for the record -- the call of the LAST site of the record's key, in genome order, that the sample
 // has called -- or ./.:. if its VCF drops the record.
-void write_joint_vcf(const std::vector<uint32_t> &pos, const std::vector<ChrLen> &chrlens, const std::vector<JointSample> &samples, const std::string &vcf_in, const std::string &vcf_out, const std::string *vcf_text, const VcfOutput &how)
+namespace {
+
+Span joint_first_eight(Span ln)
+{
+	const char *q = ln.b;
+	for (int k = 0; k < 8 && q; k++) { q = (const char *)memchr(q, '\t', (size_t)(ln.e - q)); if (q && k < 7) q++; }
+	return Span{ln.b, q ? q : ln.e};
+}
+
+// The plan of a run of data lines (../vg_jtext.h), built by the pass's threads: head offsets count from the start of the SNP list's text
+struct JointPlan {
+	std::vector<vg_jtext_record> recs;
+	std::vector<uint32_t> sites;
+	void clear() { recs.clear(); sites.clear(); }
+};
+
+// The planned routes of write_joint_vcf (vg_host.h: JointText::Planned and ::Device).  false: the device has no memory for the
+// handle and nothing has been written -- the caller's own loop writes the file.
+bool write_joint_vcf_planned(const std::vector<uint32_t> &pos, const std::vector<ChrLen> &chrlens, const std::vector<JointSample> &samples, const std::string &vcf_in, const std::string &vcf_out, const std::string *vcf_text,
+                             const VcfOutput &how, const JointTextRoute &tr)
+{
+	struct timespec c0, c1; clock_gettime(CLOCK_MONOTONIC, &c0);
+	const bool on_device = tr.route == JointText::Device;
+	const char *const route = on_device ? "device" : "planned";
+	const size_t n = samples.size();
+	if (n == 0 || n > 16384) throw Error{std::string("VARGENO_JOINT_TEXT=") + route + " takes 1 to 16384 samples"};
+	// a span: at most `lines` records, SPAN_HEADS bytes of the list from its first head to its last, and site_cap site references
+	const uint64_t per_line = VG_JT_LINE_FIXED + (uint64_t)VG_JT_CELL_MAX * n, SPAN_HEADS = 32ull << 20;
+	const uint64_t lines = tr.lines ? std::min<uint64_t>(tr.lines, 1u << 22) : std::max<uint64_t>(1, std::min<uint64_t>(1u << 20, (128ull << 20) / (per_line + 64)));
+	const uint64_t site_cap = 4 * lines + 4096;
+	const bool stream = on_device && how.bgzf == VcfBgzf::Device;         // the text leaves the device compressed
+	vg_jtext *jt = nullptr;
+	struct Closer { vg_jtext *&h; ~Closer() { if (h) vg_jtext_destroy(h); } } closer{jt};
+	if (on_device) {
+		uint32_t wide = 0;                                                // samples with a gq the 2-byte column cannot hold
+		for (const JointSample &js : samples) {
+			bool w = false;
+			for (size_t i = 0; i < js.calls.gt.size() && !w; i++) w = js.calls.gt[i] != GT_NONE && (js.calls.gq[i] < 0 || js.calls.gq[i] >= (int32_t)VG_JT_GQ_ESCAPE);
+			wide += w;
+		}
+		const int rc = vg_jtext_create(tr.device, pos.size(), (uint32_t)n, wide, lines, SPAN_HEADS, site_cap, stream, &jt);
+		if (rc == VG_ENOMEM) {
+			if (how.verbose) fprintf(stderr, "joint text: no device memory for the text kernels (%s): %s is written by the host loop\n", vg_last_error(), vcf_out.c_str());
+			return false;
+		}
+		if (rc != VG_OK) throw Error{std::string("VARGENO_JOINT_TEXT=device: ") + vg_last_error()};
+		for (size_t j = 0; j < n && !pos.empty(); j++)
+			if (vg_jtext_set(jt,(uint32_t)j, samples[j].calls.gt.data(), samples[j].calls.gq.data()) != VG_OK) throw Error{"vg_jtext_set failed for sample " + samples[j].name + ": " + vg_last_error()};
+	}
+	const CallBook book(pos, chrlens);
+	bool ok = vcf_text != nullptr;
+	std::string own;
+	if (!vcf_text) own = slurp(vcf_in, ok);
+	const std::string &text = vcf_text ? *vcf_text : own;
+	if (!ok) throw Error{"Error opening: " + vcf_in + " . You have failed."};
+
+	// where the bytes go: the sink of every other route, or -- the stream -- BGZF blocks from the handle straight into the file
+	std::unique_ptr<VcfSink> out;
+	FILE *f = nullptr;
+	struct FileCloser { FILE *&f; ~FileCloser() { if (f) fclose(f); } } file_closer{f};
+	std::vector<uint8_t> buf;
+	auto put = [&](uint64_t len) { if (len && fwrite(buf.data(), 1, (size_t)len, f) != (size_t)len) throw Error{"cannot write " + vcf_out}; };
+	if (stream) {
+		f = fopen(vcf_out.c_str(), "wb");
+		if (!f) throw Error{"cannot write " + vcf_out};
+		if (vg_jtext_bgzf_begin(jt, how.block, how.codes) != VG_OK) throw Error{std::string("vg_jtext_bgzf_begin failed: ") + vg_last_error()};
+	} else out = open_vcf_sink(vcf_out, how);
+
+	std::vector<const uint8_t *> gts(n);
+	std::vector<const int32_t *> gqs(n);
+	for (size_t j = 0; j < n; j++) { gts[j] = samples[j].calls.gt.data(); gqs[j] = samples[j].calls.gq.data(); }
+
+	bool declares_gt = false, declares_gq = false;
+	auto header = [&](const char *&p, const char *end, std::string &dst) {
+		while (p < end) {
+			const char *at = p;
+			const Span ln = next_line(p, end);
+			if (ln.size() == 0) continue;
+			if (ln.b[0] != '#') { p = at; return; }
+			if (ln.size() > 1 && ln.b[1] == '#') {
+				dst.append(ln.b, ln.e).push_back('\n');
+				const std::string meta(ln.b, ln.e);
+				if (meta.find("ID=GT,") != std::string::npos) declares_gt = true;
+				else if (meta.find("ID=GQ,") != std::string::npos) declares_gq = true;
+			} else {
+				if (!declares_gt) dst += kGtDecl;
+				if (!declares_gq) dst += kGqDecl;
+				const Span cols = joint_first_eight(ln);
+				dst.append(cols.b, cols.e) += "\tFORMAT";
+				for (const JointSample &js : samples) { dst.push_back('\t'); dst += js.name; }
+				dst.push_back('\n');
+			}
+		}
+	};
+	// one data line -> its record, if its key is in the book
+	auto plan_line = [&](Span ln, JointPlan &pl, Scratch &sc) {
+		if (count_fields(ln, '\t') < 2) return;
+		const Span chrom = field(ln, '\t', 0), ps = field(ln, '\t', 1);
+		std::string &key = sc.key;
+		key.clear();
+		if (chrom.size() == 0 || chrom.b[0] != 'c') key = "chr";
+		key.append(chrom.b, chrom.e).push_back('$');
+		key.append(ps.b, ps.e);
+		const CalledSite *first = book.find(key, sc.hint);
+		if (!first) return;
+		const Span head = joint_first_eight(ln);
+		if (head.size() > SPAN_HEADS) throw Error{"a record of the SNP list has more than " + std::to_string(SPAN_HEADS) + " bytes in its first eight fields: VARGENO_JOINT_TEXT=host writes such a file"};
+		vg_jtext_record r;
+		r.head_off = (uint64_t)(head.b - text.data()); r.head_len = (uint32_t)head.size(); r.site_at = pl.sites.size(); r.n_sites = 0;
+		for (const CalledSite *q = first, *e = CallBook::list_end(sc.hint); q < e && q->local == first->local; q++) { pl.sites.push_back(q->order); r.n_sites++; }      // the sites of this key, in genome order
+		if (r.n_sites > site_cap) throw Error{"a key of the SNP list names more than " + std::to_string(site_cap) + " sites: VARGENO_JOINT_TEXT=host writes such a file"};
+		pl.recs.push_back(r);
+	};
+
+	uint64_t n_records = 0, n_lines = 0, n_spans = 0, n_text = 0;
+	std::vector<vg_jtext_record> span_recs;
+	// records [i0, i1) of the run's plan -> their text, to the sink or the stream
+	auto render_span = [&](const JointPlan &pl, size_t i0, size_t i1) {
+		const vg_jtext_record &a = pl.recs[i0], &z = pl.recs[i1 - 1];
+		const uint64_t heads_len = z.head_off + z.head_len - a.head_off, refs = z.site_at + z.n_sites - a.site_at;
+		span_recs.assign(pl.recs.begin() + (ptrdiff_t)i0, pl.recs.begin() + (ptrdiff_t)i1);
+		uint64_t head_sum = 0;
+		for (vg_jtext_record &r : span_recs) { r.head_off -= a.head_off; r.site_at -= a.site_at; head_sum += r.head_len; }
+		const uint8_t *heads = (const uint8_t *)text.data() + a.head_off;
+		const uint32_t *sites = pl.sites.data() + a.site_at;
+		const uint64_t bound = vg_jtext_text_bound(head_sum, i1 - i0, (uint32_t)n);
+		uint64_t len = 0, got_lines = 0;
+		if (stream) {
+			uint64_t text_len = 0;
+			buf.resize((size_t)vg_jtext_bgzf_bound(bound, how.block));
+			if (vg_jtext_bgzf_lines(jt, heads, heads_len, span_recs.data(), span_recs.size(), sites, refs, buf.data(), buf.size(), &len, &text_len, &got_lines) != VG_OK) throw Error{std::string("vg_jtext_bgzf_lines failed: ") + vg_last_error()};
+			put(len);
+			n_text += text_len;
+		} else {
+			buf.resize((size_t)std::max<uint64_t>(1, bound));
+			const int rc = on_device ? vg_jtext_render(jt, heads, heads_len, span_recs.data(), span_recs.size(), sites, refs, buf.data(), buf.size(), &len, &got_lines)
+			                         : vg_jtext_render_host(pos.size(), (uint32_t)n, gts.data(), gqs.data(), heads, heads_len, span_recs.data(), span_recs.size(), sites, refs, (int)vcf_threads(), buf.data(), buf.size(), &len, &got_lines);
+			if (rc != VG_OK) throw Error{std::string(on_device ? "vg_jtext_render" : "vg_jtext_render_host") + " failed: " + vg_last_error()};
+			out->write((const char *)buf.data(), (size_t)len);
+			n_text += len;
+		}
+		n_lines += got_lines; n_spans++;
+	};
+
+	// the pass: vcf_pass's structure -- header lines on one thread in file order, then the run of data lines up to the next line
+	// that starts with '#', cut at line starts into one piece per thread; the threads plan, the spans render
+	const unsigned threads = vcf_threads();
+	const char *p = text.data(), *const end = p + text.size();
+	JointPlan run;
+	while (p < end) {
+		std::string seq;
+		header(p, end, seq);
+		if (stream) {
+			uint64_t len = 0;
+			buf.resize((size_t)vg_jtext_bgzf_bound(seq.size(), how.block));
+			if (vg_jtext_bgzf_text(jt, (const uint8_t *)seq.data(), seq.size(), buf.data(), buf.size(), &len) != VG_OK) throw Error{std::string("vg_jtext_bgzf_text failed: ") + vg_last_error()};
+			put(len);
+		} else out->write(seq.data(), seq.size());
+		const char *stop = end;
+		for (const char *q = p; q < end;) {
+			const char *h = (const char *)memchr(q, '#', (size_t)(end - q));
+			if (!h) break;
+			if (h == text.data() || h[-1] == '\n') { stop = h; break; }
+			q = h + 1;
+		}
+		const size_t bytes = (size_t)(stop - p);
+		const unsigned nt = bytes < (1u << 20) ? 1u : threads;
+		std::vector<const char *> cut(nt + 1, stop);
+		cut[0] = p;
+		for (unsigned t = 1; t < nt; t++) {
+			const char *c = p + bytes / nt * t;
+			const char *nl = (const char *)memchr(c, '\n', (size_t)(stop - c));
+			cut[t] = nl ? nl + 1 : stop;
+		}
+		std::vector<JointPlan> piece(nt);
+		std::vector<std::string> err(nt);
+		auto work = [&](unsigned t) {
+			const char *q = cut[t], *const e = cut[t + 1];
+			Scratch sc;
+			try {
+				while (q < e) { const Span ln = next_line(q, e); if (ln.size()) plan_line(ln, piece[t], sc); }
+			} catch (const Error &x) { err[t] = x.msg; }
+		};
+		if (nt == 1) work(0);
+		else {
+			std::vector<std::thread> th;
+			for (unsigned t = 0; t < nt; t++) th.emplace_back(work, t);
+			for (auto &x : th) x.join();
+		}
+		for (unsigned t = 0; t < nt; t++) if (!err[t].empty()) throw Error{err[t]};
+		run.clear();
+		for (unsigned t = 0; t < nt; t++) {                               // the pieces' plans, joined in file order
+			const uint64_t base = run.sites.size();
+			for (vg_jtext_record r : piece[t].recs) { r.site_at += base; run.recs.push_back(r); }
+			run.sites.insert(run.sites.end(), piece[t].sites.begin(), piece[t].sites.end());
+		}
+		n_records += run.recs.size();
+		for (size_t i0 = 0; i0 < run.recs.size();) {                      // one span per step
+			size_t i1 = i0 + 1;
+			const vg_jtext_record &a = run.recs[i0];
+			while (i1 < run.recs.size() && i1 - i0 < lines) {
+				const vg_jtext_record &r = run.recs[i1];
+				if (r.head_off + r.head_len - a.head_off > SPAN_HEADS || r.site_at + r.n_sites - a.site_at > site_cap) break;
+				i1++;
+			}
+			render_span(run, i0, i1);
+			i0 = i1;
+		}
+		p = stop;
+	}
+	if (stream) {
+		uint64_t len = 0;
+		buf.resize((size_t)vg_jtext_bgzf_bound(0, how.block));
+		if (vg_jtext_bgzf_end(jt, buf.data(), buf.size(), &len) != VG_OK) throw Error{std::string("vg_jtext_bgzf_end failed: ") + vg_last_error()};
+		put(len);
+		FILE *g = f;
+		f = nullptr;
+		if (fclose(g) != 0) throw Error{"cannot write " + vcf_out};
+	} else out->close();
+	clock_gettime(CLOCK_MONOTONIC, &c1);
+	if (how.verbose)
+		fprintf(stderr, "joint text: %s%s, %lu records, %lu lines written, %lu spans of at most %lu records, %lu text bytes, %.3f s\n", route, stream ? " (BGZF stream)" : "", (unsigned long)n_records, (unsigned long)n_lines,
+		        (unsigned long)n_spans, (unsigned long)lines, (unsigned long)n_text, (double)(c1.tv_sec - c0.tv_sec) + 1e-9 * (double)(c1.tv_nsec - c0.tv_nsec));
+	return true;
+}
+
+}  // namespace
+
+void write_joint_vcf(const std::vector<uint32_t> &pos, const std::vector<ChrLen> &chrlens, const std::vector<JointSample> &samples, const std::string &vcf_in, const std::string &vcf_out, const std::string *vcf_text, const VcfOutput &how,
+                     const JointTextRoute &text_route)
 {
 	for (const JointSample &js : samples)
 		if (js.calls.gt.size() != pos.size() || js.calls.gq.size() != pos.size()) throw Error{"sample " + js.name + " has calls for another number of sites than the index has"};
+	if (text_route.route != JointText::Host && write_joint_vcf_planned(pos, chrlens, samples, vcf_in, vcf_out, vcf_text, how, text_route)) return;
 	const CallBook book(pos, chrlens);
 	bool ok = vcf_text != nullptr;
 	std::string own;

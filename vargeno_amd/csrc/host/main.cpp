@@ -51,6 +51,15 @@
 //                         codes built for the block on the route that compresses it -- the same match finder, smaller files, exactly
 //                         vg_bgzf_deflate_host_coded(..., VG_DEFLATE_DYNAMIC, ...) on either route.  Any other value is refused before
 //                         a device is touched
+//   VARGENO_JOINT_TEXT=host|planned|device  joint (and the hidden jointvcf): who makes the data lines of the joint VCF; the file is the same
+//                         bytes on every route.  `host`, also unset or empty: the writer's loop, a line at a time on the VCF threads.
+//                         `planned`: the threads only build the plan of the lines (first eight fields + the key's sites, csrc/vg_jtext.h) and
+//                         spans of it are rendered by the header's host loop.  `device`: the spans are rendered by the joint text kernels
+//                         on replica 0's device (vg_jtext_*); with VARGENO_VCF_BGZF=device the header and the lines are joined and
+//                         deflated there, so the rendered text never crosses the link.  No device memory for it: `host` after all, one
+//                         line under VARGENO_VERBOSE, which also prints "joint text: <route>, records, lines, spans, text bytes, seconds".
+//                         Any other value is refused before an index or a device is looked at
+//   VARGENO_JOINT_TEXT_LINES=n  records per rendered span (default: what keeps a span's text near 128 MiB, at most 2^20)
 //   VARGENO_PAIRS_MIN_GQ=n  the table counts a call iff it is called and its GQ is at least n (default 0)
 //   VARGENO_VERBOSE=1     stderr: the index plan and start-up report, one "ingest, replica g:" line per route taken, the "reads:" line with
 //                         the wall time phase by phase; index: the "cuts:" line
@@ -148,6 +157,18 @@ static bool vcf_bgzf_codes(int *codes)
 	fprintf(stderr, "vargeno: VARGENO_VCF_CODES=%s is not understood: `fixed` or `dynamic` names the Huffman codes of a BGZF VCF, unset is `fixed`\n", v.c_str());
 	return false;
 }
+// VARGENO_JOINT_TEXT (and VARGENO_JOINT_TEXT_LINES), read once: who makes the data lines of the joint file -- `host` (unset or empty),
+// `planned` or `device` (vg_host.h: JointText).  false: another value -- said on stderr, in one line
+static bool joint_text_route(vgh::JointTextRoute *r)
+{
+	const std::string v = env_str("VARGENO_JOINT_TEXT");
+	r->route = v == "planned" ? vgh::JointText::Planned : v == "device" ? vgh::JointText::Device : vgh::JointText::Host;
+	r->lines = (uint64_t)std::max(0ll, atoll(env_str("VARGENO_JOINT_TEXT_LINES")));
+	r->device = 0;                                                   // (replica 0 sits on device 0)
+	if (v.empty() || v == "host" || r->route != vgh::JointText::Host) return true;
+	fprintf(stderr, "vargeno: VARGENO_JOINT_TEXT=%s is not understood: `host`, `planned` or `device` names who makes the lines of the joint VCF, unset is `host`\n", v.c_str());
+	return false;
+}
 // CPUs this process may use: the hardware threads, capped by a cgroup CPU quota (cpu.max: "<quota> <period>"; this pool's GPU boxes
 // give a container 16 CPUs' worth of time on a 256-thread host)
 static int usable_cpus()
@@ -202,6 +223,8 @@ struct GenoOptions {
 	const int pairs_threads = std::max(1, env_int("VARGENO_THREADS", usable_cpus()));
 	// how the VCF is written (VARGENO_VCF_BGZF and VARGENO_VCF_CODES; main() has refused a value that is neither of its two words): on replica 0's
 	// device, which is device 0, or on the BGZF threads
+	// joint: who makes the data lines (VARGENO_JOINT_TEXT; main() has refused a value that is none of its three words)
+	const vgh::JointTextRoute joint_text = [] { vgh::JointTextRoute r; (void)joint_text_route(&r); return r; }();
 	const vgh::VcfOutput vcf_out = [this] { vgh::VcfOutput w; (void)vcf_bgzf_route(&w.bgzf); (void)vcf_bgzf_codes(&w.codes); w.device = 0; w.threads = bgzf_threads; w.verbose = verbose; return w; }();
 	explicit GenoOptions(int devices) : have(devices)
 	{
@@ -1433,7 +1456,7 @@ static int run_cohort(const std::string &prefix, const std::string &manifest, co
 	for (auto &t : th) t.join();
 	if (joint && !failed.load()) {
 		try {
-			vgh::write_joint_vcf(sites.pos, chrlens, columns, vcf_in, *joint_out, &vcf_text, o.vcf_out);
+			vgh::write_joint_vcf(sites.pos, chrlens, columns, vcf_in, *joint_out, &vcf_text, o.vcf_out, o.joint_text);
 			if (!o.joint_pairs.empty()) joint_pairs_table(o, 0, columns, sites.pos.size());      // (replica 0 sits on device 0)
 		}
 		catch (const vgh::Error &e) { fprintf(stderr, "vargeno: %s\n", e.msg.c_str()); failed.store(1); }
@@ -1466,7 +1489,9 @@ int main(int argc, const char *argv[])
 	try {
 		vgh::VcfBgzf vcf_bgzf;
 		int vcf_codes = VG_DEFLATE_FIXED;
-		if ((opt == "geno" || opt == "cohort" || opt == "joint" || opt == "bgzfzip") && (!vcf_bgzf_route(&vcf_bgzf) || !vcf_bgzf_codes(&vcf_codes))) return EXIT_FAILURE;      // (before anything else is looked at)
+		if ((opt == "geno" || opt == "cohort" || opt == "joint" || opt == "jointvcf" || opt == "bgzfzip") &&(!vcf_bgzf_route(&vcf_bgzf) || !vcf_bgzf_codes(&vcf_codes))) return EXIT_FAILURE;      // (before anything else is looked at)
+		vgh::JointTextRoute joint_text;
+		if ((opt == "joint" || opt == "jointvcf") && !joint_text_route(&joint_text)) return EXIT_FAILURE;
 		if (opt == "index") {
 			arg_check(argc, 3);
 			vgh::IndexOptions io;
@@ -1679,7 +1704,14 @@ int main(int argc, const char *argv[])
 				vgh::call_sites(sc, js.calls);
 				columns.push_back(std::move(js));
 			}
-			vgh::write_joint_vcf(pos, vgh::read_chrlens(argv[2]), columns, argv[3], argv[4]);
+			// the output options of `joint`: VARGENO_VCF_BGZF / VARGENO_VCF_CODES (unset: plain text, as ever) and VARGENO_JOINT_TEXT
+			vgh::VcfOutput how;
+			how.bgzf = vcf_bgzf;
+			how.codes = vcf_codes;
+			how.threads = std::max(1, std::min(env_int("VARGENO_BGZF_THREADS", vgh::bgzf_threads_default(usable_cpus())), 256));
+			how.verbose = env_int("VARGENO_VERBOSE", 0) != 0;
+			if (how.bgzf == vgh::VcfBgzf::Device && vg_device_count() <= 0) { fprintf(stderr, "vargeno: no HIP device found (VARGENO_VCF_BGZF=host compresses on the host)\n"); return EXIT_FAILURE; }
+			vgh::write_joint_vcf(pos, vgh::read_chrlens(argv[2]), columns, argv[3], argv[4], nullptr, how, joint_text);
 			return EXIT_SUCCESS;
 		} else if (opt == "pairstsv") {
 			// hidden: the pair table alone, by the host loop, from one calls file per sample ("gt gq" per line; all of one length):

@@ -200,8 +200,23 @@ CallSummary write_genotyped_vcf(const SiteCounts &s, const std::vector<ChrLen> &
 // One multi-sample VCF: a line per record that at least one sample's own VCF would contain, a column per sample in the given order.
 // Throws when the SNP list cannot be read or the file cannot be written.
 struct JointSample { std::string name; SiteCalls calls; };
+// Who makes the data lines (VARGENO_JOINT_TEXT).  Host: the writer's own loop, a line at a time on the VCF threads.  Planned and Device:
+// the threads only build the PLAN of a run of data lines -- per line that names a key of the book its first eight fields and the key's
+// sites (../vg_jtext.h) -- and the run is rendered in spans of at most `lines` records (0: a default that keeps a span's text near
+// 128 MiB): Planned by the header's host loop (the plan builder's test on machines without a device), Device by the kernels of
+// vg_jtext_render on `device`.  With Device and VcfBgzf::Device header text and lines go through the handle's BGZF stream and the
+// rendered text never crosses the link; otherwise the text goes to the sink like the host loop's.  The handle is made before the
+// output file: VG_ENOMEM hands the file to Host (one line under `verbose`), any other failure throws.  The bytes of the file are
+// the same on every route.
+enum class JointText { Host, Planned, Device };
+struct JointTextRoute {
+	JointText route = JointText::Host;
+	uint64_t lines = 0;                            // VARGENO_JOINT_TEXT_LINES
+	int device = 0;
+};
 void write_joint_vcf(const std::vector<uint32_t> &pos, const std::vector<ChrLen> &chrlens, const std::vector<JointSample> &samples,
-                     const std::string &vcf_in, const std::string &vcf_out, const std::string *vcf_text = nullptr, const VcfOutput &how = VcfOutput());
+                     const std::string &vcf_in, const std::string &vcf_out, const std::string *vcf_text = nullptr, const VcfOutput &how = VcfOutput(),
+                     const JointTextRoute &text_route = JointTextRoute());
 bool read_whole_file(const std::string &path, std::string &text);
 
 }  // namespace vgh

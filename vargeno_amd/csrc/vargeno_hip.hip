@@ -18,6 +18,7 @@
 #include "vg_gunzip.h"
 #include "vg_caller.h"
 #include "vg_pairs.h"
+#include "vg_jtext.h"
 
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -4141,6 +4142,48 @@ extern "C" int vg_bgzf_deflate_host(const uint8_t *text, uint64_t nbytes, uint32
 	return vg_bgzf_deflate_host_coded(text, nbytes, block, eof, threads, VG_DEFLATE_FIXED, bgzf, cap, bgzf_len);
 }
 
+// One chunk of blocks, from text that is ALREADY on the device (the call below uploads it; the joint text stream renders it there):
+// d_text[0, tn) in k blocks of B bytes (the last one shorter) -> their BGZF bytes at dst in host memory, *sum of them.  The work
+// buffers hold k blocks: slots k * slot_words words, tok k * tok_words words (dynamic codes only), meta / offs and their host
+// mirrors k entries, out out_cap bytes.  Default stream, synchronous.
+struct BzDeflateDev {
+	uint32_t *slots, *tok; uint2 *meta; uint64_t *offs; uint8_t *out;
+	uint2 *h_meta; uint64_t *h_offs;
+	uint32_t slot_words, tok_words;
+	uint64_t out_cap;
+	bool timed; hipEvent_t e0, e1, e2;
+};
+static int bz_deflate_chunk(const BzDeflateDev &w, const uint8_t *d_text, uint64_t tn, uint32_t B, uint32_t k, bool dyn, uint8_t *dst, uint64_t *sum_out, float *ms_deflate, float *ms_frame)
+{
+	if (w.timed) HIP_TRY(hipEventRecord(w.e0, nullptr));
+	if (dyn) vg_bgzf_deflate_dyn_kernel<<<k, 64>>>(d_text, tn, B, k, w.slots, w.slot_words, w.tok, w.tok_words, w.meta);
+	else vg_bgzf_deflate_kernel<<<k, 64>>>(d_text, tn, B, k, w.slots, w.slot_words, w.meta);
+	HIP_TRY(hipGetLastError());
+	if (w.timed) HIP_TRY(hipEventRecord(w.e1, nullptr));
+	HIP_TRY(hipMemcpy(w.h_meta, w.meta, (size_t)k * sizeof(uint2), hipMemcpyDeviceToHost));
+	uint64_t sum = 0;
+	bool sane = true;
+	for (uint32_t i = 0; i < k; i++) {
+		const uint32_t n = (uint32_t)std::min<uint64_t>(B, tn - (uint64_t)i * B);
+		sane = sane && w.h_meta[i].x < n;                                  // (the core stores a block that would not shrink)
+		w.h_offs[i] = sum;
+		sum += VG_BGZF_HEADER + (w.h_meta[i].x ? w.h_meta[i].x : n + 5u) + VG_BGZF_TRAILER;
+	}
+	if (!sane || sum > w.out_cap) return fail(VG_EIO, "the deflate kernel reported a block that is not shorter than its text");
+	HIP_TRY(hipMemcpy(w.offs, w.h_offs, (size_t)k * sizeof(uint64_t), hipMemcpyHostToDevice));
+	vg_bgzf_frame_kernel<<<k, 64>>>(d_text, tn, B, k, w.slots, w.slot_words, w.meta, w.offs, w.out);
+	HIP_TRY(hipGetLastError());
+	if (w.timed) {
+		HIP_TRY(hipEventRecord(w.e2, nullptr)); HIP_TRY(hipEventSynchronize(w.e2));
+		float a = 0, c = 0;
+		HIP_TRY(hipEventElapsedTime(&a, w.e0, w.e1)); HIP_TRY(hipEventElapsedTime(&c, w.e1, w.e2));
+		*ms_deflate += a; *ms_frame += c;
+	}
+	HIP_TRY(hipMemcpy(dst, w.out, sum, hipMemcpyDeviceToHost));
+	*sum_out = sum;
+	return VG_OK;
+}
+
 extern "C" int vg_bgzf_deflate_device_coded(int device, const uint8_t *text, uint64_t nbytes, uint32_t block, int eof, int codes, uint8_t *bgzf, uint64_t cap, uint64_t *bgzf_len)
 {
 	int rc = bz_deflate_args(text, nbytes, block, codes, bgzf, bgzf_len);
@@ -4168,35 +4211,13 @@ extern "C" int vg_bgzf_deflate_device_coded(int device, const uint8_t *text, uin
 		if (timed) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); HIP_TRY(hipEventCreate(&e2)); }
 		float ms_deflate = 0, ms_frame = 0;
 		uint64_t len = 0;
+		const BzDeflateDev dev{d_slots.p, d_tok.p, d_meta.p, d_offs.p, d_out.p, meta.data(), offs.data(), slot_words, tok_words, chunk_out, timed, e0, e1, e2};
 		for (uint64_t b0 = 0; b0 < nb; b0 += chunk_blocks) {                   // one chunk per step
 			const uint32_t k = (uint32_t)std::min(chunk_blocks, nb - b0);
 			const uint64_t t0 = b0 * B, tn = std::min<uint64_t>((uint64_t)k * B, nbytes - t0);
 			HIP_TRY(hipMemcpy(d_text.p, text + t0, tn, hipMemcpyHostToDevice));
-			if (timed) HIP_TRY(hipEventRecord(e0, nullptr));
-			if (dyn) vg_bgzf_deflate_dyn_kernel<<<k, 64>>>(d_text.p, tn, B, k, d_slots.p, slot_words, d_tok.p, tok_words, d_meta.p);
-			else vg_bgzf_deflate_kernel<<<k, 64>>>(d_text.p, tn, B, k, d_slots.p, slot_words, d_meta.p);
-			HIP_TRY(hipGetLastError());
-			if (timed) HIP_TRY(hipEventRecord(e1, nullptr));
-			HIP_TRY(hipMemcpy(meta.data(), d_meta.p, (size_t)k * sizeof(uint2), hipMemcpyDeviceToHost));
 			uint64_t sum = 0;
-			bool sane = true;
-			for (uint32_t i = 0; i < k; i++) {
-				const uint32_t n = (uint32_t)std::min<uint64_t>(B, tn - (uint64_t)i * B);
-				sane = sane && meta[i].x < n;                                  // (the core stores a block that would not shrink)
-				offs[i] = sum;
-				sum += VG_BGZF_HEADER + (meta[i].x ? meta[i].x : n + 5u) + VG_BGZF_TRAILER;
-			}
-			if (!sane || sum > chunk_out) return fail(VG_EIO, "the deflate kernel reported a block that is not shorter than its text");
-			HIP_TRY(hipMemcpy(d_offs.p, offs.data(), (size_t)k * sizeof(uint64_t), hipMemcpyHostToDevice));
-			vg_bgzf_frame_kernel<<<k, 64>>>(d_text.p, tn, B, k, d_slots.p, slot_words, d_meta.p, d_offs.p, d_out.p);
-			HIP_TRY(hipGetLastError());
-			if (timed) {
-				HIP_TRY(hipEventRecord(e2, nullptr)); HIP_TRY(hipEventSynchronize(e2));
-				float a = 0, c = 0;
-				HIP_TRY(hipEventElapsedTime(&a, e0, e1)); HIP_TRY(hipEventElapsedTime(&c, e1, e2));
-				ms_deflate += a; ms_frame += c;
-			}
-			HIP_TRY(hipMemcpy(out.work + len, d_out.p, sum, hipMemcpyDeviceToHost));
+			if ((rc = bz_deflate_chunk(dev, d_text.p, tn, B, k, dyn, out.work + len, &sum, &ms_deflate, &ms_frame))) return rc;
 			len += sum;
 		}
 		if (timed) {
@@ -5577,4 +5598,537 @@ extern "C" int vg_pairs_host(const uint8_t *gt, const int32_t *gq, uint64_t n_si
 		vg_pairs_host_run(gt, gq, n_sites, n_samples, min_gq, threads, counts);
 		return VG_OK;
 	});
+}
+
+// ---- the joint VCF's data lines rendered on the device (vg_jtext.h; no reference counterpart) -------------------------------------
+// A vg_jtext holds, on one device, the calls of n_samples samples in SAMPLE-MAJOR columns and every buffer a span of records needs.
+//   narrow[sample][site]   uint16: gt << 14 | gq, the word vg_sample_calls_fetch moves, when 0 <= gq <= 16382; gt << 14 | 16383 says
+//                          "the gq is in the sample's wide column"; 0: no call.  2 bytes per site and sample
+//   wide[slot][site]       int32 gq, one column per sample that has a gq outside 0 .. 16382 (wide_slot[sample], -1: none); create
+//                          takes `wide_samples` of them
+// Sample-major makes vg_jtext_set one stream (a column arrives, a column is written) and the render a gather: a wave reads 64
+// samples' words of one site, 64 addresses n_sites * 2 bytes apart.  Site-major would make the render's reads one 128-byte line and
+// set a scatter.  No measurement supports the choice yet.
+//
+// A span of R records is P = G + 1 PIECES per record, G = ceil(n_samples / 64): piece 0 is the head and "\tGT:GQ", piece 1 + g the
+// cells of samples [64 g, 64 g + 64) -- the last one with the line's "\n".  Three steps:
+//   vg_jt_len_kernel      one wave per (record, group), one lane per sample: the lane's call (vg_jt_pick over the record's sites),
+//                         its cell's length, the wave's sum and whether any lane has a call
+//   vg_jt_settle_kernel   one lane per record: a record no group of which has a call gets length 0 in every piece; the others their
+//                         head piece's length and the newline; counts the lines
+//   vg_jt_scan_*          exclusive scan of the R * P lengths to 64-bit byte offsets: per-block sums, one block over the sums, apply
+//   vg_jt_write_kernel    TILED BY OUTPUT BYTES: a workgroup owns JT_TILE bytes of the output buffer at a dword-aligned address, finds
+//                         the pieces that overlap them by bisection of the offsets, composes them in LDS -- a wave per piece: a head is
+//                         a 64-byte-per-step copy, a group is one lane per sample, the cell's place a wave scan of the lengths -- and
+//                         leaves as aligned dword stores.  A line or a head longer than a tile simply spans several workgroups.  The
+//                         text may start at any byte of the buffer (the BGZF stream appends to pending text): the workgroup that owns
+//                         the dword the text starts in loads that dword into LDS first, so the bytes in front are written back as
+//                         they were; no other dword is shared.  The bytes after the end of the text in its last dword are unspecified
+// ------------------------------------------------------------------------------------------------
+constexpr uint32_t JT_TILE = 16384, JT_SCAN_ITEMS = 16, JT_SCAN_BLOCK = 256 * JT_SCAN_ITEMS;
+constexpr uint32_t VG_JTEXT_MAX_SAMPLES = 16384;
+constexpr uint64_t JT_CHUNK_TEXT = 16ull << 20, JT_CHUNK_BLOCKS = 16384;      // the stream's deflate work buffers: a chunk of blocks
+
+struct JtStore {
+	const uint16_t *narrow; const int32_t *wide; const int32_t *wide_slot;
+	uint64_t n_sites; uint32_t n_samples;
+};
+// the call of `sample` at `site` as vg_jt_pick wants it: gt << 32 | (uint32_t)gq
+__device__ __forceinline__ uint64_t jt_call(const JtStore &st, uint32_t sample, int32_t slot, uint32_t site)
+{
+	const uint32_t w = st.narrow[(uint64_t)sample * st.n_sites + site];
+	uint32_t gq = w & 0x3fffu;
+	if (gq == VG_JT_GQ_ESCAPE && slot >= 0) gq = (uint32_t)st.wide[(uint64_t)slot * st.n_sites + site];
+	return (uint64_t)(w >> 14) << 32 | gq;
+}
+__device__ __forceinline__ vg_jt_cell_t jt_lane_cell(const JtStore &st, uint32_t sample, const uint32_t *sites, uint32_t n, bool *called)
+{
+	uint64_t v = 0;
+	if (sample < st.n_samples) {
+		const int32_t slot = st.wide_slot[sample];
+		v = vg_jt_pick(sites, n, [&](uint32_t site) { return jt_call(st, sample, slot, site); });
+	}
+	*called = (v >> 32) != 0;
+	vg_jt_cell_t c = vg_jt_cell((uint32_t)(v >> 32), (int32_t)(uint32_t)v);
+	if (sample >= st.n_samples) c.len = 0;
+	return c;
+}
+
+// one sample's columns -> its narrow column, and its wide one if it has a slot (wide != nullptr)
+__global__ __launch_bounds__(256) void vg_jt_pack_kernel(const uint8_t *__restrict__ gt, const int32_t *__restrict__ gq, uint64_t n_sites, uint16_t *__restrict__ narrow, int32_t *__restrict__ wide)
+{
+	for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n_sites; i += (uint64_t)gridDim.x * 256) {
+		const uint32_t g = gt[i];
+		const int32_t q = gq[i];
+		const bool fits = q >= 0 && q < (int32_t)VG_JT_GQ_ESCAPE;
+		narrow[i] = g ? (uint16_t)(g << 14 | (fits ? (uint32_t)q : VG_JT_GQ_ESCAPE)) : (uint16_t)0;
+		if (wide) wide[i] = g ? q : 0;
+	}
+}
+
+__global__ __launch_bounds__(256) void vg_jt_len_kernel(JtStore st, const vg_jtext_record *__restrict__ recs, uint64_t n_records, const uint32_t *__restrict__ sites, uint32_t G, uint32_t *__restrict__ len)
+{
+	const uint32_t lane = threadIdx.x & 63;
+	const uint64_t u = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);          // (the same for a wave's lanes)
+	if (u >= n_records * G) return;
+	const uint64_t r = u / G;
+	const uint32_t g = (uint32_t)(u % G);
+	const vg_jtext_record rec = recs[r];
+	bool called;
+	const vg_jt_cell_t c = jt_lane_cell(st, g * 64 + lane, sites + rec.site_at, rec.n_sites, &called);
+	uint32_t sum = c.len;
+	for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+	const bool any = __ballot(called) != 0;
+	if (lane == 0) len[r * (G + 1) + 1 + g] = sum | (any ? 1u << 31 : 0u);
+}
+
+__global__ __launch_bounds__(256) void vg_jt_settle_kernel(const vg_jtext_record *__restrict__ recs, uint64_t n_records, uint32_t G, uint32_t *__restrict__ len, unsigned long long *__restrict__ n_lines)
+{
+	const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+	bool line = false;
+	if (r < n_records) {
+		uint32_t *p = len + r * (G + 1);
+		for (uint32_t g = 0; g < G; g++) line = line || (p[1 + g] >> 31);
+		p[0] = line ? recs[r].head_len + 6u : 0u;
+		for (uint32_t g = 0; g < G; g++) p[1 + g] = line ? (p[1 + g] & 0x7fffffffu) + (g + 1 == G ? 1u : 0u) : 0u;
+	}
+	const unsigned long long votes = __ballot(line);
+	if ((threadIdx.x & 63) == 0 && votes) atomicAdd(n_lines, (unsigned long long)__popcll(votes));
+}
+
+// exclusive scan of len[0, n) into off[0, n], off[n] = the total: a thread owns JT_SCAN_ITEMS consecutive items
+__device__ __forceinline__ uint64_t jt_block_exclusive(uint64_t mine, uint64_t *lds /* 256 */, uint64_t *total)
+{
+	const unsigned t = threadIdx.x;
+	lds[t] = mine;
+	__syncthreads();
+	for (unsigned o = 1; o < 256; o <<= 1) {
+		const uint64_t y = t >= o ? lds[t - o] : 0;
+		__syncthreads();
+		lds[t] += y;
+		__syncthreads();
+	}
+	const uint64_t incl = lds[t];
+	*total = lds[255];
+	__syncthreads();
+	return incl - mine;
+}
+__global__ __launch_bounds__(256) void vg_jt_scan_sums_kernel(const uint32_t *__restrict__ len, uint64_t n, uint64_t *__restrict__ bsum)
+{
+	__shared__ uint64_t lds[256];
+	const uint64_t base = (uint64_t)blockIdx.x * JT_SCAN_BLOCK + (uint64_t)threadIdx.x * JT_SCAN_ITEMS;
+	uint64_t s = 0;
+	for (uint32_t i = 0; i < JT_SCAN_ITEMS; i++) if (base + i < n) s += len[base + i];
+	uint64_t total;
+	(void)jt_block_exclusive(s, lds, &total);
+	if (threadIdx.x == 0) bsum[blockIdx.x] = total;
+}
+// one workgroup: bsum[0, nb) -> its exclusive scan in place, the total to bsum[nb] and off_total
+__global__ __launch_bounds__(256) void vg_jt_scan_top_kernel(uint64_t *__restrict__ bsum, uint64_t nb, uint64_t *__restrict__ off_total)
+{
+	__shared__ uint64_t lds[256];
+	uint64_t carry = 0;
+	for (uint64_t c = 0; c < nb; c += 256) {
+		const uint64_t i = c + threadIdx.x;
+		const uint64_t v = i < nb ? bsum[i] : 0;
+		uint64_t total;
+		const uint64_t ex = jt_block_exclusive(v, lds, &total);
+		if (i < nb) bsum[i] = carry + ex;
+		carry += total;
+	}
+	if (threadIdx.x == 0) { bsum[nb] = carry; *off_total = carry; }
+}
+__global__ __launch_bounds__(256) void vg_jt_scan_apply_kernel(const uint32_t *__restrict__ len, uint64_t n, const uint64_t *__restrict__ bsum, uint64_t *__restrict__ off)
+{
+	__shared__ uint64_t lds[256];
+	const uint64_t base = (uint64_t)blockIdx.x * JT_SCAN_BLOCK + (uint64_t)threadIdx.x * JT_SCAN_ITEMS;
+	uint32_t v[JT_SCAN_ITEMS];
+	uint64_t s = 0;
+#pragma unroll
+	for (uint32_t i = 0; i < JT_SCAN_ITEMS; i++) { v[i] = base + i < n ? len[base + i] : 0u; s += v[i]; }
+	uint64_t total;
+	uint64_t at = bsum[blockIdx.x] + jt_block_exclusive(s, lds, &total);
+#pragma unroll
+	for (uint32_t i = 0; i < JT_SCAN_ITEMS; i++) { if (base + i < n) off[base + i] = at; at += v[i]; }
+}
+
+// out: the dword-aligned output buffer; the span's text goes to out[start, start + off[n_items]).  grid: the tiles from the dword
+// that holds byte `start` on (the host sizes it by the span's bound; a tile beyond the text returns)
+__global__ __launch_bounds__(256) void vg_jt_write_kernel(JtStore st, const uint8_t *__restrict__ heads, const vg_jtext_record *__restrict__ recs, const uint32_t *__restrict__ sites, uint32_t G,
+                                                          const uint32_t *__restrict__ len, const uint64_t *__restrict__ off, uint64_t n_items, uint8_t *out, uint64_t start)
+{
+	__shared__ uint32_t tile[JT_TILE / 4];
+	uint8_t *const tb = (uint8_t *)tile;
+	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, P = G + 1;
+	const uint64_t end_abs = start + off[n_items];
+	const uint64_t A = (start & ~3ull) + (uint64_t)blockIdx.x * JT_TILE;       // the tile: bytes [A, A + JT_TILE) of out
+	if (A >= end_abs) return;
+	// the part of the text this tile holds, as text offsets [lo, hi); a text offset x lies at tile byte x - shift
+	const uint64_t lo = (A > start ? A : start) - start, hi = (A + JT_TILE < end_abs ? A + JT_TILE : end_abs) - start;
+	const int64_t shift = (int64_t)A - (int64_t)start;
+	if (A < start && threadIdx.x == 0) tile[0] = *(const uint32_t *)(out + A);   // bytes of earlier text in the first dword stay as they are
+	uint64_t a = 0, b = n_items;                                              // the first piece that ends behind lo
+	while (a < b) { const uint64_t m = a + ((b - a) >> 1); if (off[m + 1] > lo) b = m; else a = m + 1; }
+	__syncthreads();
+	for (uint64_t p = a + wave; p < n_items; p += 4) {                          // a piece per wave and step
+		const uint64_t o = off[p];
+		if (o >= hi) break;
+		const uint32_t n = len[p];
+		if (!n) continue;
+		const uint64_t r = p / P;
+		const uint32_t k = (uint32_t)(p % P);
+		const vg_jtext_record rec = recs[r];
+		if (k == 0) {
+			// the head and "\tGT:GQ": bytes [j0, j1) of the piece are this tile's
+			const uint64_t j0 = lo > o ? lo - o : 0, j1 = hi - o < n ? hi - o : n;
+			const uint8_t *h = heads + rec.head_off;
+			for (uint64_t j = j0 + lane; j < j1; j += 64) {
+				const uint32_t v = j < rec.head_len ? h[j] : (uint32_t)(0x51473a544709ull >> (8 * (j - rec.head_len))) & 0xffu;
+				tb[(int64_t)(o + j) - shift] = (uint8_t)v;
+			}
+		} else {
+			const uint32_t g = k - 1;
+			bool called;
+			const vg_jt_cell_t c = jt_lane_cell(st, g * 64 + lane, sites + rec.site_at, rec.n_sites, &called);
+			uint32_t incl = c.len;
+			for (int s = 1; s < 64; s <<= 1) { const uint32_t y = __shfl_up(incl, s); if ((int)lane >= s) incl += y; }
+			const uint64_t at = o + incl - c.len;                               // the cell's text offset
+			for (uint32_t i = 0; i < c.len; i++) {
+				const uint64_t x = at + i;
+				if (x >= lo && x < hi) tb[(int64_t)x - shift] = (uint8_t)vg_jt_byte(c, i);
+			}
+			if (g + 1 == G && lane == 0) { const uint64_t x = o + n - 1; if (x >= lo && x < hi) tb[(int64_t)x - shift] = '\n'; }
+		}
+	}
+	__syncthreads();
+	const uint32_t n_dw = (uint32_t)(((int64_t)hi - shift + 3) / 4);
+	uint32_t *dst = (uint32_t *)(out + A);
+	for (uint32_t i = threadIdx.x; i < n_dw; i += 256) dst[i] = tile[i];       // 1 KiB of the tile per step
+}
+
+struct vg_jtext {
+	int device = 0;
+	uint64_t n_sites = 0, rec_cap = 0, head_cap = 0, site_cap = 0, text_cap = 0, text_room = 0, dev_bytes = 0;
+	uint32_t n_samples = 0, G = 0, wide_cap = 0;
+	uint16_t *d_narrow = nullptr;
+	int32_t *d_wide = nullptr, *d_wide_slot = nullptr, *d_gq = nullptr;
+	uint8_t *d_gt = nullptr, *d_heads = nullptr, *d_text = nullptr;
+	vg_jtext_record *d_recs = nullptr;
+	uint32_t *d_sites = nullptr, *d_len = nullptr;
+	uint64_t *d_off = nullptr, *d_bsum = nullptr;
+	unsigned long long *d_lines = nullptr;
+	std::vector<int32_t> wide_slot;                  // host mirror of d_wide_slot
+	std::vector<uint8_t> slot_used;
+	hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
+	// the BGZF stream
+	bool with_bgzf = false, open = false, dyn = false;
+	uint32_t B = 0;
+	uint64_t pend = 0;                               // bytes of text in d_text that no block holds yet
+	uint32_t *d_slots = nullptr, *d_tok = nullptr;
+	uint2 *d_meta = nullptr;
+	uint64_t *d_boffs = nullptr;
+	uint8_t *d_bout = nullptr;
+	uint64_t bout_cap = 0;
+	std::vector<uint2> h_meta;
+	std::vector<uint64_t> h_boffs;
+};
+
+static void jtext_free(vg_jtext *jt)
+{
+	if (!jt) return;
+	(void)hipSetDevice(jt->device);
+	for (hipEvent_t e : {jt->ev0, jt->ev1, jt->ev2}) if (e) (void)hipEventDestroy(e);
+	for (void *p : {(void *)jt->d_narrow, (void *)jt->d_wide, (void *)jt->d_wide_slot, (void *)jt->d_gq, (void *)jt->d_gt, (void *)jt->d_heads, (void *)jt->d_text, (void *)jt->d_recs, (void *)jt->d_sites,
+	                (void *)jt->d_len, (void *)jt->d_off, (void *)jt->d_bsum, (void *)jt->d_lines, (void *)jt->d_slots, (void *)jt->d_tok, (void *)jt->d_meta, (void *)jt->d_boffs, (void *)jt->d_bout})
+		if (p) (void)hipFree(p);
+	(void)hipGetLastError();
+	delete jt;
+}
+
+extern "C" uint64_t vg_jtext_text_bound(uint64_t head_bytes, uint64_t n_records, uint32_t n_samples) { return vg_jt_bound(head_bytes, n_records, n_samples); }
+extern "C" uint64_t vg_jtext_bgzf_bound(uint64_t text_bytes, uint32_t block)
+{
+	if (block > VG_BGZF_TEXT_BLOCK) return 0;
+	const uint32_t B = block ? block : VG_BGZF_TEXT_BLOCK;
+	return vg_bgzf_bound(text_bytes + B - 1, B);                              // (the pending text of earlier calls: less than a block)
+}
+
+extern "C" int vg_jtext_create(int device, uint64_t n_sites, uint32_t n_samples, uint32_t wide_samples, uint64_t max_records, uint64_t max_head_bytes, uint64_t max_site_refs, int with_bgzf, vg_jtext **out)
+{
+	if (!out) return fail(VG_EINVAL, "null argument");
+	*out = nullptr;
+	if (n_samples == 0) return fail(VG_EINVAL, "vg_jtext_create: no samples");
+	if (n_sites >= (1ull << 32)) return fail(VG_EINVAL, "vg_jtext_create: 2^32 sites or more");
+	if (n_samples > VG_JTEXT_MAX_SAMPLES) return fail(VG_ETOOBIG, "vg_jtext_create: more than %s samples", std::to_string(VG_JTEXT_MAX_SAMPLES).c_str());
+	if (max_records == 0 || max_records >= (1ull << 32) || max_head_bytes >= (1ull << 40) || max_site_refs >= (1ull << 40)) return fail(VG_EINVAL, "vg_jtext_create: a span holds 1 to 2^32 - 1 records and less than 2^40 head bytes and site references");
+	int ndev = 0;
+	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(VG_ENODEV, "no HIP device available (vg_jtext_render_host is the host's loop)"); }
+	return guarded([&]() -> int {
+		HIP_TRY(hipSetDevice(device));
+		vg_jtext *jt = new vg_jtext;
+		jt->device = device; jt->n_sites = n_sites; jt->n_samples = n_samples; jt->G = (n_samples + 63) / 64; jt->wide_cap = std::min(wide_samples, n_samples);
+		jt->rec_cap = max_records; jt->head_cap = max_head_bytes; jt->site_cap = max_site_refs; jt->with_bgzf = with_bgzf != 0;
+		jt->text_cap = vg_jt_bound(max_head_bytes, max_records, n_samples);
+		jt->text_room = jt->text_cap + VG_BGZF_TEXT_BLOCK;
+		const uint64_t items = max_records * (jt->G + 1);
+		jt->bout_cap = JT_CHUNK_TEXT + JT_CHUNK_BLOCKS * 32 + 64;
+		struct { void **p; uint64_t bytes; const char *what; bool stream; } want[] = {
+			{(void **)&jt->d_narrow, (uint64_t)n_samples * n_sites * 2, "the samples' columns", false}, {(void **)&jt->d_wide, (uint64_t)jt->wide_cap * n_sites * 4, "the wide columns", false},
+			{(void **)&jt->d_wide_slot, (uint64_t)n_samples * 4, "the wide column table", false}, {(void **)&jt->d_gt, n_sites, "a gt column", false}, {(void **)&jt->d_gq, n_sites * 4, "a gq column", false},
+			{(void **)&jt->d_heads, max_head_bytes, "the heads", false}, {(void **)&jt->d_recs, max_records * sizeof(vg_jtext_record), "the records", false}, {(void **)&jt->d_sites, max_site_refs * 4, "the site references", false},
+			{(void **)&jt->d_len, items * 4, "the piece lengths", false}, {(void **)&jt->d_off, (items + 1) * 8, "the piece offsets", false}, {(void **)&jt->d_bsum, (items / JT_SCAN_BLOCK + 2) * 8, "the scan's sums", false},
+			{(void **)&jt->d_lines, 8, "the line count", false}, {(void **)&jt->d_text, jt->text_room + JT_TILE + 64, "the text", false},
+			{(void **)&jt->d_slots, JT_CHUNK_TEXT + JT_CHUNK_BLOCKS * (VG_DEF_SLACK + 32), "deflate slots", true}, {(void **)&jt->d_tok, (JT_CHUNK_TEXT + JT_CHUNK_BLOCKS * 16) * 4, "deflate tokens", true},
+			{(void **)&jt->d_meta, JT_CHUNK_BLOCKS * sizeof(uint2), "block results", true}, {(void **)&jt->d_boffs, JT_CHUNK_BLOCKS * 8, "block offsets", true}, {(void **)&jt->d_bout, jt->bout_cap, "BGZF bytes", true}};
+		for (auto &w : want) {
+			if (w.stream && !jt->with_bgzf) continue;
+			const uint64_t bytes = w.bytes ? w.bytes : 8;
+			if (vg_malloc_patient(w.p, bytes) != hipSuccess) {
+				(void)hipGetLastError();
+				*w.p = nullptr;
+				jtext_free(jt);
+				return fail(VG_ENOMEM, "vg_jtext_create: no device memory for %s (%s bytes)", w.what, std::to_string(bytes).c_str());
+			}
+			jt->dev_bytes += bytes;
+		}
+		jt->wide_slot.assign(n_samples, -1);
+		jt->slot_used.assign(jt->wide_cap, 0);
+		if (jt->with_bgzf) { jt->h_meta.resize(JT_CHUNK_BLOCKS); jt->h_boffs.resize(JT_CHUNK_BLOCKS); }
+		hipError_t e = hipEventCreate(&jt->ev0);
+		if (e == hipSuccess) e = hipEventCreate(&jt->ev1);
+		if (e == hipSuccess) e = hipEventCreate(&jt->ev2);
+		if (e == hipSuccess) e = hipMemset(jt->d_narrow, 0, std::max<uint64_t>(8, (uint64_t)n_samples * n_sites * 2));
+		if (e == hipSuccess) e = hipMemset(jt->d_wide_slot, 0xff, (uint64_t)n_samples * 4);
+		if (e == hipSuccess) e = hipMemset(jt->d_text, 0, 64);
+		if (e == hipSuccess) e = hipDeviceSynchronize();
+		if (e != hipSuccess) { jtext_free(jt); return fail(VG_ENODEV, "vg_jtext_create: %s", hipGetErrorString(e)); }
+		*out = jt;
+		return VG_OK;
+	});
+}
+
+extern "C" void vg_jtext_destroy(vg_jtext *jt) { jtext_free(jt); }
+extern "C" uint64_t vg_jtext_device_bytes(const vg_jtext *jt) { return jt ? jt->dev_bytes : 0; }
+
+extern "C" int vg_jtext_set(vg_jtext *jt, uint32_t sample, const uint8_t *gt, const int32_t *gq)
+{
+	if (!jt || !gt || !gq) return fail(VG_EINVAL, "null argument");
+	if (sample >= jt->n_samples) return fail(VG_EINVAL, "vg_jtext_set: sample %s is out of range", std::to_string(sample).c_str());
+	bool wide = false;
+	for (uint64_t i = 0; i < jt->n_sites; i++) {
+		if (gt[i] > 3) return fail(VG_EINVAL, "vg_jtext_set: a gt above 3 (site %s)", std::to_string(i).c_str());
+		wide = wide || (gt[i] && (gq[i] < 0 || gq[i] >= (int32_t)VG_JT_GQ_ESCAPE));
+	}
+	int32_t slot = jt->wide_slot[sample];
+	if (wide && slot < 0) {
+		for (uint32_t k = 0; k < jt->wide_cap && slot < 0; k++) if (!jt->slot_used[k]) slot = (int32_t)k;
+		if (slot < 0) return fail(VG_ETOOBIG, "vg_jtext_set: sample %s has a gq outside 0 .. 16382 and every wide column is taken (vg_jtext_create's wide_samples)", std::to_string(sample).c_str());
+	}
+	if (jt->n_sites == 0) return VG_OK;
+	HIP_TRY(hipSetDevice(jt->device));
+	HIP_TRY(hipMemcpy(jt->d_gt, gt, jt->n_sites, hipMemcpyHostToDevice));
+	HIP_TRY(hipMemcpy(jt->d_gq, gq, jt->n_sites * 4, hipMemcpyHostToDevice));
+	const int32_t now = wide ? slot : -1;
+	const unsigned grid = (unsigned)std::min<uint64_t>((jt->n_sites + 255) / 256, 4096);
+	vg_jt_pack_kernel<<<grid, 256>>>(jt->d_gt, jt->d_gq, jt->n_sites, jt->d_narrow + (uint64_t)sample * jt->n_sites, wide ? jt->d_wide + (uint64_t)slot * jt->n_sites : nullptr);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpy(jt->d_wide_slot + sample, &now, 4, hipMemcpyHostToDevice));
+	HIP_TRY(hipDeviceSynchronize());
+	if (jt->wide_slot[sample] >= 0 && !wide) jt->slot_used[(size_t)jt->wide_slot[sample]] = 0;
+	if (wide) jt->slot_used[(size_t)slot] = 1;
+	jt->wide_slot[sample] = now;
+	return VG_OK;
+}
+
+// what every call that takes a span checks before anything is written: null pointers and references outside their arrays are
+// VG_EINVAL, a span beyond the handle's limits VG_ETOOBIG.  *head_sum: the sum of the records' head_len
+static int jt_span_args(const uint64_t n_sites, const uint8_t *heads, uint64_t heads_len, const vg_jtext_record *recs, uint64_t n_records, const uint32_t *sites, uint64_t n_site_refs, uint64_t *head_sum)
+{
+	if ((!heads && heads_len) || (!recs && n_records) || (!sites && n_site_refs)) return fail(VG_EINVAL, "null argument");
+	uint64_t sum = 0;
+	for (uint64_t i = 0; i < n_records; i++) {
+		const vg_jtext_record &r = recs[i];
+		if (r.head_off > heads_len || r.head_len > heads_len - r.head_off) return fail(VG_EINVAL, "record %s: its head lies outside the heads", std::to_string(i).c_str());
+		if (r.site_at > n_site_refs || r.n_sites > n_site_refs - r.site_at) return fail(VG_EINVAL, "record %s: its site run lies outside the site references", std::to_string(i).c_str());
+		sum += r.head_len;
+	}
+	for (uint64_t i = 0; i < n_site_refs; i++) if (sites[i] >= n_sites) return fail(VG_EINVAL, "site reference %s names a site the handle does not have", std::to_string(i).c_str());
+	*head_sum = sum;
+	return VG_OK;
+}
+
+// the three steps of a span (checked by jt_span_args and against the limits): its text to d_text[start, start + *total)
+static int jt_render_dev(vg_jtext *jt, const uint8_t *heads, uint64_t heads_len, const vg_jtext_record *recs, uint64_t n_records, const uint32_t *sites, uint64_t n_site_refs, uint64_t head_sum, uint64_t start,
+                         uint64_t *total, uint64_t *n_lines)
+{
+	*total = 0; *n_lines = 0;
+	if (!n_records) return VG_OK;
+	if (heads_len) HIP_TRY(hipMemcpy(jt->d_heads, heads, heads_len, hipMemcpyHostToDevice));
+	HIP_TRY(hipMemcpy(jt->d_recs, recs, n_records * sizeof(vg_jtext_record), hipMemcpyHostToDevice));
+	if (n_site_refs) HIP_TRY(hipMemcpy(jt->d_sites, sites, n_site_refs * 4, hipMemcpyHostToDevice));
+	HIP_TRY(hipMemset(jt->d_lines, 0, 8));
+	const JtStore st{jt->d_narrow, jt->d_wide, jt->d_wide_slot, jt->n_sites, jt->n_samples};
+	const uint32_t G = jt->G;
+	const uint64_t items = n_records * (G + 1), nb = (items + JT_SCAN_BLOCK - 1) / JT_SCAN_BLOCK;
+	const bool timed = getenv("VG_VERBOSE") != nullptr;
+	if (timed) HIP_TRY(hipEventRecord(jt->ev0, nullptr));
+	vg_jt_len_kernel<<<(unsigned)((n_records * G + 3) / 4), 256>>>(st, jt->d_recs, n_records, jt->d_sites, G, jt->d_len);
+	HIP_TRY(hipGetLastError());
+	vg_jt_settle_kernel<<<(unsigned)((n_records + 255) / 256), 256>>>(jt->d_recs, n_records, G, jt->d_len, jt->d_lines);
+	HIP_TRY(hipGetLastError());
+	vg_jt_scan_sums_kernel<<<(unsigned)nb, 256>>>(jt->d_len, items, jt->d_bsum);
+	HIP_TRY(hipGetLastError());
+	vg_jt_scan_top_kernel<<<1, 256>>>(jt->d_bsum, nb, jt->d_off + items);
+	HIP_TRY(hipGetLastError());
+	vg_jt_scan_apply_kernel<<<(unsigned)nb, 256>>>(jt->d_len, items, jt->d_bsum, jt->d_off);
+	HIP_TRY(hipGetLastError());
+	if (timed) HIP_TRY(hipEventRecord(jt->ev1, nullptr));
+	// the tiles of the bound: one that lies beyond the text returns at once
+	const uint64_t bound = vg_jt_bound(head_sum, n_records, jt->n_samples);
+	const uint64_t tiles = ((start & 3) + bound + JT_TILE - 1) / JT_TILE;
+	vg_jt_write_kernel<<<(unsigned)tiles, 256>>>(st, jt->d_heads, jt->d_recs, jt->d_sites, G, jt->d_len, jt->d_off, items, jt->d_text, start);
+	HIP_TRY(hipGetLastError());
+	if (timed) HIP_TRY(hipEventRecord(jt->ev2, nullptr));
+	unsigned long long lines = 0;
+	HIP_TRY(hipMemcpy(total, jt->d_off + items, 8, hipMemcpyDeviceToHost));
+	HIP_TRY(hipMemcpy(&lines, jt->d_lines, 8, hipMemcpyDeviceToHost));
+	*n_lines = lines;
+	if (*total > bound) return fail(VG_EIO, "the joint text kernels produced more bytes than the span's bound");
+	if (timed) {
+		float a = 0, c = 0;
+		HIP_TRY(hipEventElapsedTime(&a, jt->ev0, jt->ev1)); HIP_TRY(hipEventElapsedTime(&c, jt->ev1, jt->ev2));
+		fprintf(stderr, "[vargeno_hip] joint text: %lu records, %u samples, %lu lines, %lu bytes: lengths + scan %.3f ms, write %.3f ms (%.2f GB/s text)\n", (unsigned long)n_records, jt->n_samples, (unsigned long)lines,
+		        (unsigned long)*total, a, c, c > 0 ? (double)*total / 1e6 / c : 0.0);
+	}
+	return VG_OK;
+}
+
+// a span against the handle's limits; the bound of its text must fit the text buffer behind `start` bytes
+static int jt_span_limits(const vg_jtext *jt, uint64_t heads_len, uint64_t n_records, uint64_t n_site_refs, uint64_t head_sum)
+{
+	const uint64_t bound = vg_jt_bound(head_sum, n_records, jt->n_samples);
+	if (n_records > jt->rec_cap || heads_len > jt->head_cap || n_site_refs > jt->site_cap || bound > jt->text_cap || n_records * (jt->G + 1) >= (1ull << 32) || bound / JT_TILE >= (1ull << 31))      // (the last two: a grid's size)
+		return fail(VG_ETOOBIG, "the span is beyond the limits the handle was created with (records, head bytes, site references)");
+	return VG_OK;
+}
+
+extern "C" int vg_jtext_render(vg_jtext *jt, const uint8_t *heads, uint64_t heads_len, const vg_jtext_record *records, uint64_t n_records, const uint32_t *sites, uint64_t n_site_refs,
+                               uint8_t *text, uint64_t cap, uint64_t *len, uint64_t *n_lines)
+{
+	if (!jt || !len || !n_lines || (!text && cap)) return fail(VG_EINVAL, "null argument");
+	if (jt->open) return fail(VG_EINVAL, "vg_jtext_render: a BGZF stream is open on the handle (vg_jtext_bgzf_end closes it)");
+	uint64_t head_sum = 0;
+	int rc = jt_span_args(jt->n_sites, heads, heads_len, records, n_records, sites, n_site_refs, &head_sum);
+	if (rc || (rc = jt_span_limits(jt, heads_len, n_records, n_site_refs, head_sum))) return rc;
+	if (cap < vg_jt_bound(head_sum, n_records, jt->n_samples)) return fail(VG_ETOOBIG, "the text buffer is smaller than the span's bound (vg_jtext_text_bound)");
+	HIP_TRY(hipSetDevice(jt->device));
+	uint64_t total = 0, lines = 0;
+	if ((rc = jt_render_dev(jt, heads, heads_len, records, n_records, sites, n_site_refs, head_sum, 0, &total, &lines))) return rc;
+	if (total) HIP_TRY(hipMemcpy(text, jt->d_text, total, hipMemcpyDeviceToHost));
+	*len = total; *n_lines = lines;
+	return VG_OK;
+}
+
+extern "C" int vg_jtext_render_host(uint64_t n_sites, uint32_t n_samples, const uint8_t *const *gt, const int32_t *const *gq, const uint8_t *heads, uint64_t heads_len, const vg_jtext_record *records, uint64_t n_records,
+                                    const uint32_t *sites, uint64_t n_site_refs, int threads, uint8_t *text, uint64_t cap, uint64_t *len, uint64_t *n_lines)
+{
+	if (!gt || !gq || !len || !n_lines || (!text && cap)) return fail(VG_EINVAL, "null argument");
+	if (n_samples == 0) return fail(VG_EINVAL, "vg_jtext_render_host: no samples");
+	if (n_samples > VG_JTEXT_MAX_SAMPLES) return fail(VG_ETOOBIG, "vg_jtext_render_host: more than %s samples", std::to_string(VG_JTEXT_MAX_SAMPLES).c_str());
+	if (n_sites >= (1ull << 32)) return fail(VG_EINVAL, "vg_jtext_render_host: 2^32 sites or more");
+	for (uint32_t s = 0; s < n_samples; s++) if (gt[s] && !gq[s]) return fail(VG_EINVAL, "null argument");
+	uint64_t head_sum = 0;
+	const int rc = jt_span_args(n_sites, heads, heads_len, records, n_records, sites, n_site_refs, &head_sum);
+	if (rc) return rc;
+	return guarded([&]() -> int {
+		if (!vg_jtext_host_run(gt, gq, n_samples, heads, records, n_records, sites, threads, text, cap, len, n_lines)) return fail(VG_ETOOBIG, "the text buffer is smaller than the span's bound (vg_jtext_text_bound)");
+		return VG_OK;
+	});
+}
+
+// ---- the BGZF stream of a vg_jtext: text gathers in d_text; every call compresses the whole blocks it completed ----
+// d_text[0, have): its whole blocks (final: and the partial last one) -> bgzf + *len, chunk by chunk; the rest moves to the front
+static int jt_stream_flush(vg_jtext *jt, uint64_t have, bool final, uint8_t *bgzf, uint64_t *len)
+{
+	const uint32_t B = jt->B;
+	const uint64_t nb = final ? vg_bgzf_blocks_of(have, B) : have / B;
+	const uint64_t chunk_blocks = std::min<uint64_t>(JT_CHUNK_BLOCKS, std::max<uint64_t>(1, JT_CHUNK_TEXT / B));
+	const bool timed = getenv("VG_VERBOSE") != nullptr;
+	const BzDeflateDev dev{jt->d_slots, jt->d_tok, jt->d_meta, jt->d_boffs, jt->d_bout, jt->h_meta.data(), jt->h_boffs.data(), ((B + VG_DEF_SLACK + 15u) & ~15u) / 4, (B + 15u) & ~15u, jt->bout_cap, timed, jt->ev0, jt->ev1, jt->ev2};
+	float ms_deflate = 0, ms_frame = 0;
+	const uint64_t len0 = *len;
+	for (uint64_t b0 = 0; b0 < nb; b0 += chunk_blocks) {
+		const uint32_t k = (uint32_t)std::min(chunk_blocks, nb - b0);
+		const uint64_t t0 = b0 * B, tn = std::min<uint64_t>((uint64_t)k * B, have - t0);
+		uint64_t sum = 0;
+		const int rc = bz_deflate_chunk(dev, jt->d_text + t0, tn, B, k, jt->dyn, bgzf + *len, &sum, &ms_deflate, &ms_frame);
+		if (rc) return rc;
+		*len += sum;
+	}
+	const uint64_t done = std::min(have, nb * B);
+	jt->pend = have - done;
+	if (jt->pend && done) HIP_TRY(hipMemcpy(jt->d_text, jt->d_text + done, jt->pend, hipMemcpyDeviceToDevice));      // (less than a block behind at least one: no overlap)
+	if (timed && nb) fprintf(stderr, "[vargeno_hip] joint text stream: %lu blocks, %s codes, %.3f ms deflate kernel, %.3f ms framing, %lu bytes of BGZF\n", (unsigned long)nb, jt->dyn ? "dynamic" : "fixed", ms_deflate, ms_frame, (unsigned long)(*len - len0));
+	return VG_OK;
+}
+
+extern "C" int vg_jtext_bgzf_begin(vg_jtext *jt, uint32_t block, int codes)
+{
+	if (!jt) return fail(VG_EINVAL, "null argument");
+	if (!jt->with_bgzf) return fail(VG_EINVAL, "vg_jtext_bgzf_begin: the handle was created without the stream's buffers (with_bgzf)");
+	if (codes != VG_DEFLATE_FIXED && codes != VG_DEFLATE_DYNAMIC) return fail(VG_EINVAL, "codes is VG_DEFLATE_FIXED or VG_DEFLATE_DYNAMIC");
+	if (block > VG_BGZF_TEXT_BLOCK) return fail(VG_EINVAL, "a BGZF block holds at most 65280 bytes of text here");
+	jt->B = block ? block : VG_BGZF_TEXT_BLOCK; jt->dyn = codes == VG_DEFLATE_DYNAMIC; jt->pend = 0; jt->open = true;
+	return VG_OK;
+}
+
+extern "C" int vg_jtext_bgzf_text(vg_jtext *jt, const uint8_t *text, uint64_t nbytes, uint8_t *bgzf, uint64_t cap, uint64_t *bgzf_len)
+{
+	if (!jt || (!text && nbytes) || !bgzf || !bgzf_len) return fail(VG_EINVAL, "null argument");
+	if (!jt->open) return fail(VG_EINVAL, "no BGZF stream is open on the handle (vg_jtext_bgzf_begin)");
+	if (cap < vg_jtext_bgzf_bound(nbytes, jt->B)) return fail(VG_ETOOBIG, "the BGZF buffer is smaller than the call's bound (vg_jtext_bgzf_bound)");
+	HIP_TRY(hipSetDevice(jt->device));
+	uint64_t len = 0;
+	for (uint64_t at = 0; at < nbytes;) {                                       // as much as the text buffer takes per step
+		const uint64_t take = std::min(nbytes - at, jt->text_room - jt->pend);
+		HIP_TRY(hipMemcpy(jt->d_text + jt->pend, text + at, take, hipMemcpyHostToDevice));
+		at += take;
+		const int rc = jt_stream_flush(jt, jt->pend + take, false, bgzf, &len);
+		if (rc) { jt->open = false; return rc; }
+	}
+	*bgzf_len = len;
+	return VG_OK;
+}
+
+extern "C" int vg_jtext_bgzf_lines(vg_jtext *jt, const uint8_t *heads, uint64_t heads_len, const vg_jtext_record *records, uint64_t n_records, const uint32_t *sites, uint64_t n_site_refs,
+                                   uint8_t *bgzf, uint64_t cap, uint64_t *bgzf_len, uint64_t *text_len, uint64_t *n_lines)
+{
+	if (!jt || !bgzf || !bgzf_len || !text_len || !n_lines) return fail(VG_EINVAL, "null argument");
+	if (!jt->open) return fail(VG_EINVAL, "no BGZF stream is open on the handle (vg_jtext_bgzf_begin)");
+	uint64_t head_sum = 0;
+	int rc = jt_span_args(jt->n_sites, heads, heads_len, records, n_records, sites, n_site_refs, &head_sum);
+	if (rc || (rc = jt_span_limits(jt, heads_len, n_records, n_site_refs, head_sum))) return rc;
+	if (cap < vg_jtext_bgzf_bound(vg_jt_bound(head_sum, n_records, jt->n_samples), jt->B)) return fail(VG_ETOOBIG, "the BGZF buffer is smaller than the call's bound (vg_jtext_bgzf_bound of the span's text bound)");
+	HIP_TRY(hipSetDevice(jt->device));
+	uint64_t total = 0, lines = 0, len = 0;
+	rc = jt_render_dev(jt, heads, heads_len, records, n_records, sites, n_site_refs, head_sum, jt->pend, &total, &lines);
+	if (!rc) rc = jt_stream_flush(jt, jt->pend + total, false, bgzf, &len);
+	if (rc) { jt->open = false; return rc; }
+	*bgzf_len = len; *text_len = total; *n_lines = lines;
+	return VG_OK;
+}
+
+extern "C" int vg_jtext_bgzf_end(vg_jtext *jt, uint8_t *bgzf, uint64_t cap, uint64_t *bgzf_len)
+{
+	if (!jt || !bgzf || !bgzf_len) return fail(VG_EINVAL, "null argument");
+	if (!jt->open) return fail(VG_EINVAL, "no BGZF stream is open on the handle (vg_jtext_bgzf_begin)");
+	if (cap < vg_jtext_bgzf_bound(0, jt->B)) return fail(VG_ETOOBIG, "the BGZF buffer is smaller than the call's bound (vg_jtext_bgzf_bound)");
+	HIP_TRY(hipSetDevice(jt->device));
+	uint64_t len = 0;
+	const int rc = jt_stream_flush(jt, jt->pend, true, bgzf, &len);
+	jt->open = false;
+	if (rc) return rc;
+	memcpy(bgzf + len, vg_bgzf_eof_marker(), VG_BGZF_EOF_BYTES);
+	*bgzf_len = len + VG_BGZF_EOF_BYTES;
+	return VG_OK;
 }
