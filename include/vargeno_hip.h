@@ -521,6 +521,43 @@ int  vg_jtext_bgzf_lines(vg_jtext *jt, const uint8_t *heads, uint64_t heads_len,
                          uint8_t *bgzf, uint64_t cap, uint64_t *bgzf_len, uint64_t *text_len, uint64_t *n_lines);
 int  vg_jtext_bgzf_end(vg_jtext *jt, uint8_t *bgzf, uint64_t cap, uint64_t *bgzf_len);
 
+/* The tabix index (.tbi) of a BGZF VCF, made while the file is compressed.  No reference counterpart.  The rules -- which lines
+ * count, coordinates, bins, chunks, the linear index, the file layout -- live in csrc/vg_vcfidx.h, stated once for the host scanner
+ * and the scan kernels; small bins are not merged into their parents and INFO/END is not read (both differ from htslib, both are
+ * valid), coordinates end at 2^29.  A vg_vcfidx is a streaming handle tied to no vg_index and no device; thread-compatible.
+ *   vg_vcfidx_create       `block`: text bytes per BGZF block of the file (0: 65 280; above: VG_EINVAL)
+ *   vg_vcfidx_text_host    the next n bytes of the VCF text, cut anywhere (mid-line, mid-field), scanned on `threads` host threads
+ *   vg_vcfidx_text_device  the same state afterwards, by upload and the scan kernels on `device`.  It never falls back: VG_ENODEV or
+ *                          VG_ENOMEM leaves the handle as it was, so the same bytes can go to the host form
+ *   vg_vcfidx_bgzf         the file's BGZF bytes as they are produced: whole blocks, sizes read from BSIZE (else VG_EINVAL); the
+ *                          end-of-file marker is ignored
+ *   vg_vcfidx_finish       ends the text (a last line without '\n' is a line) and writes the raw index bytes to tbi[0, cap), *len of
+ *                          them; vg_vcfidx_bound says what fits them.  VG_EINVAL: the index was refused, or the blocks fed are not
+ *                          those of the text fed.  VG_ETOOBIG: cap is too small.  The .tbi FILE is these bytes through
+ *                          vg_bgzf_deflate_host_coded(block 0, eof 1, VG_DEFLATE_FIXED)
+ *   vg_vcfidx_error        after a data line broke a rule: the rule's words and *offset = the line's offset in the text; NULL while
+ *                          the index stands.  A refusal is sticky: later text is counted and ignored, the compressor never sees it
+ *   vg_vcfidx_stats        out[0 .. 5): data lines, chromosomes, bins, chunks, microseconds spent scanning
+ * Two fused forms, so that text is uploaded once:
+ *   vg_bgzf_deflate_device_indexed  vg_bgzf_deflate_device_coded that also scans each uploaded chunk while it is resident and feeds
+ *                          the blocks it made (not the marker) to idx.  idx == NULL: the old call, byte for byte.  A chunk whose
+ *                          scan finds no device memory is scanned by the host scanner (one line with VG_VERBOSE)
+ *   vg_jtext_bgzf_index    after vg_jtext_bgzf_begin: from then on _text, _lines and _end scan what they join -- header text on the
+ *                          host, which has it; the rendered region on the device, which alone has it -- and feed the blocks they
+ *                          hand back.  The scan's buffers are the one thing these calls allocate.  idx == NULL detaches. */
+typedef struct vg_vcfidx vg_vcfidx;
+int  vg_vcfidx_create(uint32_t block, vg_vcfidx **out);
+void vg_vcfidx_destroy(vg_vcfidx *idx);
+int  vg_vcfidx_text_host(vg_vcfidx *idx, const uint8_t *text, uint64_t n, int threads);
+int  vg_vcfidx_text_device(vg_vcfidx *idx, int device, const uint8_t *text, uint64_t n);
+int  vg_vcfidx_bgzf(vg_vcfidx *idx, const uint8_t *bgzf, uint64_t n);
+uint64_t vg_vcfidx_bound(const vg_vcfidx *idx);
+int  vg_vcfidx_finish(vg_vcfidx *idx, uint8_t *tbi, uint64_t cap, uint64_t *len);
+const char *vg_vcfidx_error(const vg_vcfidx *idx, uint64_t *offset);
+int  vg_vcfidx_stats(const vg_vcfidx *idx, uint64_t *out);
+int  vg_bgzf_deflate_device_indexed(int device, const uint8_t *text, uint64_t nbytes, uint32_t block, int eof, int codes, vg_vcfidx *idx, uint8_t *bgzf, uint64_t cap, uint64_t *bgzf_len);
+int  vg_jtext_bgzf_index(vg_jtext *jt, vg_vcfidx *idx);
+
 /* Sample planes: several samples against ONE resident index. The reference genotypes one sample per process: the counters it hands
  * to the caller (qv.cc:1573-1626) are the only per-sample state of its read loop, the dictionaries are read-only.  A PLANE is that
  * state for one sample on the device: the exact sums (8 bytes per SNP site) and the wave kernel's base-indexed counters (16 bytes

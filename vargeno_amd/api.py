@@ -469,11 +469,104 @@ def bgzf_inflate(data, device=0, out=None, text_cap=None):
 DEFLATE_CODES = {"fixed": 0, "dynamic": 1}                     # VG_DEFLATE_FIXED, VG_DEFLATE_DYNAMIC
 
 
-def bgzf_deflate(text, device=None, block=0, eof=True, threads=None, codes="fixed"):
+class VcfIndexRefused(ValueError):
+    """A data line of the VCF breaks one of the index's rules (csrc/vg_vcfidx.h): .rule names it, .offset is the line's offset in
+    the text."""
+
+    def __init__(self, rule, offset):
+        super().__init__("the VCF cannot be indexed: %s (the line at text offset %d)" % (rule, offset))
+        self.rule, self.offset = rule, offset
+
+
+class VcfIndex:
+    """The streaming handle behind a .tbi (vg_vcfidx_*): VCF text in pieces cut anywhere (text), the file's BGZF blocks as they are
+    made (bgzf), then the raw index bytes (finish); a refused index raises VcfIndexRefused there."""
+
+    def __init__(self, block=0):
+        self._h = None
+        h = C.c_void_p()
+        check(lib().vg_vcfidx_create(int(block), C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if self._h:
+            lib().vg_vcfidx_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def text(self, data, device=None, threads=1):
+        a = _u8(data)
+        self._text_at(a.ctypes.data, len(a), device, threads)
+
+    def _text_at(self, address, n, device, threads):
+        if device is None:
+            check(lib().vg_vcfidx_text_host(self._h, C.c_void_p(address), n, int(threads)))
+        else:
+            check(lib().vg_vcfidx_text_device(self._h, int(device), C.c_void_p(address), n))
+
+    def bgzf(self, data):
+        a = _u8(data)
+        check(lib().vg_vcfidx_bgzf(self._h, _ptr(a), len(a)))
+
+    def error(self):
+        """None, or (rule, offset) of the data line that refused the index."""
+        at = C.c_uint64()
+        rule = lib().vg_vcfidx_error(self._h, C.byref(at))
+        return None if rule is None else (rule.decode(), int(at.value))
+
+    def stats(self):
+        out = np.zeros(5, dtype=np.uint64)
+        check(lib().vg_vcfidx_stats(self._h, _ptr(out)))
+        return dict(zip(("data_lines", "chromosomes", "bins", "chunks", "scan_us"), (int(v) for v in out)))
+
+    def finish(self):
+        """The raw index bytes (the .tbi file is bgzf_deflate of them)."""
+        cap = int(lib().vg_vcfidx_bound(self._h))
+        out = np.zeros(max(1, cap), dtype=np.uint8)
+        n = C.c_uint64()
+        rc = lib().vg_vcfidx_finish(self._h, _ptr(out), cap, C.byref(n))
+        err = self.error()
+        if err is not None:
+            raise VcfIndexRefused(*err)
+        check(rc)
+        return out[:int(n.value)].tobytes()
+
+
+def vcf_index(text, block=0, device=None, pieces=None, threads=1):
+    """The raw tabix index bytes of `text` written as BGZF with `block` text bytes per block (csrc/vg_vcfidx.h has the rules).
+    device=None: the host scanner on `threads` threads; else the scan kernels on that device.  pieces: ascending cut points of the
+    streaming feed (the text goes in as text[0:c0], text[c0:c1], ...).  Raises VcfIndexRefused (rule, offset) when a data line breaks
+    a rule."""
+    a = _u8(text)
+    cuts = [0] + [int(c) for c in (pieces or [])] + [len(a)]
+    with VcfIndex(block) as ix:
+        for lo, hi in zip(cuts[:-1], cuts[1:]):
+            if not 0 <= lo <= hi <= len(a):
+                raise ValueError("pieces are ascending offsets into the text")
+            if hi > lo:
+                ix._text_at(a.ctypes.data + lo, hi - lo, device, threads)
+        ix.bgzf(bgzf_deflate(a, block=block))
+        return ix.finish()
+
+
+def bgzf_deflate(text, device=None, block=0, eof=True, threads=None, codes="fixed", index=False):
     """`text` written as BGZF (vg_bgzf_deflate_*_coded): on `device` by the deflate kernel, or (device=None) by the host build of the
     same compressor on `threads` threads (default: the CPUs of this process, at most 16).  block: text bytes per block, 0 = 65 280;
     eof: append the empty end-of-file block.  codes: "fixed" (fixed Huffman codes) or "dynamic" (per block the smallest of stored,
-    fixed and dynamic codes); anything else is a ValueError.  The bytes depend on the text, `block` and `codes` alone.  Returns bytes."""
+    fixed and dynamic codes); anything else is a ValueError.  The bytes depend on the text, `block` and `codes` alone.  Returns bytes.
+    index=True (a device is needed): the fused call, vg_bgzf_deflate_device_indexed -- the text is a VCF and is scanned while it is
+    resident; returns (bgzf, raw tabix index bytes) or raises VcfIndexRefused."""
     if not isinstance(codes, str) or codes not in DEFLATE_CODES:
         raise ValueError("codes is \"fixed\" or \"dynamic\", not %r" % (codes,))
     mode = DEFLATE_CODES[codes]
@@ -481,6 +574,12 @@ def bgzf_deflate(text, device=None, block=0, eof=True, threads=None, codes="fixe
     cap = int(lib().vg_bgzf_deflate_bound(len(a), int(block)))
     out = np.zeros(max(1, cap), dtype=np.uint8)
     n = C.c_uint64()
+    if index:
+        if device is None:
+            raise ValueError("bgzf_deflate(index=True) is the fused device call: name a device (vcf_index is the host's scanner)")
+        with VcfIndex(block) as ix:
+            check(lib().vg_bgzf_deflate_device_indexed(int(device), _ptr(a), len(a), int(block), int(bool(eof)), mode, ix._h, _ptr(out), cap, C.byref(n)))
+            return out[:int(n.value)].tobytes(), ix.finish()
     if device is None:
         if threads is None:
             threads = min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1))
@@ -746,6 +845,7 @@ class JointText:
             raise ValueError("codes is \"fixed\" or \"dynamic\", not %r" % (codes,))
         check(lib().vg_jtext_bgzf_begin(self._h, int(block), DEFLATE_CODES[codes]))
         self._block = int(block)
+        self._index = None
 
     def bgzf_text(self, text):
         """Host bytes joined to the stream; returns the BGZF blocks the call completed."""
@@ -767,13 +867,26 @@ class JointText:
         blocks = out[:int(n.value)].tobytes()
         return (blocks, int(tn.value), int(lines.value)) if with_counts else blocks
 
+    def bgzf_index(self):
+        """Attaches a tabix index to the open stream (vg_jtext_bgzf_index): what bgzf_text, bgzf_lines and bgzf_end join from now on
+        is scanned, and bgzf_end returns (blocks, raw index bytes)."""
+        self._index = VcfIndex(self._block)
+        check(lib().vg_jtext_bgzf_index(self._h, self._index._h))
+
     def bgzf_end(self):
-        """The last partial block and the end-of-file marker."""
+        """The last partial block and the end-of-file marker; with an index attached (bgzf_index): (those bytes, the raw index bytes),
+        or VcfIndexRefused."""
         cap = jtext_bgzf_bound(0, self._block)
         out = np.zeros(max(1, cap), dtype=np.uint8)
         n = C.c_uint64()
-        check(lib().vg_jtext_bgzf_end(self._h, _ptr(out), cap, C.byref(n)))
-        return out[:int(n.value)].tobytes()
+        ix, self._index = getattr(self, "_index", None), None
+        try:
+            check(lib().vg_jtext_bgzf_end(self._h, _ptr(out), cap, C.byref(n)))
+            blocks = out[:int(n.value)].tobytes()
+            return blocks if ix is None else (blocks, ix.finish())
+        finally:
+            if ix is not None:
+                ix.close()
 
 
 def joint_text_host(gt, gq, heads, records, sites, threads=1, n_sites=None, with_lines=False):

@@ -19,6 +19,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <atomic>
 #include <condition_variable>
 #include <deque>
 #include <map>
@@ -384,6 +385,35 @@ private:
 	FILE *f_;
 };
 
+std::atomic<unsigned> g_index_refusals{0};
+
+// <vcf_path>.tbi from a handle that has seen the whole text and every block of the file, after the VCF has closed cleanly
+void write_tbi(vg_vcfidx *idx, const std::string &vcf_path, const VcfOutput &how, const char *route)
+{
+	const std::string path = vcf_path + ".tbi";
+	std::vector<uint8_t> raw((size_t)vg_vcfidx_bound(idx));
+	uint64_t len = 0, at = 0;
+	const int rc = vg_vcfidx_finish(idx, raw.data(), raw.size(), &len);
+	if (const char *rule = vg_vcfidx_error(idx, &at)) {
+		fprintf(stderr, "vargeno: %s cannot be indexed: %s (the line at byte %lu of the text); the VCF is complete, no .tbi is written\n", vcf_path.c_str(), rule, (unsigned long)at);
+		remove(path.c_str());
+		g_index_refusals++;
+		return;
+	}
+	if (rc != VG_OK) throw Error{std::string("vg_vcfidx_finish failed: ") + vg_last_error()};
+	std::vector<uint8_t> z((size_t)vg_bgzf_deflate_bound(len, 0));
+	uint64_t zlen = 0;
+	if (vg_bgzf_deflate_host_coded(raw.data(), len, 0, 1, 1, VG_DEFLATE_FIXED, z.data(), z.size(), &zlen) != VG_OK) throw Error{std::string("vg_bgzf_deflate_host_coded failed: ") + vg_last_error()};
+	FILE *f = fopen(path.c_str(), "wb");
+	const bool wrote = f && fwrite(z.data(), 1, (size_t)zlen, f) == (size_t)zlen;
+	if ((f && fclose(f) != 0) || !wrote) throw Error{"cannot write " + path};
+	if (how.verbose) {
+		uint64_t st[5] = {0, 0, 0, 0, 0};
+		(void)vg_vcfidx_stats(idx, st);
+		fprintf(stderr, "vcf index: %s, %lu data lines, %lu chromosomes, %lu bins, %lu chunks, %lu bytes, %.3f s\n", route, (unsigned long)st[0], (unsigned long)st[1], (unsigned long)st[2], (unsigned long)st[3], (unsigned long)zlen, (double)st[4] / 1e6);
+	}
+}
+
 // Spans of span_ bytes (a multiple of the block: the blocks of the file are those of one call over the whole text) go to a worker
 // thread, which compresses and writes them in order; the producer waits while two are queued.
 class BgzfSink : public VcfSink {
@@ -394,12 +424,14 @@ public:
 		const uint64_t block = how.block ? how.block : 65280;
 		span_ = (size_t)(block * std::max<uint64_t>(1, (16ull << 20) / block));
 		device_ = how.bgzf == VcfBgzf::Device;
+		if (how.index && vg_vcfidx_create(how.block, &idx_) != VG_OK) { fclose(f_); throw Error{std::string("vg_vcfidx_create failed: ") + vg_last_error()}; }
 		worker_ = std::thread([this] { work(); });
 	}
 	~BgzfSink() override
 	{
 		stop(true);
 		if (f_) fclose(f_);
+		vg_vcfidx_destroy(idx_);
 	}
 	void write(const char *p, size_t n) override
 	{
@@ -419,6 +451,7 @@ public:
 		const bool closed = fclose(f) == 0;
 		if (!error_.empty()) throw Error{error_};
 		if (!closed) throw Error{"cannot write " + path_};
+		if (idx_) write_tbi(idx_, path_, how_, how_.bgzf != VcfBgzf::Device ? "host" : device_ ? "device" : "device, then host");
 	}
 private:
 	struct Span { std::vector<uint8_t> text; bool last; };
@@ -445,14 +478,19 @@ private:
 		uint64_t len = 0;
 		const uint8_t *text = s.text.empty() ? out.data() : s.text.data();      // (no text: any pointer that is not null)
 		if (device_) {
-			const int rc = vg_bgzf_deflate_device_coded(how_.device, text, s.text.size(), how_.block, s.last, how_.codes, out.data(), cap, &len);
+			const int rc = idx_ ? vg_bgzf_deflate_device_indexed(how_.device, text, s.text.size(), how_.block, s.last, how_.codes, idx_, out.data(), cap, &len)
+			                    : vg_bgzf_deflate_device_coded(how_.device, text, s.text.size(), how_.block, s.last, how_.codes, out.data(), cap, &len);
 			if (rc == VG_ENOMEM) {
 				if (how_.verbose) fprintf(stderr, "vcf: no device memory for the deflate kernel (%s): the rest of %s is compressed on the host\n", vg_last_error(), path_.c_str());
 				device_ = false;
 			} else if (rc != VG_OK) return std::string("vg_bgzf_deflate_device_coded failed: ") + vg_last_error();
 		}
-		if (!device_ && vg_bgzf_deflate_host_coded(text, s.text.size(), how_.block, s.last, how_.threads, how_.codes, out.data(), cap, &len) != VG_OK)
-			return std::string("vg_bgzf_deflate_host_coded failed: ") + vg_last_error();
+		if (!device_) {                                               // (the index: the host scanner and the blocks, around the compressor)
+			if (idx_ && vg_vcfidx_text_host(idx_, text, s.text.size(), how_.threads) != VG_OK) return std::string("vg_vcfidx_text_host failed: ") + vg_last_error();
+			if (vg_bgzf_deflate_host_coded(text, s.text.size(), how_.block, s.last, how_.threads, how_.codes, out.data(), cap, &len) != VG_OK)
+				return std::string("vg_bgzf_deflate_host_coded failed: ") + vg_last_error();
+			if (idx_ && vg_vcfidx_bgzf(idx_, out.data(), len) != VG_OK) return std::string("vg_vcfidx_bgzf failed: ") + vg_last_error();
+		}
 		out.resize((size_t)len);
 		return std::string();
 	}
@@ -482,6 +520,7 @@ private:
 	FILE *f_;
 	size_t span_ = 0;
 	bool device_ = false;
+	vg_vcfidx *idx_ = nullptr;                                        // VcfOutput::index: fed by the worker alone, read by close() after the join
 	std::vector<uint8_t> cur_;
 	std::thread worker_;
 	std::mutex mu_; std::condition_variable cv_;
@@ -491,6 +530,8 @@ private:
 };
 
 }  // namespace
+
+unsigned vcf_index_refusals() { return g_index_refusals; }
 
 std::unique_ptr<VcfSink> open_vcf_sink(const std::string &path, const VcfOutput &how)
 {
@@ -656,12 +697,16 @@ bool write_joint_vcf_planned(const std::vector<uint32_t> &pos, const std::vector
 	std::unique_ptr<VcfSink> out;
 	FILE *f = nullptr;
 	struct FileCloser { FILE *&f; ~FileCloser() { if (f) fclose(f); } } file_closer{f};
+	vg_vcfidx *idx = nullptr;
+	struct IndexCloser { vg_vcfidx *&h; ~IndexCloser() { vg_vcfidx_destroy(h); } } index_closer{idx};
 	std::vector<uint8_t> buf;
 	auto put = [&](uint64_t len) { if (len && fwrite(buf.data(), 1, (size_t)len, f) != (size_t)len) throw Error{"cannot write " + vcf_out}; };
 	if (stream) {
 		f = fopen(vcf_out.c_str(), "wb");
 		if (!f) throw Error{"cannot write " + vcf_out};
 		if (vg_jtext_bgzf_begin(jt, how.block, how.codes) != VG_OK) throw Error{std::string("vg_jtext_bgzf_begin failed: ") + vg_last_error()};
+		// the index follows the stream: the rendered lines are scanned where they are, on the device
+		if (how.index && (vg_vcfidx_create(how.block, &idx) != VG_OK || vg_jtext_bgzf_index(jt, idx) != VG_OK)) throw Error{std::string("the index could not be attached to the stream: ") + vg_last_error()};
 	} else out = open_vcf_sink(vcf_out, how);
 
 	std::vector<const uint8_t *> gts(n);
@@ -814,6 +859,7 @@ bool write_joint_vcf_planned(const std::vector<uint32_t> &pos, const std::vector
 		FILE *g = f;
 		f = nullptr;
 		if (fclose(g) != 0) throw Error{"cannot write " + vcf_out};
+		if (idx) write_tbi(idx, vcf_out, how, "device stream");
 	} else out->close();
 	clock_gettime(CLOCK_MONOTONIC, &c1);
 	if (how.verbose)

@@ -51,6 +51,14 @@
 //                         codes built for the block on the route that compresses it -- the same match finder, smaller files, exactly
 //                         vg_bgzf_deflate_host_coded(..., VG_DEFLATE_DYNAMIC, ...) on either route.  Any other value is refused before
 //                         a device is touched
+//   VARGENO_VCF_INDEX=tbi   geno, cohort, joint: every BGZF VCF the command writes gets its tabix index <path>.tbi, made in the pass
+//                         that compresses the file on the route that compresses it (csrc/vg_vcfidx.h has the rules; on the
+//                         VARGENO_JOINT_TEXT=device + VARGENO_VCF_BGZF=device stream the scan kernels read the rendered text where it is).
+//                         The pair table is never indexed.  A data line the index cannot hold (unsorted positions, a chromosome that
+//                         comes back, POS 0 or not a number, an end beyond 2^29, ...): the VCF is completed as ever, no .tbi is left, one
+//                         line on stderr names the rule and the line's byte offset in the text, and the command ends non-zero.
+//                         VARGENO_VERBOSE prints "vcf index: <route>, data lines, chromosomes, bins, chunks, bytes, seconds".  Unset or
+//                         empty: no index.  Any other value, or `tbi` without VARGENO_VCF_BGZF, is refused before a device is touched
 //   VARGENO_JOINT_TEXT=host|planned|device  joint (and the hidden jointvcf): who makes the data lines of the joint VCF; the file is the same
 //                         bytes on every route.  `host`, also unset or empty: the writer's loop, a line at a time on the VCF threads.
 //                         `planned`: the threads only build the plan of the lines (first eight fields + the key's sites, csrc/vg_jtext.h) and
@@ -157,6 +165,18 @@ static bool vcf_bgzf_codes(int *codes)
 	fprintf(stderr, "vargeno: VARGENO_VCF_CODES=%s is not understood: `fixed` or `dynamic` names the Huffman codes of a BGZF VCF, unset is `fixed`\n", v.c_str());
 	return false;
 }
+// VARGENO_VCF_INDEX, read once: on (`tbi`) or off (unset or empty).  false: another value, or `tbi` while the VCF is plain text --
+// said on stderr, in one line
+static bool vcf_index_switch(bool *on, vgh::VcfBgzf route)
+{
+	const std::string v = env_str("VARGENO_VCF_INDEX");
+	*on = v == "tbi";
+	if (v.empty()) return true;
+	if (!*on) { fprintf(stderr, "vargeno: VARGENO_VCF_INDEX=%s is not understood: `tbi` writes a tabix index beside every BGZF VCF, unset writes none\n", v.c_str()); return false; }
+	if (route != vgh::VcfBgzf::Off) return true;
+	fprintf(stderr, "vargeno: VARGENO_VCF_INDEX=tbi indexes BGZF output: set VARGENO_VCF_BGZF=device or VARGENO_VCF_BGZF=host as well\n");
+	return false;
+}
 // VARGENO_JOINT_TEXT (and VARGENO_JOINT_TEXT_LINES), read once: who makes the data lines of the joint file -- `host` (unset or empty),
 // `planned` or `device` (vg_host.h: JointText).  false: another value -- said on stderr, in one line
 static bool joint_text_route(vgh::JointTextRoute *r)
@@ -225,7 +245,7 @@ struct GenoOptions {
 	// device, which is device 0, or on the BGZF threads
 	// joint: who makes the data lines (VARGENO_JOINT_TEXT; main() has refused a value that is none of its three words)
 	const vgh::JointTextRoute joint_text = [] { vgh::JointTextRoute r; (void)joint_text_route(&r); return r; }();
-	const vgh::VcfOutput vcf_out = [this] { vgh::VcfOutput w; (void)vcf_bgzf_route(&w.bgzf); (void)vcf_bgzf_codes(&w.codes); w.device = 0; w.threads = bgzf_threads; w.verbose = verbose; return w; }();
+	const vgh::VcfOutput vcf_out = [this] { vgh::VcfOutput w; (void)vcf_bgzf_route(&w.bgzf); (void)vcf_bgzf_codes(&w.codes); (void)vcf_index_switch(&w.index, w.bgzf); w.device = 0; w.threads = bgzf_threads; w.verbose = verbose; return w; }();
 	explicit GenoOptions(int devices) : have(devices)
 	{
 		if (ngpu > have && !share) ngpu = have;
@@ -1489,7 +1509,10 @@ int main(int argc, const char *argv[])
 	try {
 		vgh::VcfBgzf vcf_bgzf;
 		int vcf_codes = VG_DEFLATE_FIXED;
-		if ((opt == "geno" || opt == "cohort" || opt == "joint" || opt == "jointvcf" || opt == "bgzfzip") &&(!vcf_bgzf_route(&vcf_bgzf) || !vcf_bgzf_codes(&vcf_codes))) return EXIT_FAILURE;      // (before anything else is looked at)
+		bool vcf_index = false;
+		if ((opt == "geno" || opt == "cohort" || opt == "joint" || opt == "jointvcf" || opt == "bgzfzip") &&(!vcf_bgzf_route(&vcf_bgzf) || !vcf_bgzf_codes(&vcf_codes) || !vcf_index_switch(&vcf_index, vcf_bgzf))) return EXIT_FAILURE;      // (before anything else is looked at)
+		// a VCF that could not be indexed (said on stderr where it was found) is complete, and the command fails like `vargeno ... && tabix` would
+		auto with_index = [](int rc) { return rc == EXIT_SUCCESS && vgh::vcf_index_refusals() ? EXIT_FAILURE : rc; };
 		vgh::JointTextRoute joint_text;
 		if ((opt == "joint" || opt == "jointvcf") && !joint_text_route(&joint_text)) return EXIT_FAILURE;
 		if (opt == "index") {
@@ -1501,14 +1524,14 @@ int main(int argc, const char *argv[])
 			return EXIT_SUCCESS;
 		} else if (opt == "geno") {
 			arg_check(argc, 4);
-			return run_geno(argv[2], argv[3], argv[4], argv[5]);
+			return with_index(run_geno(argv[2], argv[3], argv[4], argv[5]));
 		} else if (opt == "cohort") {
 			arg_check(argc, 3);
-			return run_cohort(argv[2], argv[3], argv[4]);
+			return with_index(run_cohort(argv[2], argv[3], argv[4]));
 		} else if (opt == "joint") {
 			arg_check(argc, 4);
 			const std::string out = argv[5];
-			return run_cohort(argv[2], argv[3], argv[4], &out);
+			return with_index(run_cohort(argv[2], argv[3], argv[4], &out));
 		} else if (opt == "bgzfcat") {
 			// hidden: a BGZF file's text on stdout, inflated by the host threads of the BgzfTextPipe (no device needed; tests/test_bgzf_cpu.py)
 			arg_check(argc, 1);
@@ -1534,6 +1557,7 @@ int main(int argc, const char *argv[])
 			vgh::VcfOutput how;
 			how.bgzf = vcf_bgzf == vgh::VcfBgzf::Device ? vgh::VcfBgzf::Device : vgh::VcfBgzf::Host;
 			how.codes = vcf_codes;
+			how.index = vcf_index;
 			how.threads = std::max(1, std::min(env_int("VARGENO_BGZF_THREADS", vgh::bgzf_threads_default(usable_cpus())), 256));
 			how.verbose = env_int("VARGENO_VERBOSE", 0) != 0;
 			const long block = argc == 5 ? atol(argv[4]) : 0;
@@ -1558,7 +1582,7 @@ int main(int argc, const char *argv[])
 			sink->close();
 			clock_gettime(CLOCK_MONOTONIC, &b);
 			if (how.verbose) fprintf(stderr, "bgzfzip: %s route, %s codes, %.3f GB of text in %.3f s (%.2f GB/s)\n", how.bgzf == vgh::VcfBgzf::Device ? "device" : "host", how.codes == VG_DEFLATE_DYNAMIC ? "dynamic" : "fixed", (double)total / 1e9, secs(a, b), (double)total / 1e9 / std::max(1e-9, secs(a, b)));
-			return EXIT_SUCCESS;
+			return with_index(EXIT_SUCCESS);
 		} else if (opt == "gzcat") {
 			// hidden: a plain gzip file's text on stdout, by the host build of the decoder alone (no device needed; tests/test_gzip_cpu.py)
 			arg_check(argc, 1);
@@ -1708,11 +1732,12 @@ int main(int argc, const char *argv[])
 			vgh::VcfOutput how;
 			how.bgzf = vcf_bgzf;
 			how.codes = vcf_codes;
+			how.index = vcf_index;
 			how.threads = std::max(1, std::min(env_int("VARGENO_BGZF_THREADS", vgh::bgzf_threads_default(usable_cpus())), 256));
 			how.verbose = env_int("VARGENO_VERBOSE", 0) != 0;
 			if (how.bgzf == vgh::VcfBgzf::Device && vg_device_count() <= 0) { fprintf(stderr, "vargeno: no HIP device found (VARGENO_VCF_BGZF=host compresses on the host)\n"); return EXIT_FAILURE; }
 			vgh::write_joint_vcf(pos, vgh::read_chrlens(argv[2]), columns, argv[3], argv[4], nullptr, how, joint_text);
-			return EXIT_SUCCESS;
+			return with_index(EXIT_SUCCESS);
 		} else if (opt == "pairstsv") {
 			// hidden: the pair table alone, by the host loop, from one calls file per sample ("gt gq" per line; all of one length):
 			// <out.tsv> <min_gq> <name>=<calls.txt> ...  (no device needed; tests/test_pairs_cpu.py)

@@ -177,6 +177,7 @@ struct VcfOutput {
 	int device = 0, threads = 1;
 	uint32_t block = 0;                            // text bytes per BGZF block; 0: 65 280
 	int codes = 0;                                 // VG_DEFLATE_FIXED or VG_DEFLATE_DYNAMIC (VARGENO_VCF_CODES)
+	bool index = false;                            // VARGENO_VCF_INDEX=tbi: <path>.tbi beside a BGZF file (never beside plain text)
 	bool verbose = false;
 };
 class VcfSink {
@@ -186,6 +187,11 @@ public:
 	virtual void close() = 0;                      // the last bytes (BGZF: and the marker) are in the file; throws Error when it could not be written
 };
 std::unique_ptr<VcfSink> open_vcf_sink(const std::string &path, const VcfOutput &how);      // throws Error when the file cannot be created
+// The index of a BGZF file (VcfOutput::index) is made by the sink's worker as it compresses -- on the device route by the fused call
+// (vg_bgzf_deflate_device_indexed), on the host route by the host scanner around the host compressor -- and written by close() after
+// the VCF has closed cleanly; a sink destroyed unclosed writes none.  A VCF with a data line the index cannot hold is completed, gets
+// no .tbi (one left by an earlier run is removed), one line on stderr, and counts here: a command that ends with a count above zero fails.
+unsigned vcf_index_refusals();
 
 // returns {ref calls, alt calls, het calls}
 struct CallSummary { uint64_t ref = 0, alt = 0, het = 0; };

@@ -19,6 +19,7 @@
 #include "vg_caller.h"
 #include "vg_pairs.h"
 #include "vg_jtext.h"
+#include "vg_vcfidx.h"
 
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -4184,7 +4185,12 @@ static int bz_deflate_chunk(const BzDeflateDev &w, const uint8_t *d_text, uint64
 	return VG_OK;
 }
 
-extern "C" int vg_bgzf_deflate_device_coded(int device, const uint8_t *text, uint64_t nbytes, uint32_t block, int eof, int codes, uint8_t *bgzf, uint64_t cap, uint64_t *bgzf_len)
+// the index's side of the fused call (the tabix section at the end of this file): the chunk text[0, tn) that is resident at d_text,
+// and the blocks made from it
+static int vi_fused_chunk(vg_vcfidx *idx, const uint8_t *d_text, const uint8_t *text, uint64_t tn);
+static int vi_fused_blocks(vg_vcfidx *idx, const uint8_t *bgzf, uint64_t n);
+
+extern "C" int vg_bgzf_deflate_device_indexed(int device, const uint8_t *text, uint64_t nbytes, uint32_t block, int eof, int codes, vg_vcfidx *idx, uint8_t *bgzf, uint64_t cap, uint64_t *bgzf_len)
 {
 	int rc = bz_deflate_args(text, nbytes, block, codes, bgzf, bgzf_len);
 	if (rc) return rc;
@@ -4216,8 +4222,10 @@ extern "C" int vg_bgzf_deflate_device_coded(int device, const uint8_t *text, uin
 			const uint32_t k = (uint32_t)std::min(chunk_blocks, nb - b0);
 			const uint64_t t0 = b0 * B, tn = std::min<uint64_t>((uint64_t)k * B, nbytes - t0);
 			HIP_TRY(hipMemcpy(d_text.p, text + t0, tn, hipMemcpyHostToDevice));
+			if (idx && (rc = vi_fused_chunk(idx, d_text.p, text + t0, tn))) return rc;
 			uint64_t sum = 0;
 			if ((rc = bz_deflate_chunk(dev, d_text.p, tn, B, k, dyn, out.work + len, &sum, &ms_deflate, &ms_frame))) return rc;
+			if (idx && (rc = vi_fused_blocks(idx, out.work + len, sum))) return rc;
 			len += sum;
 		}
 		if (timed) {
@@ -4227,6 +4235,11 @@ extern "C" int vg_bgzf_deflate_device_coded(int device, const uint8_t *text, uin
 		}
 		return out.deliver(len, eof, bgzf_len);
 	});
+}
+
+extern "C" int vg_bgzf_deflate_device_coded(int device, const uint8_t *text, uint64_t nbytes, uint32_t block, int eof, int codes, uint8_t *bgzf, uint64_t cap, uint64_t *bgzf_len)
+{
+	return vg_bgzf_deflate_device_indexed(device, text, nbytes, block, eof, codes, nullptr, bgzf, cap, bgzf_len);
 }
 
 extern "C" int vg_bgzf_deflate_device(int device, const uint8_t *text, uint64_t nbytes, uint32_t block, int eof, uint8_t *bgzf, uint64_t cap, uint64_t *bgzf_len)
@@ -5806,6 +5819,305 @@ __global__ __launch_bounds__(256) void vg_jt_write_kernel(JtStore st, const uint
 	for (uint32_t i = threadIdx.x; i < n_dw; i += 256) dst[i] = tile[i];       // 1 KiB of the tile per step
 }
 
+// ------------------------------------------------------------------------------------------------
+// The tabix index of a BGZF VCF (vg_vcfidx.h has the rules, the host scanner, the builder and the serialiser).  The kernels scan
+// WHOLE LINES that are resident on the device, text[0, n) with text[n - 1] == '\n', into the header's records:
+//   vg_vi_count_kernel    newlines per tile of VI_TILE bytes: a wave takes 64 bytes per step, ballot + popcount
+//   (vg_jt_scan_*)        the counts' exclusive scan, 64-bit: where a tile's newlines go in the newline array
+//   vg_vi_starts_kernel   nl[i] = offset of the i-th '\n': line i is text[nl[i - 1] + 1, nl[i])
+//   vg_vi_parse_kernel    a lane per line: vg_vi_parse (a long REF is a long loop of one lane: slow, not wrong)
+//   vg_vi_heads_kernel    a lane per line: does it open a record (flag), is its CHROM that of the line before it (same)
+//   (vg_jt_scan_*)        the flags' exclusive scan: the record a line belongs to
+//   vg_vi_emit_kernel     a record's first line writes its start and first facts, its last line the end: plain stores, no atomics
+// What crosses the link is the records -- a run of lines in one 16 kb window is one -- and, on the joint text route, the CHROM
+// bytes of the few records whose `same` bit is clear.
+// ------------------------------------------------------------------------------------------------
+constexpr uint32_t VI_TILE = 4096, VI_STEPS = VI_TILE / 256;             // 4 waves, 1 KiB each
+
+// the newlines of this wave's KiB (wave-uniform), and in wsum[] those of the workgroup's four waves
+__device__ __forceinline__ uint32_t vi_wave_count(const uint8_t *__restrict__ text, uint64_t n, uint64_t base, uint32_t lane, uint32_t wave, uint32_t *wsum)
+{
+	uint32_t c = 0;
+	for (uint32_t s = 0; s < VI_STEPS; s++) {
+		const uint64_t i = base + (uint64_t)s * 64 + lane;
+		c += (uint32_t)__popcll(__ballot(i < n && text[i] == '\n'));
+	}
+	if (lane == 0) wsum[wave] = c;
+	__syncthreads();
+	return c;
+}
+__global__ __launch_bounds__(256) void vg_vi_count_kernel(const uint8_t *__restrict__ text, uint64_t n, uint32_t *__restrict__ cnt)
+{
+	__shared__ uint32_t wsum[4];
+	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	(void)vi_wave_count(text, n, (uint64_t)blockIdx.x * VI_TILE + (uint64_t)wave * (VI_TILE / 4), lane, wave, wsum);
+	if (threadIdx.x == 0) cnt[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+// off: the exclusive scan of cnt; nl holds off[tiles] entries
+__global__ __launch_bounds__(256) void vg_vi_starts_kernel(const uint8_t *__restrict__ text, uint64_t n, const uint64_t *__restrict__ off, uint64_t n_lines, uint64_t *__restrict__ nl)
+{
+	__shared__ uint32_t wsum[4];
+	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const uint64_t base = (uint64_t)blockIdx.x * VI_TILE + (uint64_t)wave * (VI_TILE / 4);
+	(void)vi_wave_count(text, n, base, lane, wave, wsum);
+	uint64_t at = off[blockIdx.x];
+	for (uint32_t w = 0; w < wave; w++) at += wsum[w];
+	for (uint32_t s = 0; s < VI_STEPS; s++) {
+		const uint64_t i = base + (uint64_t)s * 64 + lane;
+		const bool is_nl = i < n && text[i] == '\n';
+		const uint64_t m = __ballot(is_nl);
+		const uint64_t slot = at + (uint64_t)__popcll(m & ((1ull << lane) - 1));
+		if (is_nl && slot < n_lines) nl[slot] = i;
+		at += (uint64_t)__popcll(m);
+	}
+}
+__global__ __launch_bounds__(256) void vg_vi_parse_kernel(const uint8_t *__restrict__ text, const uint64_t *__restrict__ nl, uint64_t n_lines, vg_vi_line *__restrict__ lines)
+{
+	const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+	if (i >= n_lines) return;
+	const uint64_t a = i ? nl[i - 1] + 1 : 0;
+	lines[i] = vg_vi_parse(text + a, nl[i] - a);
+}
+__global__ __launch_bounds__(256) void vg_vi_heads_kernel(const uint8_t *__restrict__ text, const uint64_t *__restrict__ nl, uint64_t n_lines, const vg_vi_line *__restrict__ lines,
+                                                          uint32_t *__restrict__ flag, uint32_t *__restrict__ same)
+{
+	const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+	if (i >= n_lines) return;
+	const vg_vi_line cur = lines[i];
+	uint32_t f = 0, sm = 0;
+	if (cur.kind != VG_VI_SKIP) {
+		f = 1;
+		if (i && cur.kind == VG_VI_DATA) {
+			const vg_vi_line prev = lines[i - 1];
+			if (prev.kind == VG_VI_DATA && prev.clen == cur.clen) {
+				const uint8_t *p = text + (i > 1 ? nl[i - 2] + 1 : 0), *q = text + nl[i - 1] + 1;
+				uint32_t k = 0;
+				while (k < cur.clen && p[k] == q[k]) k++;
+				sm = k == cur.clen;
+			}
+			if (vg_vi_joins(prev, cur, sm != 0)) f = 0;
+		}
+	}
+	flag[i] = f; same[i] = sm;
+}
+// roff: the exclusive scan of flag; recs holds roff[n_lines] records
+__global__ __launch_bounds__(256) void vg_vi_emit_kernel(const uint64_t *__restrict__ nl, uint64_t n_lines, const vg_vi_line *__restrict__ lines, const uint32_t *__restrict__ flag, const uint32_t *__restrict__ same,
+                                                         const uint64_t *__restrict__ roff, uint64_t n_recs, uint64_t base, vg_vi_rec *__restrict__ recs)
+{
+	const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+	if (i >= n_lines) return;
+	const vg_vi_line cur = lines[i];
+	if (cur.kind == VG_VI_SKIP) return;
+	const uint32_t f = flag[i];
+	const uint64_t r = roff[i] + f - 1;                                      // (a line that joins has a record before it: roff[i] >= 1)
+	if (r >= n_recs) return;
+	if (f) {
+		recs[r].start = base + (i ? nl[i - 1] + 1 : 0);
+		recs[r].first_line = (uint32_t)i; recs[r].beg_first = cur.beg; recs[r].end_first = cur.end; recs[r].clen = cur.clen; recs[r].kind = cur.kind; recs[r].same = same[i];
+	}
+	const bool last = i + 1 == n_lines || lines[i + 1].kind == VG_VI_SKIP || flag[i + 1] != 0;
+	if (last) { recs[r].end = base + nl[i] + 1; recs[r].last_line = (uint32_t)i; recs[r].beg_last = cur.beg; }
+}
+
+struct vg_vcfidx : VgVcfIdx {
+	// the scan's device buffers: grow-only, on the device that scanned last
+	int scratch_device = -1;
+	DevBuf<uint8_t> d_text;
+	DevBuf<uint32_t> d_cnt, d_flag, d_same;
+	DevBuf<uint64_t> d_off, d_bsum, d_nl, d_roff;
+	DevBuf<vg_vi_line> d_lines;
+	DevBuf<vg_vi_rec> d_recs;
+	hipEvent_t e0 = nullptr, e1 = nullptr;
+	std::vector<uint8_t> name;                       // a record's CHROM bytes fetched from the device
+	void release()
+	{
+		d_text.release(); d_cnt.release(); d_flag.release(); d_same.release(); d_off.release(); d_bsum.release(); d_nl.release(); d_roff.release(); d_lines.release(); d_recs.release();
+		if (e0) (void)hipEventDestroy(e0);
+		if (e1) (void)hipEventDestroy(e1);
+		e0 = e1 = nullptr;
+	}
+};
+
+// len[0, n) -> its exclusive scan off[0, n], 64-bit (the joint text's three scan kernels); bsum holds n / JT_SCAN_BLOCK + 2 entries
+static int vi_exclusive(const uint32_t *len, uint64_t n, uint64_t *bsum, uint64_t *off)
+{
+	const uint64_t nb = (n + JT_SCAN_BLOCK - 1) / JT_SCAN_BLOCK;
+	vg_jt_scan_sums_kernel<<<(unsigned)nb, 256>>>(len, n, bsum);
+	HIP_TRY(hipGetLastError());
+	vg_jt_scan_top_kernel<<<1, 256>>>(bsum, nb, off + n);
+	HIP_TRY(hipGetLastError());
+	vg_jt_scan_apply_kernel<<<(unsigned)nb, 256>>>(len, n, bsum, off);
+	HIP_TRY(hipGetLastError());
+	return VG_OK;
+}
+
+// The records of the whole lines d[0, n) (device memory of the current device; n == 0 or d[n - 1] == '\n'), text offset `base`,
+// appended to out.  Nothing of the handle but its scratch buffers changes.  Default stream, synchronous.
+static int vi_scan_resident(vg_vcfidx *ix, int device, const uint8_t *d, uint64_t n, uint64_t base, std::vector<vg_vi_rec> &out)
+{
+	if (!n) return VG_OK;
+	if (ix->scratch_device != device) { ix->release(); ix->scratch_device = device; }
+	const uint64_t tiles = (n + VI_TILE - 1) / VI_TILE;
+	if (tiles >= (1ull << 31)) return fail(VG_ETOOBIG, "the index scan takes less than 8 TiB of text per piece");
+	int rc;
+	if ((rc = ix->d_cnt.reserve(tiles, "newline counts")) || (rc = ix->d_off.reserve(tiles + 1, "newline offsets")) || (rc = ix->d_bsum.reserve(tiles / JT_SCAN_BLOCK + 2, "the scan's sums"))) return rc;
+	const bool timed = getenv("VG_VERBOSE") != nullptr;
+	if (timed && !ix->e0) { HIP_TRY(hipEventCreate(&ix->e0)); HIP_TRY(hipEventCreate(&ix->e1)); }
+	if (timed) HIP_TRY(hipEventRecord(ix->e0, nullptr));
+	vg_vi_count_kernel<<<(unsigned)tiles, 256>>>(d, n, ix->d_cnt.p);
+	HIP_TRY(hipGetLastError());
+	if ((rc = vi_exclusive(ix->d_cnt.p, tiles, ix->d_bsum.p, ix->d_off.p))) return rc;
+	uint64_t L = 0, R = 0;
+	HIP_TRY(hipMemcpy(&L, ix->d_off.p + tiles, 8, hipMemcpyDeviceToHost));
+	if (L > n) return fail(VG_EIO, "the index scan counted more lines than bytes");
+	if (L >= (1ull << 32)) return fail(VG_ETOOBIG, "the index scan takes less than 2^32 lines per piece");
+	if (L) {
+		if ((rc = ix->d_nl.reserve(L, "line ends")) || (rc = ix->d_lines.reserve(L, "parsed lines")) || (rc = ix->d_flag.reserve(L, "record flags")) || (rc = ix->d_same.reserve(L, "chromosome bits"))
+		    || (rc = ix->d_roff.reserve(L + 1, "record offsets")) || (rc = ix->d_bsum.reserve(L / JT_SCAN_BLOCK + 2, "the scan's sums"))) return rc;
+		const unsigned grid = (unsigned)((L + 255) / 256);
+		vg_vi_starts_kernel<<<(unsigned)tiles, 256>>>(d, n, ix->d_off.p, L, ix->d_nl.p);
+		HIP_TRY(hipGetLastError());
+		vg_vi_parse_kernel<<<grid, 256>>>(d, ix->d_nl.p, L, ix->d_lines.p);
+		HIP_TRY(hipGetLastError());
+		vg_vi_heads_kernel<<<grid, 256>>>(d, ix->d_nl.p, L, ix->d_lines.p, ix->d_flag.p, ix->d_same.p);
+		HIP_TRY(hipGetLastError());
+		if ((rc = vi_exclusive(ix->d_flag.p, L, ix->d_bsum.p, ix->d_roff.p))) return rc;
+		HIP_TRY(hipMemcpy(&R, ix->d_roff.p + L, 8, hipMemcpyDeviceToHost));
+		if (R > L) return fail(VG_EIO, "the index scan counted more records than lines");
+		if (R) {
+			if ((rc = ix->d_recs.reserve(R, "index records"))) return rc;
+			vg_vi_emit_kernel<<<grid, 256>>>(ix->d_nl.p, L, ix->d_lines.p, ix->d_flag.p, ix->d_same.p, ix->d_roff.p, R, base, ix->d_recs.p);
+			HIP_TRY(hipGetLastError());
+		}
+	}
+	float ms = 0;
+	if (timed) { HIP_TRY(hipEventRecord(ix->e1, nullptr)); HIP_TRY(hipEventSynchronize(ix->e1)); HIP_TRY(hipEventElapsedTime(&ms, ix->e0, ix->e1)); }
+	if (R) {
+		const size_t at = out.size();
+		out.resize(at + (size_t)R);
+		HIP_TRY(hipMemcpy(out.data() + at, ix->d_recs.p, (size_t)R * sizeof(vg_vi_rec), hipMemcpyDeviceToHost));
+	} else HIP_TRY(hipDeviceSynchronize());
+	if (timed) fprintf(stderr, "[vargeno_hip] vcf index scan: %lu bytes, %lu lines, %lu records, %.3f ms kernels (%.2f GB/s text, incl. two counts' round trips)\n", (unsigned long)n, (unsigned long)L, (unsigned long)R, ms, ms > 0 ? n / 1e6 / ms : 0.0);
+	return VG_OK;
+}
+
+extern "C" int vg_vcfidx_create(uint32_t block, vg_vcfidx **out)
+{
+	if (!out) return fail(VG_EINVAL, "null argument");
+	*out = nullptr;
+	if (block > VG_BGZF_TEXT_BLOCK) return fail(VG_EINVAL, "a BGZF block holds at most 65280 bytes of text here");
+	return guarded([&]() -> int {
+		vg_vcfidx *ix = new vg_vcfidx;
+		ix->B = block ? block : VG_BGZF_TEXT_BLOCK;
+		*out = ix;
+		return VG_OK;
+	});
+}
+extern "C" void vg_vcfidx_destroy(vg_vcfidx *idx)
+{
+	if (!idx) return;
+	idx->release();
+	(void)hipGetLastError();
+	delete idx;
+}
+extern "C" int vg_vcfidx_text_host(vg_vcfidx *idx, const uint8_t *text, uint64_t n, int threads)
+{
+	if (!idx || (!text && n)) return fail(VG_EINVAL, "null argument");
+	return guarded([&]() -> int {
+		const double t0 = now_s();
+		(void)idx->feed_host(text, n, threads);
+		idx->seconds += now_s() - t0;
+		return VG_OK;
+	});
+}
+extern "C" int vg_vcfidx_text_device(vg_vcfidx *idx, int device, const uint8_t *text, uint64_t n)
+{
+	if (!idx || (!text && n)) return fail(VG_EINVAL, "null argument");
+	int ndev = 0;
+	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(VG_ENODEV, "no HIP device available (vg_vcfidx_text_host is the host's scanner)"); }
+	return guarded([&]() -> int {
+		HIP_TRY(hipSetDevice(device));
+		const double t0 = now_s();
+		// whole lines go up in pieces of about 64 MiB that end behind a '\n'
+		const int rc = idx->feed(text, n, [&](uint64_t off, uint64_t len, std::vector<vg_vi_rec> &out) -> int {
+			const uint64_t piece = 64ull << 20, end = off + len;
+			for (uint64_t a = off; a < end;) {
+				uint64_t b = std::min(end, a + piece);
+				if (b < end) {
+					while (b > a && text[b - 1] != '\n') b--;
+					if (b == a) { const uint8_t *q = (const uint8_t *)memchr(text + a + piece, '\n', (size_t)(end - a - piece)); b = q ? (uint64_t)(q - text) + 1 : end; }
+				}
+				if (idx->scratch_device != device) { idx->release(); idx->scratch_device = device; }
+				int r = idx->d_text.reserve(b - a + 16, "text");
+				if (r) return r;
+				HIP_TRY(hipMemcpy(idx->d_text.p, text + a, b - a, hipMemcpyHostToDevice));
+				if ((r = vi_scan_resident(idx, device, idx->d_text.p, b - a, idx->fed + a, out))) return r;
+				a = b;
+			}
+			return VG_OK;
+		});
+		idx->seconds += now_s() - t0;
+		return rc;
+	});
+}
+extern "C" int vg_vcfidx_bgzf(vg_vcfidx *idx, const uint8_t *bgzf, uint64_t n)
+{
+	if (!idx || (!bgzf && n)) return fail(VG_EINVAL, "null argument");
+	return guarded([&]() -> int {
+		if (!idx->feed_bgzf(bgzf, n)) return fail(VG_EINVAL, "vg_vcfidx_bgzf: the bytes are not whole BGZF blocks");
+		return VG_OK;
+	});
+}
+static int vi_fused_chunk(vg_vcfidx *idx, const uint8_t *d_text, const uint8_t *text, uint64_t tn)
+{
+	int device = 0;
+	HIP_TRY(hipGetDevice(&device));
+	const double t0 = now_s();
+	const int rc = idx->feed(text, tn, [&](uint64_t off, uint64_t len, std::vector<vg_vi_rec> &out) -> int {
+		const int r = vi_scan_resident(idx, device, d_text + off, len, idx->fed + off, out);
+		if (r != VG_ENOMEM) return r;
+		// no device memory for the scan's buffers: the host has this chunk's text
+		if (getenv("VG_VERBOSE")) fprintf(stderr, "[vargeno_hip] vcf index scan: no device memory (%s): this chunk is scanned on the host\n", vg_last_error());
+		out.clear();
+		vg_vi_scan_lines(text + off, len, idx->fed + off, out);
+		return VG_OK;
+	});
+	idx->seconds += now_s() - t0;
+	return rc;
+}
+static int vi_fused_blocks(vg_vcfidx *idx, const uint8_t *bgzf, uint64_t n)
+{
+	if (!idx->feed_bgzf(bgzf, n)) return fail(VG_EIO, "the index was handed bytes that are not whole BGZF blocks");
+	return VG_OK;
+}
+extern "C" uint64_t vg_vcfidx_bound(const vg_vcfidx *idx) { return idx ? idx->raw_bytes() + (idx->carry.empty() ? 0 : idx->carry.size() + 1 + 8 * 4 + 2 * 24 + 32 + 8 * ((1u << 15) + 1)) : 0; }
+extern "C" int vg_vcfidx_finish(vg_vcfidx *idx, uint8_t *tbi, uint64_t cap, uint64_t *len)
+{
+	if (!idx || !len || (!tbi && cap)) return fail(VG_EINVAL, "null argument");
+	return guarded([&]() -> int {
+		std::vector<uint8_t> raw;
+		const int what = idx->serialise(raw);
+		if (what == 1) return fail(VG_EINVAL, "the VCF cannot be indexed: %s (the line at text offset %s)", vg_vi_rule(idx->err), std::to_string(idx->err_at).c_str());
+		if (what == 2) return fail(VG_EINVAL, "vg_vcfidx_finish: the BGZF blocks fed (%s) are not those of the text fed (%s)", std::to_string(idx->cstart.size()).c_str(), std::to_string(idx->blocks_of_text()).c_str());
+		if (raw.size() > cap) return fail(VG_ETOOBIG, "the index does not fit the caller's buffer (vg_vcfidx_bound)");
+		memcpy(tbi, raw.data(), raw.size());
+		*len = raw.size();
+		return VG_OK;
+	});
+}
+extern "C" const char *vg_vcfidx_error(const vg_vcfidx *idx, uint64_t *offset)
+{
+	if (!idx || !idx->err) return nullptr;
+	if (offset) *offset = idx->err_at;
+	return vg_vi_rule(idx->err);
+}
+extern "C" int vg_vcfidx_stats(const vg_vcfidx *idx, uint64_t *out)
+{
+	if (!idx || !out) return fail(VG_EINVAL, "null argument");
+	out[0] = idx->n_lines; out[1] = idx->tids.size(); out[2] = idx->n_bins; out[3] = idx->n_chunks; out[4] = (uint64_t)(idx->seconds * 1e6);
+	return VG_OK;
+}
+
 struct vg_jtext {
 	int device = 0;
 	uint64_t n_sites = 0, rec_cap = 0, head_cap = 0, site_cap = 0, text_cap = 0, text_room = 0, dev_bytes = 0;
@@ -5824,6 +6136,7 @@ struct vg_jtext {
 	bool with_bgzf = false, open = false, dyn = false;
 	uint32_t B = 0;
 	uint64_t pend = 0;                               // bytes of text in d_text that no block holds yet
+	vg_vcfidx *idx = nullptr;                        // vg_jtext_bgzf_index: the index that follows the stream (not owned)
 	uint32_t *d_slots = nullptr, *d_tok = nullptr;
 	uint2 *d_meta = nullptr;
 	uint64_t *d_boffs = nullptr;
@@ -6078,8 +6391,47 @@ extern "C" int vg_jtext_bgzf_begin(vg_jtext *jt, uint32_t block, int codes)
 	if (!jt->with_bgzf) return fail(VG_EINVAL, "vg_jtext_bgzf_begin: the handle was created without the stream's buffers (with_bgzf)");
 	if (codes != VG_DEFLATE_FIXED && codes != VG_DEFLATE_DYNAMIC) return fail(VG_EINVAL, "codes is VG_DEFLATE_FIXED or VG_DEFLATE_DYNAMIC");
 	if (block > VG_BGZF_TEXT_BLOCK) return fail(VG_EINVAL, "a BGZF block holds at most 65280 bytes of text here");
-	jt->B = block ? block : VG_BGZF_TEXT_BLOCK; jt->dyn = codes == VG_DEFLATE_DYNAMIC; jt->pend = 0; jt->open = true;
+	jt->B = block ? block : VG_BGZF_TEXT_BLOCK; jt->dyn = codes == VG_DEFLATE_DYNAMIC; jt->pend = 0; jt->open = true; jt->idx = nullptr;
 	return VG_OK;
+}
+
+extern "C" int vg_jtext_bgzf_index(vg_jtext *jt, vg_vcfidx *idx)
+{
+	if (!jt) return fail(VG_EINVAL, "null argument");
+	if (!jt->open) return fail(VG_EINVAL, "no BGZF stream is open on the handle (vg_jtext_bgzf_begin)");
+	if (idx && idx->B != jt->B) return fail(VG_EINVAL, "vg_jtext_bgzf_index: the index was created for another block size than the stream's");
+	jt->idx = idx;
+	return VG_OK;
+}
+// the index's side of the stream: the rendered lines d_text[pend, pend + total) -- whole lines, on the device alone
+static int jt_index_lines(vg_jtext *jt, uint64_t total)
+{
+	vg_vcfidx *ix = jt->idx;
+	return guarded([&]() -> int {
+		const double t0 = now_s();
+		if (!ix->carry.empty()) return fail(VG_EINVAL, "vg_jtext_bgzf_lines: the text joined before the span does not end with a line's end, the index cannot follow");
+		std::vector<vg_vi_rec> recs;
+		const uint64_t base = ix->fed;
+		const int rc = vi_scan_resident(ix, jt->device, jt->d_text + jt->pend, total, base, recs);
+		if (rc) return rc;
+		bool copied = true;
+		(void)ix->feed_records(total, recs, [&](const vg_vi_rec &r) -> const uint8_t * {
+			ix->name.resize((size_t)r.clen + 1);
+			if (r.clen && hipMemcpy(ix->name.data(), jt->d_text + jt->pend + (r.start - base), r.clen, hipMemcpyDeviceToHost) != hipSuccess) { copied = false; memset(ix->name.data(), 0, r.clen); }
+			return ix->name.data();
+		});
+		ix->seconds += now_s() - t0;
+		if (!copied) return fail(VG_ENODEV, "vg_jtext_bgzf_lines: a chromosome name could not be copied from the device");
+		return VG_OK;
+	});
+}
+// ... and the blocks a call hands back
+static int jt_index_blocks(vg_jtext *jt, const uint8_t *bgzf, uint64_t len)
+{
+	if (!jt->idx || !len) return VG_OK;
+	const int rc = vi_fused_blocks(jt->idx, bgzf, len);
+	if (rc) jt->open = false;
+	return rc;
 }
 
 extern "C" int vg_jtext_bgzf_text(vg_jtext *jt, const uint8_t *text, uint64_t nbytes, uint8_t *bgzf, uint64_t cap, uint64_t *bgzf_len)
@@ -6094,6 +6446,11 @@ extern "C" int vg_jtext_bgzf_text(vg_jtext *jt, const uint8_t *text, uint64_t nb
 		HIP_TRY(hipMemcpy(jt->d_text + jt->pend, text + at, take, hipMemcpyHostToDevice));
 		at += take;
 		const int rc = jt_stream_flush(jt, jt->pend + take, false, bgzf, &len);
+		if (rc) { jt->open = false; return rc; }
+	}
+	if (jt->idx) {                                                            // header text: the host has it
+		int rc = guarded([&]() -> int { const double t0 = now_s(); (void)jt->idx->feed_host(text, nbytes, 1); jt->idx->seconds += now_s() - t0; return VG_OK; });
+		if (!rc) rc = jt_index_blocks(jt, bgzf, len);
 		if (rc) { jt->open = false; return rc; }
 	}
 	*bgzf_len = len;
@@ -6112,7 +6469,9 @@ extern "C" int vg_jtext_bgzf_lines(vg_jtext *jt, const uint8_t *heads, uint64_t 
 	HIP_TRY(hipSetDevice(jt->device));
 	uint64_t total = 0, lines = 0, len = 0;
 	rc = jt_render_dev(jt, heads, heads_len, records, n_records, sites, n_site_refs, head_sum, jt->pend, &total, &lines);
+	if (!rc && jt->idx && total) rc = jt_index_lines(jt, total);                // (before the flush moves the text)
 	if (!rc) rc = jt_stream_flush(jt, jt->pend + total, false, bgzf, &len);
+	if (!rc) rc = jt_index_blocks(jt, bgzf, len);
 	if (rc) { jt->open = false; return rc; }
 	*bgzf_len = len; *text_len = total; *n_lines = lines;
 	return VG_OK;
@@ -6125,7 +6484,8 @@ extern "C" int vg_jtext_bgzf_end(vg_jtext *jt, uint8_t *bgzf, uint64_t cap, uint
 	if (cap < vg_jtext_bgzf_bound(0, jt->B)) return fail(VG_ETOOBIG, "the BGZF buffer is smaller than the call's bound (vg_jtext_bgzf_bound)");
 	HIP_TRY(hipSetDevice(jt->device));
 	uint64_t len = 0;
-	const int rc = jt_stream_flush(jt, jt->pend, true, bgzf, &len);
+	int rc = jt_stream_flush(jt, jt->pend, true, bgzf, &len);
+	if (!rc) rc = jt_index_blocks(jt, bgzf, len);
 	jt->open = false;
 	if (rc) return rc;
 	memcpy(bgzf + len, vg_bgzf_eof_marker(), VG_BGZF_EOF_BYTES);
