@@ -475,7 +475,8 @@ int  vg_pairs_host(const uint8_t *gt, const int32_t *gq, uint64_t n_sites, uint3
  *                          2 bytes per site and sample (gt << 14 | gq); `wide_samples` wide columns of 4 bytes per site for samples
  *                          that have a gq outside 0 .. 16382; one sample's columns of staging (5 bytes per site); and the buffers of a
  *                          span of at most max_records records, max_head_bytes bytes of heads and max_site_refs site references: those,
- *                          ceil(n_samples / 64) + 1 lengths and offsets (12 bytes) per record and the span's text bound + 80 KiB.
+ *                          ceil(n_samples / 64) + 1 lengths and offsets (12 bytes each) and 12 bytes of counts per record and the
+ *                          span's text bound + 80 KiB.
  *                          with_bgzf != 0: also the work buffers of the BGZF stream below (about 110 MB).  n_samples 1 .. 16 384 (0:
  *                          VG_EINVAL, more: VG_ETOOBIG), n_sites below 2^32.  VG_ENOMEM leaves nothing behind; VG_ENODEV without a device
  *   vg_jtext_set           one sample's final gt / gq columns (host arrays of n_sites entries, free again on return).  A sample never
@@ -494,7 +495,26 @@ int  vg_pairs_host(const uint8_t *gt, const int32_t *gq, uint64_t n_sites, uint3
  * back, in bgzf[0, *bgzf_len), the blocks it completed; text short of a block stays pending on the device.  The concatenation of
  * everything handed back is vg_bgzf_deflate_host_coded(the whole text, block, eof 1, codes), byte for byte.  cap must be at least
  * vg_jtext_bgzf_bound(bytes of text the call may add, block) -- for _lines the span's text bound, for _end 0 -- else VG_ETOOBIG and
- * nothing happens.  A call without an open stream, or begin on a handle created without with_bgzf: VG_EINVAL. */
+ * nothing happens.  A call without an open stream, or begin on a handle created without with_bgzf: VG_EINVAL.
+ * The INFO mode (opt-in; the calls above are the _info calls with VG_JT_INFO_NONE and write the bytes they always wrote).  With
+ * VG_JT_INFO_COUNTS a line's head carries the record's allele counts over the calls the line SHOWS: NS = samples whose shown call has
+ * gt != 0, AN = 2 NS, AC = hets + 2 hom-alts, AF = AC / AN rounded half up to six decimals without trailing zeros ("0", "1", "0.5",
+ * "0.333333"), as the tag "NS=<NS>;AN=<AN>;AC=<AC>;AF=<AF>" (at most 38 bytes).  A head with exactly seven tabs has eight fields: an
+ * INFO of "." is replaced by the tag, an empty INFO gets the tag, any other gets ";" and the tag; a head with another number of tabs
+ * is written unchanged.  A span's bound grows by VG_JT_INFO_MAX = 40 bytes per record.  Any other mode: VG_EINVAL (the bound: 0).
+ *   vg_jtext_create_info        vg_jtext_create with the mode, which belongs to the handle: render, bgzf_lines and the index that
+ *                               follows the stream write and scan the text of that mode (the text buffer is sized by that mode's bound)
+ *   vg_jtext_text_bound_info    the bound of a span in a mode: what render's cap and bgzf_lines' bound take on such a handle
+ *   vg_jtext_render_host_info   vg_jtext_render_host in a mode
+ *   vg_jtext_counts             the numbers without the text, on a handle of either mode: counts[n_records][3] = NS, het, hom of every
+ *                               record, zeros for a record that produces no line.  Reads no head (head_off, head_len are ignored).
+ *                               Errors as render's; allowed while a stream is open
+ *   vg_jtext_counts_host        the same from per-sample column pointers, on the host */
+#ifndef VG_JT_INFO_NONE
+#define VG_JT_INFO_NONE   0
+#define VG_JT_INFO_COUNTS 1
+#define VG_JT_INFO_MAX    40
+#endif
 #ifndef VG_JTEXT_RECORD_DEFINED
 #define VG_JTEXT_RECORD_DEFINED
 typedef struct vg_jtext_record {
@@ -520,6 +540,13 @@ int  vg_jtext_bgzf_text(vg_jtext *jt, const uint8_t *text, uint64_t nbytes, uint
 int  vg_jtext_bgzf_lines(vg_jtext *jt, const uint8_t *heads, uint64_t heads_len, const vg_jtext_record *records, uint64_t n_records, const uint32_t *sites, uint64_t n_site_refs,
                          uint8_t *bgzf, uint64_t cap, uint64_t *bgzf_len, uint64_t *text_len, uint64_t *n_lines);
 int  vg_jtext_bgzf_end(vg_jtext *jt, uint8_t *bgzf, uint64_t cap, uint64_t *bgzf_len);
+int  vg_jtext_create_info(int device, uint64_t n_sites, uint32_t n_samples, uint32_t wide_samples, uint64_t max_records, uint64_t max_head_bytes, uint64_t max_site_refs, int with_bgzf, int info, vg_jtext **out);
+uint64_t vg_jtext_text_bound_info(uint64_t head_bytes, uint64_t n_records, uint32_t n_samples, int info);
+int  vg_jtext_render_host_info(uint64_t n_sites, uint32_t n_samples, const uint8_t *const *gt, const int32_t *const *gq, const uint8_t *heads, uint64_t heads_len, const vg_jtext_record *records, uint64_t n_records,
+                               const uint32_t *sites, uint64_t n_site_refs, int info, int threads, uint8_t *text, uint64_t cap, uint64_t *len, uint64_t *n_lines);
+int  vg_jtext_counts(vg_jtext *jt, const vg_jtext_record *records, uint64_t n_records, const uint32_t *sites, uint64_t n_site_refs, uint32_t *counts);
+int  vg_jtext_counts_host(uint64_t n_sites, uint32_t n_samples, const uint8_t *const *gt, const int32_t *const *gq, const vg_jtext_record *records, uint64_t n_records, const uint32_t *sites, uint64_t n_site_refs,
+                          uint32_t *counts);
 
 /* The tabix index (.tbi) of a BGZF VCF, made while the file is compressed.  No reference counterpart.  The rules -- which lines
  * count, coordinates, bins, chunks, the linear index, the file layout -- live in csrc/vg_vcfidx.h, stated once for the host scanner

@@ -34,7 +34,8 @@ SYMBOLS = ["vg_last_error", "vg_build_id", "vg_device_count", "vg_device_memory"
            "vg_jtext_create", "vg_jtext_destroy", "vg_jtext_device_bytes", "vg_jtext_set", "vg_jtext_text_bound", "vg_jtext_bgzf_bound", "vg_jtext_render", "vg_jtext_render_host",
            "vg_jtext_bgzf_begin", "vg_jtext_bgzf_text", "vg_jtext_bgzf_lines", "vg_jtext_bgzf_end",
            "vg_vcfidx_create", "vg_vcfidx_destroy", "vg_vcfidx_text_host", "vg_vcfidx_text_device", "vg_vcfidx_bgzf", "vg_vcfidx_bound", "vg_vcfidx_finish", "vg_vcfidx_error", "vg_vcfidx_stats",
-           "vg_bgzf_deflate_device_indexed", "vg_jtext_bgzf_index"]
+           "vg_bgzf_deflate_device_indexed", "vg_jtext_bgzf_index",
+           "vg_jtext_create_info", "vg_jtext_text_bound_info", "vg_jtext_render_host_info", "vg_jtext_counts", "vg_jtext_counts_host"]
 
 GZIP_STAT_FIELDS = ["members", "chunks", "guessed", "confirmed", "repaired", "tested", "slots_refused", "resume_bit"]
 
@@ -244,6 +245,12 @@ def lib():
         L.vg_vcfidx_stats.argtypes = [vp, vp]
         L.vg_bgzf_deflate_device_indexed.argtypes = [C.c_int, vp, C.c_uint64, C.c_uint32, C.c_int, C.c_int, vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
         L.vg_jtext_bgzf_index.argtypes = [vp, vp]
+        L.vg_jtext_create_info.argtypes = [C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.POINTER(vp)]
+        L.vg_jtext_text_bound_info.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_int]
+        L.vg_jtext_text_bound_info.restype = C.c_uint64
+        L.vg_jtext_render_host_info.argtypes = [C.c_uint64, C.c_uint32, vp, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, C.c_int, C.c_int, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.vg_jtext_counts.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp]
+        L.vg_jtext_counts_host.argtypes = [C.c_uint64, C.c_uint32, vp, vp, vp, C.c_uint64, vp, C.c_uint64, vp]
         # The library is a build product that travels next to its sources (not in git): refuse a stale one.  Its build id is the
         # sha256 of the sources it was compiled from (csrc/Makefile); VARGENO_HIP_LIB (A/B variants) opts out.
         if not os.environ.get("VARGENO_HIP_LIB"):

@@ -772,9 +772,15 @@ def _jtext_span(heads, records, sites):
     return _u8(heads), jtext_records(records), np.ascontiguousarray(sites, dtype=np.uint32)
 
 
-def jtext_text_bound(head_bytes, n_records, n_samples):
-    """Bytes the text of a span never exceeds: head_bytes + n_records * (7 + 16 * n_samples)."""
-    return int(lib().vg_jtext_text_bound(int(head_bytes), int(n_records), int(n_samples)))
+JT_INFO_NONE, JT_INFO_COUNTS = 0, 1
+
+
+def jtext_text_bound(head_bytes, n_records, n_samples, info=False):
+    """Bytes the text of a span never exceeds: head_bytes + n_records * (7 + 16 * n_samples); info: and 40 bytes per record for
+    the NS / AN / AC / AF of the INFO mode."""
+    if not info:
+        return int(lib().vg_jtext_text_bound(int(head_bytes), int(n_records), int(n_samples)))
+    return int(lib().vg_jtext_text_bound_info(int(head_bytes), int(n_records), int(n_samples), JT_INFO_COUNTS))
 
 
 def jtext_bgzf_bound(text_bytes, block=0):
@@ -786,17 +792,23 @@ class JointText:
     """The calls of a cohort in columns on a device (vg_jtext_*), and the data lines of the joint VCF rendered from them: as plain
     bytes (render) or joined to a BGZF stream that leaves the device compressed (bgzf_begin / bgzf_text / bgzf_lines / bgzf_end; the
     handle must be made with bgzf=True).  max_records, max_head_bytes, max_site_refs: the largest span a call may take;
-    wide_samples: samples that may hold a gq outside 0 .. 16382 (default: all)."""
+    wide_samples: samples that may hold a gq outside 0 .. 16382 (default: all).  info=True: every line's INFO carries the record's
+    NS / AN / AC / AF (vg_jtext_create_info with VG_JT_INFO_COUNTS), in render and in the stream alike."""
 
-    def __init__(self, n_sites, n_samples, device=0, max_records=1 << 16, max_head_bytes=1 << 22, max_site_refs=1 << 18, wide_samples=None, bgzf=False):
+    def __init__(self, n_sites, n_samples, device=0, max_records=1 << 16, max_head_bytes=1 << 22, max_site_refs=1 << 18, wide_samples=None, bgzf=False, info=False):
         self._h = None
+        self.info = bool(info)
         self.n_sites, self.n_samples = int(n_sites), int(n_samples)
         if self.n_sites < 0 or self.n_samples < 0:
             raise ValueError("JointText: negative size")
         self._block = 0
         h = C.c_void_p()
         wide = self.n_samples if wide_samples is None else int(wide_samples)
-        check(lib().vg_jtext_create(int(device), self.n_sites, min(self.n_samples, 2 ** 32 - 1), min(wide, 2 ** 32 - 1), int(max_records), int(max_head_bytes), int(max_site_refs), int(bool(bgzf)), C.byref(h)))
+        sizes = (int(device), self.n_sites, min(self.n_samples, 2 ** 32 - 1), min(wide, 2 ** 32 - 1), int(max_records), int(max_head_bytes), int(max_site_refs), int(bool(bgzf)))
+        if self.info:
+            check(lib().vg_jtext_create_info(*sizes, JT_INFO_COUNTS, C.byref(h)))
+        else:
+            check(lib().vg_jtext_create(*sizes, C.byref(h)))
         self._h = h
 
     def close(self):
@@ -833,12 +845,20 @@ class JointText:
     def render(self, heads, records, sites, with_lines=False):
         """The text of a span as bytes (with_lines: and the number of records that produced a line)."""
         h, r, s = _jtext_span(heads, records, sites)
-        cap = jtext_text_bound(int(r["head_len"].sum(dtype=np.uint64)), len(r), self.n_samples)
+        cap = jtext_text_bound(int(r["head_len"].sum(dtype=np.uint64)), len(r), self.n_samples, self.info)
         out = np.zeros(max(1, cap), dtype=np.uint8)
         n, lines = C.c_uint64(), C.c_uint64()
         check(lib().vg_jtext_render(self._h, _ptr(h), len(h), _ptr(r), len(r), _ptr(s), len(s), _ptr(out), cap, C.byref(n), C.byref(lines)))
         text = out[:int(n.value)].tobytes()
         return (text, int(lines.value)) if with_lines else text
+
+    def counts(self, heads, records, sites):
+        """uint32[n_records, 3]: NS, het, hom of every record over the calls its line shows -- zeros for a record that produces no
+        line -- without the text (vg_jtext_counts; heads is not read).  Works on a handle of either mode."""
+        _, r, s = _jtext_span(heads, records, sites)
+        out = np.zeros((len(r), 3), dtype=np.uint32)
+        check(lib().vg_jtext_counts(self._h, _ptr(r), len(r), _ptr(s), len(s), _ptr(out)))
+        return out
 
     def bgzf_begin(self, block=0, codes="fixed"):
         if not isinstance(codes, str) or codes not in DEFLATE_CODES:
@@ -860,7 +880,7 @@ class JointText:
         """A span rendered and joined without leaving the device; returns the BGZF blocks the call completed (with_counts: and the
         bytes of text and the lines it added)."""
         h, r, s = _jtext_span(heads, records, sites)
-        cap = jtext_bgzf_bound(jtext_text_bound(int(r["head_len"].sum(dtype=np.uint64)), len(r), self.n_samples), self._block)
+        cap = jtext_bgzf_bound(jtext_text_bound(int(r["head_len"].sum(dtype=np.uint64)), len(r), self.n_samples, self.info), self._block)
         out = np.zeros(max(1, cap), dtype=np.uint8)
         n, tn, lines = C.c_uint64(), C.c_uint64(), C.c_uint64()
         check(lib().vg_jtext_bgzf_lines(self._h, _ptr(h), len(h), _ptr(r), len(r), _ptr(s), len(s), _ptr(out), cap, C.byref(n), C.byref(tn), C.byref(lines)))
@@ -889,25 +909,47 @@ class JointText:
                 ix.close()
 
 
-def joint_text_host(gt, gq, heads, records, sites, threads=1, n_sites=None, with_lines=False):
-    """The same text by the header's host loop (vg_jtext_render_host; no device).  gt, gq: [n_samples, n_sites] arrays, or lists of
-    per-sample columns in which None stands for a sample never set.  n_sites: default, the columns' length."""
+def _jtext_columns(gt, gq, sites, n_sites, who):
     cols_gt = [None if g is None else np.ascontiguousarray(g, dtype=np.uint8) for g in gt]
     cols_gq = [None if g is None else np.ascontiguousarray(q, dtype=np.int32) for g, q in zip(gt, gq)]
     n_samples = len(cols_gt)
-    h, r, s = _jtext_span(heads, records, sites)
+    s = np.ascontiguousarray(sites, dtype=np.uint32)
     if n_sites is None:                                        # (no sample set: any number of sites above the references will do)
         n_sites = max([len(g) for g in cols_gt if g is not None] or [int(s.max()) + 1 if len(s) else 0])
     if any(g is not None and (g.shape != (n_sites,) or q.shape != (n_sites,)) for g, q in zip(cols_gt, cols_gq)):
-        raise ValueError("joint_text_host: every sample's gt and gq hold one entry per site")
+        raise ValueError("%s: every sample's gt and gq hold one entry per site" % who)
     pg = (C.c_void_p * max(1, n_samples))(*[None if g is None else g.ctypes.data for g in cols_gt])
     pq = (C.c_void_p * max(1, n_samples))(*[None if q is None else q.ctypes.data for q in cols_gq])
-    cap = jtext_text_bound(int(r["head_len"].sum(dtype=np.uint64)), len(r), n_samples)
+    return (cols_gt, cols_gq), pg, pq, n_samples, n_sites                # (the columns: kept alive beside their pointers)
+
+
+def joint_text_host(gt, gq, heads, records, sites, threads=1, n_sites=None, with_lines=False, info=False):
+    """The same text by the header's host loop (vg_jtext_render_host; no device).  gt, gq: [n_samples, n_sites] arrays, or lists of
+    per-sample columns in which None stands for a sample never set.  n_sites: default, the columns' length.  info=True: the lines
+    of the INFO mode (vg_jtext_render_host_info with VG_JT_INFO_COUNTS)."""
+    h, r, s = _jtext_span(heads, records, sites)
+    keep, pg, pq, n_samples, n_sites = _jtext_columns(gt, gq, s, n_sites, "joint_text_host")
+    cap = jtext_text_bound(int(r["head_len"].sum(dtype=np.uint64)), len(r), n_samples, info)
     out = np.zeros(max(1, cap), dtype=np.uint8)
     n, lines = C.c_uint64(), C.c_uint64()
-    check(lib().vg_jtext_render_host(n_sites, n_samples, pg, pq, _ptr(h), len(h), _ptr(r), len(r), _ptr(s), len(s), int(threads), _ptr(out), cap, C.byref(n), C.byref(lines)))
+    if info:
+        check(lib().vg_jtext_render_host_info(n_sites, n_samples, pg, pq, _ptr(h), len(h), _ptr(r), len(r), _ptr(s), len(s), JT_INFO_COUNTS, int(threads), _ptr(out), cap, C.byref(n), C.byref(lines)))
+    else:
+        check(lib().vg_jtext_render_host(n_sites, n_samples, pg, pq, _ptr(h), len(h), _ptr(r), len(r), _ptr(s), len(s), int(threads), _ptr(out), cap, C.byref(n), C.byref(lines)))
+    del keep
     text = out[:int(n.value)].tobytes()
     return (text, int(lines.value)) if with_lines else text
+
+
+def joint_counts_host(gt, gq, records, sites, n_sites=None):
+    """uint32[n_records, 3]: NS, het, hom of every record over the calls its line shows, zeros for a record that produces no line,
+    by the header's host loop (vg_jtext_counts_host; no device).  The arguments are joint_text_host's, without the heads."""
+    _, r, s = _jtext_span(b"", records, sites)
+    keep, pg, pq, n_samples, n_sites = _jtext_columns(gt, gq, s, n_sites, "joint_counts_host")
+    out = np.zeros((len(r), 3), dtype=np.uint32)
+    check(lib().vg_jtext_counts_host(n_sites, n_samples, pg, pq, _ptr(r), len(r), _ptr(s), len(s), _ptr(out)))
+    del keep
+    return out
 
 
 def pinned_buffer(nbytes):

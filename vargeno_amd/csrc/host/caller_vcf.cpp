@@ -205,6 +205,12 @@ private:
 // ------------------------------------------------------------------------------------------------
 const char kGtDecl[] = "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n";
 const char kGqDecl[] = "##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Genotype Quality\">\n";
+// the joint file under JointTextRoute::info_counts: the keys of ../vg_jtext.h's tag, in its order
+const char *const kJointInfoKeys[4] = {"NS", "AN", "AC", "AF"};
+const char kJointInfoDecl[] = "##INFO=<ID=NS,Number=1,Type=Integer,Description=\"Number of samples with a called genotype\">\n"
+                              "##INFO=<ID=AN,Number=1,Type=Integer,Description=\"Total number of alleles in called genotypes\">\n"
+                              "##INFO=<ID=AC,Number=A,Type=Integer,Description=\"Allele count in called genotypes\">\n"
+                              "##INFO=<ID=AF,Number=A,Type=Float,Description=\"Allele frequency in called genotypes, AC / AN\">\n";
 
 struct Span {
 	const char *b, *e;
@@ -664,7 +670,8 @@ bool write_joint_vcf_planned(const std::vector<uint32_t> &pos, const std::vector
 	const size_t n = samples.size();
 	if (n == 0 || n > 16384) throw Error{std::string("VARGENO_JOINT_TEXT=") + route + " takes 1 to 16384 samples"};
 	// a span: at most `lines` records, SPAN_HEADS bytes of the list from its first head to its last, and site_cap site references
-	const uint64_t per_line = VG_JT_LINE_FIXED + (uint64_t)VG_JT_CELL_MAX * n, SPAN_HEADS = 32ull << 20;
+	const int info = tr.info_counts ? VG_JT_INFO_COUNTS : VG_JT_INFO_NONE;      // the mode of every span's text
+	const uint64_t per_line = VG_JT_LINE_FIXED + (uint64_t)VG_JT_CELL_MAX * n + (tr.info_counts ? VG_JT_INFO_MAX : 0), SPAN_HEADS = 32ull << 20;
 	const uint64_t lines = tr.lines ? std::min<uint64_t>(tr.lines, 1u << 22) : std::max<uint64_t>(1, std::min<uint64_t>(1u << 20, (128ull << 20) / (per_line + 64)));
 	const uint64_t site_cap = 4 * lines + 4096;
 	const bool stream = on_device && how.bgzf == VcfBgzf::Device;         // the text leaves the device compressed
@@ -677,7 +684,7 @@ bool write_joint_vcf_planned(const std::vector<uint32_t> &pos, const std::vector
 			for (size_t i = 0; i < js.calls.gt.size() && !w; i++) w = js.calls.gt[i] != GT_NONE && (js.calls.gq[i] < 0 || js.calls.gq[i] >= (int32_t)VG_JT_GQ_ESCAPE);
 			wide += w;
 		}
-		const int rc = vg_jtext_create(tr.device, pos.size(), (uint32_t)n, wide, lines, SPAN_HEADS, site_cap, stream, &jt);
+		const int rc = vg_jtext_create_info(tr.device, pos.size(), (uint32_t)n, wide, lines, SPAN_HEADS, site_cap, stream, info, &jt);
 		if (rc == VG_ENOMEM) {
 			if (how.verbose) fprintf(stderr, "joint text: no device memory for the text kernels (%s): %s is written by the host loop\n", vg_last_error(), vcf_out.c_str());
 			return false;
@@ -728,6 +735,7 @@ bool write_joint_vcf_planned(const std::vector<uint32_t> &pos, const std::vector
 			} else {
 				if (!declares_gt) dst += kGtDecl;
 				if (!declares_gq) dst += kGqDecl;
+				if (tr.info_counts) dst += kJointInfoDecl;
 				const Span cols = joint_first_eight(ln);
 				dst.append(cols.b, cols.e) += "\tFORMAT";
 				for (const JointSample &js : samples) { dst.push_back('\t'); dst += js.name; }
@@ -766,7 +774,7 @@ bool write_joint_vcf_planned(const std::vector<uint32_t> &pos, const std::vector
 		for (vg_jtext_record &r : span_recs) { r.head_off -= a.head_off; r.site_at -= a.site_at; head_sum += r.head_len; }
 		const uint8_t *heads = (const uint8_t *)text.data() + a.head_off;
 		const uint32_t *sites = pl.sites.data() + a.site_at;
-		const uint64_t bound = vg_jtext_text_bound(head_sum, i1 - i0, (uint32_t)n);
+		const uint64_t bound = vg_jtext_text_bound_info(head_sum, i1 - i0, (uint32_t)n, info);
 		uint64_t len = 0, got_lines = 0;
 		if (stream) {
 			uint64_t text_len = 0;
@@ -777,7 +785,7 @@ bool write_joint_vcf_planned(const std::vector<uint32_t> &pos, const std::vector
 		} else {
 			buf.resize((size_t)std::max<uint64_t>(1, bound));
 			const int rc = on_device ? vg_jtext_render(jt, heads, heads_len, span_recs.data(), span_recs.size(), sites, refs, buf.data(), buf.size(), &len, &got_lines)
-			                         : vg_jtext_render_host(pos.size(), (uint32_t)n, gts.data(), gqs.data(), heads, heads_len, span_recs.data(), span_recs.size(), sites, refs, (int)vcf_threads(), buf.data(), buf.size(), &len, &got_lines);
+			                         : vg_jtext_render_host_info(pos.size(), (uint32_t)n, gts.data(), gqs.data(), heads, heads_len, span_recs.data(), span_recs.size(), sites, refs, info, (int)vcf_threads(), buf.data(), buf.size(), &len, &got_lines);
 			if (rc != VG_OK) throw Error{std::string(on_device ? "vg_jtext_render" : "vg_jtext_render_host") + " failed: " + vg_last_error()};
 			out->write((const char *)buf.data(), (size_t)len);
 			n_text += len;
@@ -863,12 +871,32 @@ bool write_joint_vcf_planned(const std::vector<uint32_t> &pos, const std::vector
 	} else out->close();
 	clock_gettime(CLOCK_MONOTONIC, &c1);
 	if (how.verbose)
-		fprintf(stderr, "joint text: %s%s, %lu records, %lu lines written, %lu spans of at most %lu records, %lu text bytes, %.3f s\n", route, stream ? " (BGZF stream)" : "", (unsigned long)n_records, (unsigned long)n_lines,
+		fprintf(stderr, "joint text: %s%s%s, %lu records, %lu lines written, %lu spans of at most %lu records, %lu text bytes, %.3f s\n", route, stream ? " (BGZF stream)" : "", tr.info_counts ? ", info counts" : "", (unsigned long)n_records, (unsigned long)n_lines,
 		        (unsigned long)n_spans, (unsigned long)lines, (unsigned long)n_text, (double)(c1.tv_sec - c0.tv_sec) + 1e-9 * (double)(c1.tv_nsec - c0.tv_nsec));
 	return true;
 }
 
 }  // namespace
+
+std::string joint_info_declared(const std::string &vcf_in)
+{
+	FILE *f = fopen(vcf_in.c_str(), "rb");
+	if (!f) return std::string();
+	std::string found, line;
+	bool more = true;
+	while (more && found.empty()) {                                       // the lines in front of the first data line, whatever their length
+		line.clear();
+		int c;
+		while ((c = fgetc(f)) != EOF && c != '\n') line.push_back((char)c);
+		more = c != EOF;
+		if (!line.empty() && line.back() == '\r') line.pop_back();
+		if (line.empty()) continue;
+		if (line[0] != '#') break;
+		for (const char *key : kJointInfoKeys) if (found.empty() && line.compare(0, 11, "##INFO=<ID=") == 0 && line.compare(11, strlen(key) + 1, std::string(key) + ",") == 0) found = key;
+	}
+	fclose(f);
+	return found;
+}
 
 void write_joint_vcf(const std::vector<uint32_t> &pos, const std::vector<ChrLen> &chrlens, const std::vector<JointSample> &samples, const std::string &vcf_in, const std::string &vcf_out, const std::string *vcf_text, const VcfOutput &how,
                      const JointTextRoute &text_route)
@@ -905,6 +933,7 @@ void write_joint_vcf(const std::vector<uint32_t> &pos, const std::vector<ChrLen>
 			} else {
 				if (!declares_gt) dst += kGtDecl;
 				if (!declares_gq) dst += kGqDecl;
+				if (text_route.info_counts) dst += kJointInfoDecl;
 				const Span cols = first_eight(ln);
 				dst.append(cols.b, cols.e) += "\tFORMAT";
 				for (const JointSample &js : samples) { dst.push_back('\t'); dst += js.name; }
@@ -927,19 +956,25 @@ void write_joint_vcf(const std::vector<uint32_t> &pos, const std::vector<ChrLen>
 		std::string &cols = sc.smp;
 		cols.clear();
 		bool any = false;
+		vg_jt_counts_t shown{0, 0, 0};                             // the line's counts over the calls it shows (../vg_jtext.h)
 		for (size_t j = 0; j < n; j++) {
 			const SiteCalls &c = samples[j].calls;
 			const CalledSite *hit = nullptr;
 			for (const CalledSite *q = last; q > first && !hit;) { q--; if (c.gt[q->order] != GT_NONE) hit = q; }
 			if (!hit) { cols += "\t./.:."; continue; }
 			any = true;
+			shown.ns += vg_jt_is_called(c.gt[hit->order]); shown.het += vg_jt_is_het(c.gt[hit->order]); shown.hom += vg_jt_is_hom(c.gt[hit->order]);
 			char buf[24];
 			snprintf(buf, sizeof buf, "\t%s:%d", gt_text(c.gt[hit->order]), (int)c.gq[hit->order]);
 			cols += buf;
 		}
 		if (!any) return;
 		const Span head = first_eight(ln);
-		dst.append(head.b, head.e) += "\tGT:GQ";
+		if (text_route.info_counts) {                              // the head with its splice and "\tGT:GQ", by the header's function
+			const size_t at = dst.size();
+			dst.resize(at + head.size() + VG_JT_INFO_MAX + 6);
+			dst.resize(at + vg_jt_head_host((const uint8_t *)head.b, (uint32_t)head.size(), VG_JT_INFO_COUNTS, shown, (uint8_t *)&dst[at]));
+		} else dst.append(head.b, head.e) += "\tGT:GQ";
 		dst.append(cols).push_back('\n');
 	};
 	vcf_pass(text, *out, vcf_threads(), header, line);

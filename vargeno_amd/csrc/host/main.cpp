@@ -67,6 +67,14 @@
 //                         deflated there, so the rendered text never crosses the link.  No device memory for it: `host` after all, one
 //                         line under VARGENO_VERBOSE, which also prints "joint text: <route>, records, lines, spans, text bytes, seconds".
 //                         Any other value is refused before an index or a device is looked at
+//   VARGENO_JOINT_INFO=counts  joint (and the hidden jointvcf): every data line's INFO also carries NS=<samples with a call>;AN=<2 NS>;
+//                         AC=<hets + 2 hom-alts>;AF=<AC / AN, six decimals at most>, counted over the calls the line shows (on the
+//                         VARGENO_JOINT_TEXT=device route by the text kernels, a wave reduction per record; csrc/vg_jtext.h has the rule),
+//                         and the header declares the four keys.  An INFO of "." is replaced, any other gets ";" and the tag; a line
+//                         with fewer than eight fields stays as it is.  The bytes are the same on every text route, plain or BGZF.
+//                         A SNP list whose header already declares one of the four keys is refused before a device is touched or a
+//                         file created (a list that carries such keys undeclared is not noticed: its lines get them twice).  Unset or
+//                         empty: the file as ever.  Any other value is refused before an index or a device is looked at
 //   VARGENO_JOINT_TEXT_LINES=n  records per rendered span (default: what keeps a span's text near 128 MiB, at most 2^20)
 //   VARGENO_PAIRS_MIN_GQ=n  the table counts a call iff it is called and its GQ is at least n (default 0)
 //   VARGENO_VERBOSE=1     stderr: the index plan and start-up report, one "ingest, replica g:" line per route taken, the "reads:" line with
@@ -189,6 +197,16 @@ static bool joint_text_route(vgh::JointTextRoute *r)
 	fprintf(stderr, "vargeno: VARGENO_JOINT_TEXT=%s is not understood: `host`, `planned` or `device` names who makes the lines of the joint VCF, unset is `host`\n", v.c_str());
 	return false;
 }
+// VARGENO_JOINT_INFO, read once: `counts` (NS / AN / AC / AF in every line's INFO) or off (unset or empty).  false: another value --
+// said on stderr, in one line
+static bool joint_info_switch(bool *counts)
+{
+	const std::string v = env_str("VARGENO_JOINT_INFO");
+	*counts = v == "counts";
+	if (v.empty() || *counts) return true;
+	fprintf(stderr, "vargeno: VARGENO_JOINT_INFO=%s is not understood: `counts` adds NS, AN, AC and AF to the INFO of the joint VCF's lines, unset adds nothing\n", v.c_str());
+	return false;
+}
 // CPUs this process may use: the hardware threads, capped by a cgroup CPU quota (cpu.max: "<quota> <period>"; this pool's GPU boxes
 // give a container 16 CPUs' worth of time on a 256-thread host)
 static int usable_cpus()
@@ -244,7 +262,8 @@ struct GenoOptions {
 	// how the VCF is written (VARGENO_VCF_BGZF and VARGENO_VCF_CODES; main() has refused a value that is neither of its two words): on replica 0's
 	// device, which is device 0, or on the BGZF threads
 	// joint: who makes the data lines (VARGENO_JOINT_TEXT; main() has refused a value that is none of its three words)
-	const vgh::JointTextRoute joint_text = [] { vgh::JointTextRoute r; (void)joint_text_route(&r); return r; }();
+	// ... and whether their INFO carries the counts (VARGENO_JOINT_INFO; refused by main() likewise)
+	const vgh::JointTextRoute joint_text = [] { vgh::JointTextRoute r; (void)joint_text_route(&r); (void)joint_info_switch(&r.info_counts); return r; }();
 	const vgh::VcfOutput vcf_out = [this] { vgh::VcfOutput w; (void)vcf_bgzf_route(&w.bgzf); (void)vcf_bgzf_codes(&w.codes); (void)vcf_index_switch(&w.index, w.bgzf); w.device = 0; w.threads = bgzf_threads; w.verbose = verbose; return w; }();
 	explicit GenoOptions(int devices) : have(devices)
 	{
@@ -1514,7 +1533,15 @@ int main(int argc, const char *argv[])
 		// a VCF that could not be indexed (said on stderr where it was found) is complete, and the command fails like `vargeno ... && tabix` would
 		auto with_index = [](int rc) { return rc == EXIT_SUCCESS && vgh::vcf_index_refusals() ? EXIT_FAILURE : rc; };
 		vgh::JointTextRoute joint_text;
-		if ((opt == "joint" || opt == "jointvcf") && !joint_text_route(&joint_text)) return EXIT_FAILURE;
+		if ((opt == "joint" || opt == "jointvcf") && (!joint_text_route(&joint_text) || !joint_info_switch(&joint_text.info_counts))) return EXIT_FAILURE;
+		// a SNP list that declares a key VARGENO_JOINT_INFO adds: refused here, before an index, a device or the output is looked at
+		if (joint_text.info_counts && ((opt == "joint" && argc == 6) || (opt == "jointvcf" && argc >= 6))) {
+			const std::string tag = vgh::joint_info_declared(argv[opt == "joint" ? 4 : 3]);
+			if (!tag.empty()) {
+				fprintf(stderr, "vargeno: %s already declares the INFO key %s, which VARGENO_JOINT_INFO=counts would declare and write again: unset the variable or take the key out of the list\n", argv[opt == "joint" ? 4 : 3], tag.c_str());
+				return EXIT_FAILURE;
+			}
+		}
 		if (opt == "index") {
 			arg_check(argc, 3);
 			vgh::IndexOptions io;

@@ -214,12 +214,19 @@ struct JointSample { std::string name; SiteCalls calls; };
 // rendered text never crosses the link; otherwise the text goes to the sink like the host loop's.  The handle is made before the
 // output file: VG_ENOMEM hands the file to Host (one line under `verbose`), any other failure throws.  The bytes of the file are
 // the same on every route.
+// info_counts (VARGENO_JOINT_INFO=counts): every data line's INFO carries NS / AN / AC / AF over the calls the line shows -- the rule,
+// the tag's text and where it is spliced into the eighth field are ../vg_jtext.h's, compiled by all three routes -- and the header
+// declares the four keys in front of the #CHROM line.  A line with fewer than eight fields is written as without it.
 enum class JointText { Host, Planned, Device };
 struct JointTextRoute {
 	JointText route = JointText::Host;
 	uint64_t lines = 0;                            // VARGENO_JOINT_TEXT_LINES
 	int device = 0;
+	bool info_counts = false;                      // VARGENO_JOINT_INFO=counts
 };
+// The first of NS, AN, AC, AF that the SNP list's leading header lines declare as an INFO key ("##INFO=<ID=AF,"), or "" -- also when
+// the list cannot be read, which the writer says in its own words.  Such a list would get the key declared twice under info_counts.
+std::string joint_info_declared(const std::string &vcf_in);
 void write_joint_vcf(const std::vector<uint32_t> &pos, const std::vector<ChrLen> &chrlens, const std::vector<JointSample> &samples,
                      const std::string &vcf_in, const std::string &vcf_out, const std::string *vcf_text = nullptr, const VcfOutput &how = VcfOutput(),
                      const JointTextRoute &text_route = JointTextRoute());

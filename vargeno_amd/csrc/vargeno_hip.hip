@@ -5626,9 +5626,11 @@ extern "C" int vg_pairs_host(const uint8_t *gt, const int32_t *gq, uint64_t n_si
 // A span of R records is P = G + 1 PIECES per record, G = ceil(n_samples / 64): piece 0 is the head and "\tGT:GQ", piece 1 + g the
 // cells of samples [64 g, 64 g + 64) -- the last one with the line's "\n".  Three steps:
 //   vg_jt_len_kernel      one wave per (record, group), one lane per sample: the lane's call (vg_jt_pick over the record's sites),
-//                         its cell's length, the wave's sum and whether any lane has a call
-//   vg_jt_settle_kernel   one lane per record: a record no group of which has a call gets length 0 in every piece; the others their
-//                         head piece's length and the newline; counts the lines
+//                         its cell's length, the wave's sum and -- ballot + popcount -- how many lanes show a call, a het, a hom; on a
+//                         handle of the INFO mode group 0's wave also finds the head's splice kind
+//   vg_jt_settle_kernel   one lane per record: sums the groups' counts into the record's NS, het, hom (12 bytes per record, also what
+//                         vg_jtext_counts hands out); a record with NS 0 gets length 0 in every piece; the others their head piece's
+//                         length -- the head, its splice (vg_jt_head_piece_len), "\tGT:GQ" -- and the newline; counts the lines
 //   vg_jt_scan_*          exclusive scan of the R * P lengths to 64-bit byte offsets: per-block sums, one block over the sums, apply
 //   vg_jt_write_kernel    TILED BY OUTPUT BYTES: a workgroup owns JT_TILE bytes of the output buffer at a dword-aligned address, finds
 //                         the pieces that overlap them by bisection of the offsets, composes them in LDS -- a wave per piece: a head is
@@ -5654,14 +5656,15 @@ __device__ __forceinline__ uint64_t jt_call(const JtStore &st, uint32_t sample, 
 	if (gq == VG_JT_GQ_ESCAPE && slot >= 0) gq = (uint32_t)st.wide[(uint64_t)slot * st.n_sites + site];
 	return (uint64_t)(w >> 14) << 32 | gq;
 }
-__device__ __forceinline__ vg_jt_cell_t jt_lane_cell(const JtStore &st, uint32_t sample, const uint32_t *sites, uint32_t n, bool *called)
+// *shown: the gt of the call the sample shows for the record (0: none, also for a lane beyond the samples)
+__device__ __forceinline__ vg_jt_cell_t jt_lane_cell(const JtStore &st, uint32_t sample, const uint32_t *sites, uint32_t n, uint32_t *shown)
 {
 	uint64_t v = 0;
 	if (sample < st.n_samples) {
 		const int32_t slot = st.wide_slot[sample];
 		v = vg_jt_pick(sites, n, [&](uint32_t site) { return jt_call(st, sample, slot, site); });
 	}
-	*called = (v >> 32) != 0;
+	*shown = (uint32_t)(v >> 32);
 	vg_jt_cell_t c = vg_jt_cell((uint32_t)(v >> 32), (int32_t)(uint32_t)v);
 	if (sample >= st.n_samples) c.len = 0;
 	return c;
@@ -5679,7 +5682,16 @@ __global__ __launch_bounds__(256) void vg_jt_pack_kernel(const uint8_t *__restri
 	}
 }
 
-__global__ __launch_bounds__(256) void vg_jt_len_kernel(JtStore st, const vg_jtext_record *__restrict__ recs, uint64_t n_records, const uint32_t *__restrict__ sites, uint32_t G, uint32_t *__restrict__ len)
+// A group's word between the length kernel and the settle kernel: the cells' length sum (at most 64 * 16: 11 bits) and, 7 bits each,
+// how many of the 64 shown calls are called, het and hom.
+constexpr uint32_t JT_SUM_BITS = 11, JT_CNT_BITS = 7, JT_CNT_MASK = (1u << JT_CNT_BITS) - 1;
+static_assert(64 * VG_JT_CELL_MAX < (1u << JT_SUM_BITS) && JT_SUM_BITS + 3 * JT_CNT_BITS == 32, "the group word holds a length sum and three counts of up to 64");
+constexpr uint32_t JT_KIND_SHIFT = 30;                                     // a record's splice kind rides on its NS word (NS <= 16 384) on the device
+
+// info != 0: group 0's wave also reads the record's head, 64 bytes a step, for its splice kind (vg_jt_splice: the number of tabs and
+// the last two bytes) and leaves it in the head piece's slot, which the settle kernel replaces by the piece's length.
+__global__ __launch_bounds__(256) void vg_jt_len_kernel(JtStore st, const uint8_t *__restrict__ heads, const vg_jtext_record *__restrict__ recs, uint64_t n_records, const uint32_t *__restrict__ sites, uint32_t G, int info,
+                                                        uint32_t *__restrict__ len)
 {
 	const uint32_t lane = threadIdx.x & 63;
 	const uint64_t u = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);          // (the same for a wave's lanes)
@@ -5687,23 +5699,43 @@ __global__ __launch_bounds__(256) void vg_jt_len_kernel(JtStore st, const vg_jte
 	const uint64_t r = u / G;
 	const uint32_t g = (uint32_t)(u % G);
 	const vg_jtext_record rec = recs[r];
-	bool called;
-	const vg_jt_cell_t c = jt_lane_cell(st, g * 64 + lane, sites + rec.site_at, rec.n_sites, &called);
+	uint32_t shown;
+	const vg_jt_cell_t c = jt_lane_cell(st, g * 64 + lane, sites + rec.site_at, rec.n_sites, &shown);
 	uint32_t sum = c.len;
 	for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-	const bool any = __ballot(called) != 0;
-	if (lane == 0) len[r * (G + 1) + 1 + g] = sum | (any ? 1u << 31 : 0u);
+	const uint32_t called = (uint32_t)__popcll(__ballot(vg_jt_is_called(shown))), het = (uint32_t)__popcll(__ballot(vg_jt_is_het(shown))), hom = (uint32_t)__popcll(__ballot(vg_jt_is_hom(shown)));
+	if (lane == 0) len[r * (G + 1) + 1 + g] = sum | called << JT_SUM_BITS | het << (JT_SUM_BITS + JT_CNT_BITS) | hom << (JT_SUM_BITS + 2 * JT_CNT_BITS);
+	if (g != 0) return;
+	uint32_t kind = VG_JT_SPLICE_NONE;
+	if (info == VG_JT_INFO_COUNTS && rec.head_len) {
+		const uint8_t *h = heads + rec.head_off;
+		uint64_t tabs = 0;
+		for (uint32_t base = 0; base < rec.head_len; base += 64) {          // (base is the wave's: every lane takes every step)
+			const uint32_t j = base + lane;
+			tabs += (uint64_t)__popcll(__ballot(j < rec.head_len && h[j] == '\t'));
+		}
+		kind = vg_jt_splice(tabs, rec.head_len, h[rec.head_len - 1], rec.head_len > 1 ? h[rec.head_len - 2] : 0u);
+	}
+	if (lane == 0) len[r * (G + 1)] = kind;
 }
 
-__global__ __launch_bounds__(256) void vg_jt_settle_kernel(const vg_jtext_record *__restrict__ recs, uint64_t n_records, uint32_t G, uint32_t *__restrict__ len, unsigned long long *__restrict__ n_lines)
+// counts[r]: the record's NS (with its splice kind above JT_KIND_SHIFT), het and hom; zeros for a record that produces no line
+__global__ __launch_bounds__(256) void vg_jt_settle_kernel(const vg_jtext_record *__restrict__ recs, uint64_t n_records, uint32_t G, uint32_t *__restrict__ len, uint32_t *__restrict__ counts, unsigned long long *__restrict__ n_lines)
 {
 	const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
 	bool line = false;
 	if (r < n_records) {
 		uint32_t *p = len + r * (G + 1);
-		for (uint32_t g = 0; g < G; g++) line = line || (p[1 + g] >> 31);
-		p[0] = line ? recs[r].head_len + 6u : 0u;
-		for (uint32_t g = 0; g < G; g++) p[1 + g] = line ? (p[1 + g] & 0x7fffffffu) + (g + 1 == G ? 1u : 0u) : 0u;
+		uint32_t ns = 0, het = 0, hom = 0;
+		for (uint32_t g = 0; g < G; g++) {
+			const uint32_t w = p[1 + g];
+			ns += w >> JT_SUM_BITS & JT_CNT_MASK; het += w >> (JT_SUM_BITS + JT_CNT_BITS) & JT_CNT_MASK; hom += w >> (JT_SUM_BITS + 2 * JT_CNT_BITS);
+		}
+		line = ns != 0;
+		const uint32_t kind = p[0];
+		p[0] = line ? vg_jt_head_piece_len(kind, recs[r].head_len, ns, het, hom) : 0u;
+		for (uint32_t g = 0; g < G; g++) p[1 + g] = line ? (p[1 + g] & ((1u << JT_SUM_BITS) - 1)) + (g + 1 == G ? 1u : 0u) : 0u;
+		counts[3 * r] = line ? ns | kind << JT_KIND_SHIFT : 0u; counts[3 * r + 1] = line ? het : 0u; counts[3 * r + 2] = line ? hom : 0u;
 	}
 	const unsigned long long votes = __ballot(line);
 	if ((threadIdx.x & 63) == 0 && votes) atomicAdd(n_lines, (unsigned long long)__popcll(votes));
@@ -5768,7 +5800,7 @@ __global__ __launch_bounds__(256) void vg_jt_scan_apply_kernel(const uint32_t *_
 // out: the dword-aligned output buffer; the span's text goes to out[start, start + off[n_items]).  grid: the tiles from the dword
 // that holds byte `start` on (the host sizes it by the span's bound; a tile beyond the text returns)
 __global__ __launch_bounds__(256) void vg_jt_write_kernel(JtStore st, const uint8_t *__restrict__ heads, const vg_jtext_record *__restrict__ recs, const uint32_t *__restrict__ sites, uint32_t G,
-                                                          const uint32_t *__restrict__ len, const uint64_t *__restrict__ off, uint64_t n_items, uint8_t *out, uint64_t start)
+                                                          const uint32_t *__restrict__ len, const uint64_t *__restrict__ off, const uint32_t *__restrict__ counts, uint64_t n_items, uint8_t *out, uint64_t start)
 {
 	__shared__ uint32_t tile[JT_TILE / 4];
 	uint8_t *const tb = (uint8_t *)tile;
@@ -5792,17 +5824,26 @@ __global__ __launch_bounds__(256) void vg_jt_write_kernel(JtStore st, const uint
 		const uint32_t k = (uint32_t)(p % P);
 		const vg_jtext_record rec = recs[r];
 		if (k == 0) {
-			// the head and "\tGT:GQ": bytes [j0, j1) of the piece are this tile's
+			// the head piece: `keep` bytes of the head, the splice (";" if the INFO goes on, the tag), "\tGT:GQ" -- without a splice
+			// keep = head_len and tag_at = fmt_at.  Bytes [j0, j1) of the piece are this tile's
 			const uint64_t j0 = lo > o ? lo - o : 0, j1 = hi - o < n ? hi - o : n;
 			const uint8_t *h = heads + rec.head_off;
+			const uint32_t ns_word = counts[3 * r], kind = ns_word >> JT_KIND_SHIFT;
+			const uint32_t keep = vg_jt_splice_keep(kind, rec.head_len), tag_at = keep + vg_jt_splice_sep(kind), fmt_at = n - 6;
 			for (uint64_t j = j0 + lane; j < j1; j += 64) {
-				const uint32_t v = j < rec.head_len ? h[j] : (uint32_t)(0x51473a544709ull >> (8 * (j - rec.head_len))) & 0xffu;
+				if (j >= tag_at && j < fmt_at) continue;                        // the tag's bytes: below
+				const uint32_t v = j < keep ? h[j] : j < tag_at ? (uint32_t)';' : (uint32_t)(0x51473a544709ull >> (8 * (j - fmt_at))) & 0xffu;
 				tb[(int64_t)(o + j) - shift] = (uint8_t)v;
 			}
+			if (lane == 0 && tag_at < fmt_at && j0 < fmt_at && j1 > tag_at)   // one lane prints the tag, a byte at a time, where the tile holds it
+				(void)vg_jt_tag(ns_word & ((1u << JT_KIND_SHIFT) - 1), counts[3 * r + 1], counts[3 * r + 2], [&](uint32_t i, uint32_t byte) {
+					const uint64_t j = (uint64_t)tag_at + i;
+					if (j >= j0 && j < j1) tb[(int64_t)(o + j) - shift] = (uint8_t)byte;
+				});
 		} else {
 			const uint32_t g = k - 1;
-			bool called;
-			const vg_jt_cell_t c = jt_lane_cell(st, g * 64 + lane, sites + rec.site_at, rec.n_sites, &called);
+			uint32_t shown;
+			const vg_jt_cell_t c = jt_lane_cell(st, g * 64 + lane, sites + rec.site_at, rec.n_sites, &shown);
 			uint32_t incl = c.len;
 			for (int s = 1; s < 64; s <<= 1) { const uint32_t y = __shfl_up(incl, s); if ((int)lane >= s) incl += y; }
 			const uint64_t at = o + incl - c.len;                               // the cell's text offset
@@ -6122,11 +6163,12 @@ struct vg_jtext {
 	int device = 0;
 	uint64_t n_sites = 0, rec_cap = 0, head_cap = 0, site_cap = 0, text_cap = 0, text_room = 0, dev_bytes = 0;
 	uint32_t n_samples = 0, G = 0, wide_cap = 0;
+	int info = VG_JT_INFO_NONE;                      // the mode of the handle's text (vg_jtext_create_info)
 	uint16_t *d_narrow = nullptr;
 	int32_t *d_wide = nullptr, *d_wide_slot = nullptr, *d_gq = nullptr;
 	uint8_t *d_gt = nullptr, *d_heads = nullptr, *d_text = nullptr;
 	vg_jtext_record *d_recs = nullptr;
-	uint32_t *d_sites = nullptr, *d_len = nullptr;
+	uint32_t *d_sites = nullptr, *d_len = nullptr, *d_counts = nullptr;
 	uint64_t *d_off = nullptr, *d_bsum = nullptr;
 	unsigned long long *d_lines = nullptr;
 	std::vector<int32_t> wide_slot;                  // host mirror of d_wide_slot
@@ -6152,13 +6194,15 @@ static void jtext_free(vg_jtext *jt)
 	(void)hipSetDevice(jt->device);
 	for (hipEvent_t e : {jt->ev0, jt->ev1, jt->ev2}) if (e) (void)hipEventDestroy(e);
 	for (void *p : {(void *)jt->d_narrow, (void *)jt->d_wide, (void *)jt->d_wide_slot, (void *)jt->d_gq, (void *)jt->d_gt, (void *)jt->d_heads, (void *)jt->d_text, (void *)jt->d_recs, (void *)jt->d_sites,
-	                (void *)jt->d_len, (void *)jt->d_off, (void *)jt->d_bsum, (void *)jt->d_lines, (void *)jt->d_slots, (void *)jt->d_tok, (void *)jt->d_meta, (void *)jt->d_boffs, (void *)jt->d_bout})
+	                (void *)jt->d_len, (void *)jt->d_counts, (void *)jt->d_off, (void *)jt->d_bsum, (void *)jt->d_lines, (void *)jt->d_slots, (void *)jt->d_tok, (void *)jt->d_meta, (void *)jt->d_boffs, (void *)jt->d_bout})
 		if (p) (void)hipFree(p);
 	(void)hipGetLastError();
 	delete jt;
 }
 
+static bool jt_info_mode(int info) { return info == VG_JT_INFO_NONE || info == VG_JT_INFO_COUNTS; }
 extern "C" uint64_t vg_jtext_text_bound(uint64_t head_bytes, uint64_t n_records, uint32_t n_samples) { return vg_jt_bound(head_bytes, n_records, n_samples); }
+extern "C" uint64_t vg_jtext_text_bound_info(uint64_t head_bytes, uint64_t n_records, uint32_t n_samples, int info) { return jt_info_mode(info) ? vg_jt_bound_info(head_bytes, n_records, n_samples, info) : 0; }
 extern "C" uint64_t vg_jtext_bgzf_bound(uint64_t text_bytes, uint32_t block)
 {
 	if (block > VG_BGZF_TEXT_BLOCK) return 0;
@@ -6166,10 +6210,11 @@ extern "C" uint64_t vg_jtext_bgzf_bound(uint64_t text_bytes, uint32_t block)
 	return vg_bgzf_bound(text_bytes + B - 1, B);                              // (the pending text of earlier calls: less than a block)
 }
 
-extern "C" int vg_jtext_create(int device, uint64_t n_sites, uint32_t n_samples, uint32_t wide_samples, uint64_t max_records, uint64_t max_head_bytes, uint64_t max_site_refs, int with_bgzf, vg_jtext **out)
+extern "C" int vg_jtext_create_info(int device, uint64_t n_sites, uint32_t n_samples, uint32_t wide_samples, uint64_t max_records, uint64_t max_head_bytes, uint64_t max_site_refs, int with_bgzf, int info, vg_jtext **out)
 {
 	if (!out) return fail(VG_EINVAL, "null argument");
 	*out = nullptr;
+	if (!jt_info_mode(info)) return fail(VG_EINVAL, "vg_jtext_create_info: info is VG_JT_INFO_NONE or VG_JT_INFO_COUNTS");
 	if (n_samples == 0) return fail(VG_EINVAL, "vg_jtext_create: no samples");
 	if (n_sites >= (1ull << 32)) return fail(VG_EINVAL, "vg_jtext_create: 2^32 sites or more");
 	if (n_samples > VG_JTEXT_MAX_SAMPLES) return fail(VG_ETOOBIG, "vg_jtext_create: more than %s samples", std::to_string(VG_JTEXT_MAX_SAMPLES).c_str());
@@ -6180,8 +6225,8 @@ extern "C" int vg_jtext_create(int device, uint64_t n_sites, uint32_t n_samples,
 		HIP_TRY(hipSetDevice(device));
 		vg_jtext *jt = new vg_jtext;
 		jt->device = device; jt->n_sites = n_sites; jt->n_samples = n_samples; jt->G = (n_samples + 63) / 64; jt->wide_cap = std::min(wide_samples, n_samples);
-		jt->rec_cap = max_records; jt->head_cap = max_head_bytes; jt->site_cap = max_site_refs; jt->with_bgzf = with_bgzf != 0;
-		jt->text_cap = vg_jt_bound(max_head_bytes, max_records, n_samples);
+		jt->rec_cap = max_records; jt->head_cap = max_head_bytes; jt->site_cap = max_site_refs; jt->with_bgzf = with_bgzf != 0; jt->info = info;
+		jt->text_cap = vg_jt_bound_info(max_head_bytes, max_records, n_samples, info);
 		jt->text_room = jt->text_cap + VG_BGZF_TEXT_BLOCK;
 		const uint64_t items = max_records * (jt->G + 1);
 		jt->bout_cap = JT_CHUNK_TEXT + JT_CHUNK_BLOCKS * 32 + 64;
@@ -6189,7 +6234,7 @@ extern "C" int vg_jtext_create(int device, uint64_t n_sites, uint32_t n_samples,
 			{(void **)&jt->d_narrow, (uint64_t)n_samples * n_sites * 2, "the samples' columns", false}, {(void **)&jt->d_wide, (uint64_t)jt->wide_cap * n_sites * 4, "the wide columns", false},
 			{(void **)&jt->d_wide_slot, (uint64_t)n_samples * 4, "the wide column table", false}, {(void **)&jt->d_gt, n_sites, "a gt column", false}, {(void **)&jt->d_gq, n_sites * 4, "a gq column", false},
 			{(void **)&jt->d_heads, max_head_bytes, "the heads", false}, {(void **)&jt->d_recs, max_records * sizeof(vg_jtext_record), "the records", false}, {(void **)&jt->d_sites, max_site_refs * 4, "the site references", false},
-			{(void **)&jt->d_len, items * 4, "the piece lengths", false}, {(void **)&jt->d_off, (items + 1) * 8, "the piece offsets", false}, {(void **)&jt->d_bsum, (items / JT_SCAN_BLOCK + 2) * 8, "the scan's sums", false},
+			{(void **)&jt->d_len, items * 4, "the piece lengths", false}, {(void **)&jt->d_counts, max_records * 12, "the records' counts", false}, {(void **)&jt->d_off, (items + 1) * 8, "the piece offsets", false}, {(void **)&jt->d_bsum, (items / JT_SCAN_BLOCK + 2) * 8, "the scan's sums", false},
 			{(void **)&jt->d_lines, 8, "the line count", false}, {(void **)&jt->d_text, jt->text_room + JT_TILE + 64, "the text", false},
 			{(void **)&jt->d_slots, JT_CHUNK_TEXT + JT_CHUNK_BLOCKS * (VG_DEF_SLACK + 32), "deflate slots", true}, {(void **)&jt->d_tok, (JT_CHUNK_TEXT + JT_CHUNK_BLOCKS * 16) * 4, "deflate tokens", true},
 			{(void **)&jt->d_meta, JT_CHUNK_BLOCKS * sizeof(uint2), "block results", true}, {(void **)&jt->d_boffs, JT_CHUNK_BLOCKS * 8, "block offsets", true}, {(void **)&jt->d_bout, jt->bout_cap, "BGZF bytes", true}};
@@ -6218,6 +6263,11 @@ extern "C" int vg_jtext_create(int device, uint64_t n_sites, uint32_t n_samples,
 		*out = jt;
 		return VG_OK;
 	});
+}
+
+extern "C" int vg_jtext_create(int device, uint64_t n_sites, uint32_t n_samples, uint32_t wide_samples, uint64_t max_records, uint64_t max_head_bytes, uint64_t max_site_refs, int with_bgzf, vg_jtext **out)
+{
+	return vg_jtext_create_info(device, n_sites, n_samples, wide_samples, max_records, max_head_bytes, max_site_refs, with_bgzf, VG_JT_INFO_NONE, out);
 }
 
 extern "C" void vg_jtext_destroy(vg_jtext *jt) { jtext_free(jt); }
@@ -6255,18 +6305,35 @@ extern "C" int vg_jtext_set(vg_jtext *jt, uint32_t sample, const uint8_t *gt, co
 
 // what every call that takes a span checks before anything is written: null pointers and references outside their arrays are
 // VG_EINVAL, a span beyond the handle's limits VG_ETOOBIG.  *head_sum: the sum of the records' head_len
-static int jt_span_args(const uint64_t n_sites, const uint8_t *heads, uint64_t heads_len, const vg_jtext_record *recs, uint64_t n_records, const uint32_t *sites, uint64_t n_site_refs, uint64_t *head_sum)
+// (with_heads false: a call that reads no head -- the counts alone -- does not look at head_off and head_len)
+static int jt_span_args(const uint64_t n_sites, const uint8_t *heads, uint64_t heads_len, const vg_jtext_record *recs, uint64_t n_records, const uint32_t *sites, uint64_t n_site_refs, uint64_t *head_sum, bool with_heads = true)
 {
 	if ((!heads && heads_len) || (!recs && n_records) || (!sites && n_site_refs)) return fail(VG_EINVAL, "null argument");
 	uint64_t sum = 0;
 	for (uint64_t i = 0; i < n_records; i++) {
 		const vg_jtext_record &r = recs[i];
-		if (r.head_off > heads_len || r.head_len > heads_len - r.head_off) return fail(VG_EINVAL, "record %s: its head lies outside the heads", std::to_string(i).c_str());
+		if (with_heads && (r.head_off > heads_len || r.head_len > heads_len - r.head_off)) return fail(VG_EINVAL, "record %s: its head lies outside the heads", std::to_string(i).c_str());
 		if (r.site_at > n_site_refs || r.n_sites > n_site_refs - r.site_at) return fail(VG_EINVAL, "record %s: its site run lies outside the site references", std::to_string(i).c_str());
 		sum += r.head_len;
 	}
 	for (uint64_t i = 0; i < n_site_refs; i++) if (sites[i] >= n_sites) return fail(VG_EINVAL, "site reference %s names a site the handle does not have", std::to_string(i).c_str());
 	*head_sum = sum;
+	return VG_OK;
+}
+
+// The first step of a span whose heads are on the device (info 0: no head is read): records and site references go up, the length
+// kernel and the settle kernel leave the pieces' lengths in d_len, the records' counts in d_counts and the lines' number in d_lines
+// (started: an event recorded in front of the kernels)
+static int jt_lengths_dev(vg_jtext *jt, const JtStore &st, const vg_jtext_record *recs, uint64_t n_records, const uint32_t *sites, uint64_t n_site_refs, int info, hipEvent_t started = nullptr)
+{
+	HIP_TRY(hipMemcpy(jt->d_recs, recs, n_records * sizeof(vg_jtext_record), hipMemcpyHostToDevice));
+	if (n_site_refs) HIP_TRY(hipMemcpy(jt->d_sites, sites, n_site_refs * 4, hipMemcpyHostToDevice));
+	HIP_TRY(hipMemset(jt->d_lines, 0, 8));
+	if (started) HIP_TRY(hipEventRecord(started, nullptr));
+	vg_jt_len_kernel<<<(unsigned)((n_records * jt->G + 3) / 4), 256>>>(st, jt->d_heads, jt->d_recs, n_records, jt->d_sites, jt->G, info, jt->d_len);
+	HIP_TRY(hipGetLastError());
+	vg_jt_settle_kernel<<<(unsigned)((n_records + 255) / 256), 256>>>(jt->d_recs, n_records, jt->G, jt->d_len, jt->d_counts, jt->d_lines);
+	HIP_TRY(hipGetLastError());
 	return VG_OK;
 }
 
@@ -6277,18 +6344,12 @@ static int jt_render_dev(vg_jtext *jt, const uint8_t *heads, uint64_t heads_len,
 	*total = 0; *n_lines = 0;
 	if (!n_records) return VG_OK;
 	if (heads_len) HIP_TRY(hipMemcpy(jt->d_heads, heads, heads_len, hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(jt->d_recs, recs, n_records * sizeof(vg_jtext_record), hipMemcpyHostToDevice));
-	if (n_site_refs) HIP_TRY(hipMemcpy(jt->d_sites, sites, n_site_refs * 4, hipMemcpyHostToDevice));
-	HIP_TRY(hipMemset(jt->d_lines, 0, 8));
 	const JtStore st{jt->d_narrow, jt->d_wide, jt->d_wide_slot, jt->n_sites, jt->n_samples};
 	const uint32_t G = jt->G;
 	const uint64_t items = n_records * (G + 1), nb = (items + JT_SCAN_BLOCK - 1) / JT_SCAN_BLOCK;
 	const bool timed = getenv("VG_VERBOSE") != nullptr;
-	if (timed) HIP_TRY(hipEventRecord(jt->ev0, nullptr));
-	vg_jt_len_kernel<<<(unsigned)((n_records * G + 3) / 4), 256>>>(st, jt->d_recs, n_records, jt->d_sites, G, jt->d_len);
-	HIP_TRY(hipGetLastError());
-	vg_jt_settle_kernel<<<(unsigned)((n_records + 255) / 256), 256>>>(jt->d_recs, n_records, G, jt->d_len, jt->d_lines);
-	HIP_TRY(hipGetLastError());
+	const int rc = jt_lengths_dev(jt, st, recs, n_records, sites, n_site_refs, jt->info, timed ? jt->ev0 : nullptr);
+	if (rc) return rc;
 	vg_jt_scan_sums_kernel<<<(unsigned)nb, 256>>>(jt->d_len, items, jt->d_bsum);
 	HIP_TRY(hipGetLastError());
 	vg_jt_scan_top_kernel<<<1, 256>>>(jt->d_bsum, nb, jt->d_off + items);
@@ -6297,9 +6358,9 @@ static int jt_render_dev(vg_jtext *jt, const uint8_t *heads, uint64_t heads_len,
 	HIP_TRY(hipGetLastError());
 	if (timed) HIP_TRY(hipEventRecord(jt->ev1, nullptr));
 	// the tiles of the bound: one that lies beyond the text returns at once
-	const uint64_t bound = vg_jt_bound(head_sum, n_records, jt->n_samples);
+	const uint64_t bound = vg_jt_bound_info(head_sum, n_records, jt->n_samples, jt->info);
 	const uint64_t tiles = ((start & 3) + bound + JT_TILE - 1) / JT_TILE;
-	vg_jt_write_kernel<<<(unsigned)tiles, 256>>>(st, jt->d_heads, jt->d_recs, jt->d_sites, G, jt->d_len, jt->d_off, items, jt->d_text, start);
+	vg_jt_write_kernel<<<(unsigned)tiles, 256>>>(st, jt->d_heads, jt->d_recs, jt->d_sites, G, jt->d_len, jt->d_off, jt->d_counts, items, jt->d_text, start);
 	HIP_TRY(hipGetLastError());
 	if (timed) HIP_TRY(hipEventRecord(jt->ev2, nullptr));
 	unsigned long long lines = 0;
@@ -6319,7 +6380,7 @@ static int jt_render_dev(vg_jtext *jt, const uint8_t *heads, uint64_t heads_len,
 // a span against the handle's limits; the bound of its text must fit the text buffer behind `start` bytes
 static int jt_span_limits(const vg_jtext *jt, uint64_t heads_len, uint64_t n_records, uint64_t n_site_refs, uint64_t head_sum)
 {
-	const uint64_t bound = vg_jt_bound(head_sum, n_records, jt->n_samples);
+	const uint64_t bound = vg_jt_bound_info(head_sum, n_records, jt->n_samples, jt->info);
 	if (n_records > jt->rec_cap || heads_len > jt->head_cap || n_site_refs > jt->site_cap || bound > jt->text_cap || n_records * (jt->G + 1) >= (1ull << 32) || bound / JT_TILE >= (1ull << 31))      // (the last two: a grid's size)
 		return fail(VG_ETOOBIG, "the span is beyond the limits the handle was created with (records, head bytes, site references)");
 	return VG_OK;
@@ -6333,7 +6394,7 @@ extern "C" int vg_jtext_render(vg_jtext *jt, const uint8_t *heads, uint64_t head
 	uint64_t head_sum = 0;
 	int rc = jt_span_args(jt->n_sites, heads, heads_len, records, n_records, sites, n_site_refs, &head_sum);
 	if (rc || (rc = jt_span_limits(jt, heads_len, n_records, n_site_refs, head_sum))) return rc;
-	if (cap < vg_jt_bound(head_sum, n_records, jt->n_samples)) return fail(VG_ETOOBIG, "the text buffer is smaller than the span's bound (vg_jtext_text_bound)");
+	if (cap < vg_jt_bound_info(head_sum, n_records, jt->n_samples, jt->info)) return fail(VG_ETOOBIG, "the text buffer is smaller than the span's bound (vg_jtext_text_bound_info with the handle's mode)");
 	HIP_TRY(hipSetDevice(jt->device));
 	uint64_t total = 0, lines = 0;
 	if ((rc = jt_render_dev(jt, heads, heads_len, records, n_records, sites, n_site_refs, head_sum, 0, &total, &lines))) return rc;
@@ -6342,10 +6403,11 @@ extern "C" int vg_jtext_render(vg_jtext *jt, const uint8_t *heads, uint64_t head
 	return VG_OK;
 }
 
-extern "C" int vg_jtext_render_host(uint64_t n_sites, uint32_t n_samples, const uint8_t *const *gt, const int32_t *const *gq, const uint8_t *heads, uint64_t heads_len, const vg_jtext_record *records, uint64_t n_records,
-                                    const uint32_t *sites, uint64_t n_site_refs, int threads, uint8_t *text, uint64_t cap, uint64_t *len, uint64_t *n_lines)
+extern "C" int vg_jtext_render_host_info(uint64_t n_sites, uint32_t n_samples, const uint8_t *const *gt, const int32_t *const *gq, const uint8_t *heads, uint64_t heads_len, const vg_jtext_record *records, uint64_t n_records,
+                                         const uint32_t *sites, uint64_t n_site_refs, int info, int threads, uint8_t *text, uint64_t cap, uint64_t *len, uint64_t *n_lines)
 {
 	if (!gt || !gq || !len || !n_lines || (!text && cap)) return fail(VG_EINVAL, "null argument");
+	if (!jt_info_mode(info)) return fail(VG_EINVAL, "vg_jtext_render_host_info: info is VG_JT_INFO_NONE or VG_JT_INFO_COUNTS");
 	if (n_samples == 0) return fail(VG_EINVAL, "vg_jtext_render_host: no samples");
 	if (n_samples > VG_JTEXT_MAX_SAMPLES) return fail(VG_ETOOBIG, "vg_jtext_render_host: more than %s samples", std::to_string(VG_JTEXT_MAX_SAMPLES).c_str());
 	if (n_sites >= (1ull << 32)) return fail(VG_EINVAL, "vg_jtext_render_host: 2^32 sites or more");
@@ -6354,9 +6416,48 @@ extern "C" int vg_jtext_render_host(uint64_t n_sites, uint32_t n_samples, const 
 	const int rc = jt_span_args(n_sites, heads, heads_len, records, n_records, sites, n_site_refs, &head_sum);
 	if (rc) return rc;
 	return guarded([&]() -> int {
-		if (!vg_jtext_host_run(gt, gq, n_samples, heads, records, n_records, sites, threads, text, cap, len, n_lines)) return fail(VG_ETOOBIG, "the text buffer is smaller than the span's bound (vg_jtext_text_bound)");
+		if (!vg_jtext_host_run_info(gt, gq, n_samples, heads, records, n_records, sites, info, threads, text, cap, len, n_lines)) return fail(VG_ETOOBIG, "the text buffer is smaller than the span's bound (vg_jtext_text_bound)");
 		return VG_OK;
 	});
+}
+extern "C" int vg_jtext_render_host(uint64_t n_sites, uint32_t n_samples, const uint8_t *const *gt, const int32_t *const *gq, const uint8_t *heads, uint64_t heads_len, const vg_jtext_record *records, uint64_t n_records,
+                                    const uint32_t *sites, uint64_t n_site_refs, int threads, uint8_t *text, uint64_t cap, uint64_t *len, uint64_t *n_lines)
+{
+	return vg_jtext_render_host_info(n_sites, n_samples, gt, gq, heads, heads_len, records, n_records, sites, n_site_refs, VG_JT_INFO_NONE, threads, text, cap, len, n_lines);
+}
+
+// the records' NS, het, hom without their text: counts[n_records][3]
+extern "C" int vg_jtext_counts(vg_jtext *jt, const vg_jtext_record *records, uint64_t n_records, const uint32_t *sites, uint64_t n_site_refs, uint32_t *counts)
+{
+	if (!jt || (!counts && n_records)) return fail(VG_EINVAL, "null argument");
+	uint64_t head_sum = 0;
+	const int rc = jt_span_args(jt->n_sites, nullptr, 0, records, n_records, sites, n_site_refs, &head_sum, false);
+	if (rc) return rc;
+	if (n_records > jt->rec_cap || n_site_refs > jt->site_cap || n_records * (jt->G + 1) >= (1ull << 32)) return fail(VG_ETOOBIG, "the span is beyond the limits the handle was created with (records, site references)");
+	if (!n_records) return VG_OK;
+	HIP_TRY(hipSetDevice(jt->device));
+	const JtStore st{jt->d_narrow, jt->d_wide, jt->d_wide_slot, jt->n_sites, jt->n_samples};
+	const int rc2 = jt_lengths_dev(jt, st, records, n_records, sites, n_site_refs, VG_JT_INFO_NONE);
+	if (rc2) return rc2;
+	HIP_TRY(hipMemcpy(counts, jt->d_counts, n_records * 12, hipMemcpyDeviceToHost));
+	return VG_OK;
+}
+extern "C" int vg_jtext_counts_host(uint64_t n_sites, uint32_t n_samples, const uint8_t *const *gt, const int32_t *const *gq, const vg_jtext_record *records, uint64_t n_records, const uint32_t *sites, uint64_t n_site_refs,
+                                    uint32_t *counts)
+{
+	if (!gt || !gq || (!counts && n_records)) return fail(VG_EINVAL, "null argument");
+	if (n_samples == 0) return fail(VG_EINVAL, "vg_jtext_counts_host: no samples");
+	if (n_samples > VG_JTEXT_MAX_SAMPLES) return fail(VG_ETOOBIG, "vg_jtext_counts_host: more than %s samples", std::to_string(VG_JTEXT_MAX_SAMPLES).c_str());
+	if (n_sites >= (1ull << 32)) return fail(VG_EINVAL, "vg_jtext_counts_host: 2^32 sites or more");
+	for (uint32_t s = 0; s < n_samples; s++) if (gt[s] && !gq[s]) return fail(VG_EINVAL, "null argument");
+	uint64_t head_sum = 0;
+	const int rc = jt_span_args(n_sites, nullptr, 0, records, n_records, sites, n_site_refs, &head_sum, false);
+	if (rc) return rc;
+	for (uint64_t i = 0; i < n_records; i++) {
+		const vg_jt_counts_t c = vg_jt_counts_host(gt, gq, n_samples, records[i], sites);
+		counts[3 * i] = c.ns; counts[3 * i + 1] = c.ns ? c.het : 0; counts[3 * i + 2] = c.ns ? c.hom : 0;
+	}
+	return VG_OK;
 }
 
 // ---- the BGZF stream of a vg_jtext: text gathers in d_text; every call compresses the whole blocks it completed ----
@@ -6465,7 +6566,7 @@ extern "C" int vg_jtext_bgzf_lines(vg_jtext *jt, const uint8_t *heads, uint64_t 
 	uint64_t head_sum = 0;
 	int rc = jt_span_args(jt->n_sites, heads, heads_len, records, n_records, sites, n_site_refs, &head_sum);
 	if (rc || (rc = jt_span_limits(jt, heads_len, n_records, n_site_refs, head_sum))) return rc;
-	if (cap < vg_jtext_bgzf_bound(vg_jt_bound(head_sum, n_records, jt->n_samples), jt->B)) return fail(VG_ETOOBIG, "the BGZF buffer is smaller than the call's bound (vg_jtext_bgzf_bound of the span's text bound)");
+	if (cap < vg_jtext_bgzf_bound(vg_jt_bound_info(head_sum, n_records, jt->n_samples, jt->info), jt->B)) return fail(VG_ETOOBIG, "the BGZF buffer is smaller than the call's bound (vg_jtext_bgzf_bound of the span's text bound)");
 	HIP_TRY(hipSetDevice(jt->device));
 	uint64_t total = 0, lines = 0, len = 0;
 	rc = jt_render_dev(jt, heads, heads_len, records, n_records, sites, n_site_refs, head_sum, jt->pend, &total, &lines);
