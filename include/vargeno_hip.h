@@ -402,6 +402,10 @@ int  vg_set_stats(vg_index *ix, int enable);      /* event counting on (default)
                                                      counting build of the kernel carries ~50 extra
                                                      registers per lane, so timed runs switch it off */
 int  vg_timing_get(vg_index *ix, vg_timing *out);
+/* Passes whose gate-open pairs the main wave tier let wait for a later iteration's stage B ("held pairs", csrc/vg_wave.h), over
+ * the batches harvested since open / vg_counts_reset (call vg_sync first).  A schedule figure, never a result: the counters are
+ * the same for every setting of VG_HOLD_PAIRS, and 0 here when that is 0. */
+uint64_t vg_held_passes(const vg_index *ix);
 
 /* SNP sites = positions seeded with ref != alt (qv.cc:637-659, 1580), ascending.
  * Counters are exact sums; the reference's 6-bit saturation (vartype.h:27, qv.cc:1411, 1419) is

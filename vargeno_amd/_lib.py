@@ -35,7 +35,8 @@ SYMBOLS = ["vg_last_error", "vg_build_id", "vg_device_count", "vg_device_memory"
            "vg_jtext_bgzf_begin", "vg_jtext_bgzf_text", "vg_jtext_bgzf_lines", "vg_jtext_bgzf_end",
            "vg_vcfidx_create", "vg_vcfidx_destroy", "vg_vcfidx_text_host", "vg_vcfidx_text_device", "vg_vcfidx_bgzf", "vg_vcfidx_bound", "vg_vcfidx_finish", "vg_vcfidx_error", "vg_vcfidx_stats",
            "vg_bgzf_deflate_device_indexed", "vg_jtext_bgzf_index",
-           "vg_jtext_create_info", "vg_jtext_text_bound_info", "vg_jtext_render_host_info", "vg_jtext_counts", "vg_jtext_counts_host"]
+           "vg_jtext_create_info", "vg_jtext_text_bound_info", "vg_jtext_render_host_info", "vg_jtext_counts", "vg_jtext_counts_host",
+           "vg_held_passes"]
 
 GZIP_STAT_FIELDS = ["members", "chunks", "guessed", "confirmed", "repaired", "tested", "slots_refused", "resume_bit"]
 
@@ -251,6 +252,12 @@ def lib():
         L.vg_jtext_render_host_info.argtypes = [C.c_uint64, C.c_uint32, vp, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, C.c_int, C.c_int, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.vg_jtext_counts.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp]
         L.vg_jtext_counts_host.argtypes = [C.c_uint64, C.c_uint32, vp, vp, vp, C.c_uint64, vp, C.c_uint64, vp]
+        try:
+            L.vg_held_passes.argtypes = [vp]
+            L.vg_held_passes.restype = C.c_uint64
+        except AttributeError:
+            if not os.environ.get("VARGENO_HIP_LIB"):                   # (an older build loaded for an A/B run holds no pairs)
+                raise
         # The library is a build product that travels next to its sources (not in git): refuse a stale one.  Its build id is the
         # sha256 of the sources it was compiled from (csrc/Makefile); VARGENO_HIP_LIB (A/B variants) opts out.
         if not os.environ.get("VARGENO_HIP_LIB"):

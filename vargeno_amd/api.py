@@ -244,6 +244,15 @@ class GenoIndex:
         check(lib().vg_timing_get(self._h, C.byref(t)))
         return dict(ms_total=float(t.ms_total), ms_pack=float(t.ms_pack), ms_main=float(t.ms_main), ms_tail=float(t.ms_tail), ms_deep_lists=float(t.ms_deep_lists), batches=int(t.batches))
 
+    @property
+    def held_passes(self):
+        """Passes the main wave tier held back for a later iteration's stage B since open / reset (vg_held_passes; sync() first).
+        Says how the kernel scheduled its work, never what it computed."""
+        fn = getattr(lib(), "vg_held_passes", None)
+        if fn is None:
+            raise RuntimeError("the library named by VARGENO_HIP_LIB predates vg_held_passes")
+        return int(fn(self._h))
+
     # ---- results -------------------------------------------------------------------------
     @property
     def num_sites(self):

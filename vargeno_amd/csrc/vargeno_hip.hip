@@ -1836,8 +1836,8 @@ struct SlotEvent : NoCopy {
 constexpr int NSLOT = 3;            // (5 and 8 were measured: no gain at 8 M-read batches, 10-30 % slower at 1 M -- more pack kernels run ahead and get in the wave kernel's way)
 struct Slot {
 	DevBuf<uint32_t> listA, listB, listC;   // spill lists, one capacity (reserve_together): main -> deep tier (A), deep tier -> lane tier (B), lost (C)
-	uint32_t *ctr = nullptr;              // [0] wave-tier overflow, [1] lane-tier overflow, [2] lost -- this batch
-	PinnedBuf<uint32_t> h_ctr;            // page-locked copy of ctr[0..3], made on the tail stream when the batch's tiers are done
+	uint32_t *ctr = nullptr;              // this batch's counter block (the layout: vg_wave.h, CTR_WORK_MAIN)
+	PinnedBuf<uint32_t> h_ctr;            // page-locked copy of ctr[0..7], made on the tail stream when the batch's tiers are done
 	// what the generic lane tier needs should the deep tier leave reads behind: it is only launched then (harvest), never empty
 	const uint8_t *lt_bases = nullptr, *lt_quals = nullptr; const uint64_t *lt_offsets = nullptr; const uint32_t *lt_gate = nullptr; bool lt_packed = false, lt_stats = false, lt_enqueued = false, lt_late = false;      // lt_late: the deep tier's leftovers went through vg_late_collect (the per-batch lane tier then only has the residual list: listA, ctr[6])
 	DevBuf<uint64_t> pk_kmer, pk_meta;                                // packed reads of this batch
@@ -1952,6 +1952,9 @@ struct vg_index {
 	int cus = 256;
 	int lane_grid_blocks = 0, wave_grid = 0;
 	uint32_t work_chunk = 128;            // reads a main-tier wave pulls from the launch's work counter at a time (VG_WORK_CHUNK)
+	uint32_t hold_pairs = VG_HOLD_PAIRS_DEFAULT;   // main tier: a wave runs stage B once this many gate-open pairs wait in it (VG_HOLD_PAIRS; 0: every iteration; at most PCAP -- vg_wave.h, "held pairs")
+	uint32_t wave_wgs = 0;                // a cap on the main tier's workgroups (VG_WAVE_WGS; 0: none).  Tests and A/B runs only: one or two workgroups make a wave of a small batch live through dozens of refills
+	uint64_t held_passes = 0;             // since reset: passes the main tier's waves have held (word CTR_HELD of a batch's counter block)
 	uint32_t w2_chunk = 8, w2_wpc = 3;    // deep tier: reads a wave pulls at a time (VG_W2_CHUNK), workgroups per CU of its grid (VG_W2_WPC)
 	bool w2_full_grid = false;            // ... and that grid for every batch, whatever the lists before were like (VG_W2_FULL_GRID)
 	FqStream *d_fq = nullptr;             // FASTQ stream state (vg_fastq_stream_*)
@@ -2324,6 +2327,8 @@ static int init_handle(vg_index *ix, int device)
 	ix->wave_grid = ix->cus * wpc;
 	if (const char *e = getenv("VG_FORCE_GENERIC")) ix->force_generic = atoi(e) != 0;
 	if (const char *e = getenv("VG_WORK_CHUNK")) ix->work_chunk = (uint32_t)std::max(1, atoi(e));
+	if (const char *e = getenv("VG_HOLD_PAIRS")) ix->hold_pairs = (uint32_t)std::min<long long>(std::max<long long>(0, atoll(e)), (long long)PCAP);
+	if (const char *e = getenv("VG_WAVE_WGS")) ix->wave_wgs = (uint32_t)std::max(0, atoi(e));
 	if (const char *e = getenv("VG_W2_CHUNK")) ix->w2_chunk = (uint32_t)std::max(1, atoi(e));
 	if (const char *e = getenv("VG_W2_WPC")) ix->w2_wpc = (uint32_t)std::max(1, atoi(e));
 	ix->w2_full_grid = getenv("VG_W2_FULL_GRID") != nullptr;
@@ -2803,7 +2808,7 @@ static int build_on_device(vg_index *ix, DevCols &c, const ViewPlan &plan, uint6
 	ix->planes[0].p = PlanePtr{ix->d.cnt, ix->d.cnt4};
 	ix->dirty_up.assign(1, 0u);
 	HIP_TRY(hipMemcpy(ix->d_planes, &ix->planes[0].p, sizeof(PlanePtr), hipMemcpyHostToDevice));
-	for (Slot &sl : ix->slot) if ((rc = dev_alloc(ix, &sl.ctr, 16, true, true))) return rc;       // [0..2] spill counts, [3] invalid reads, [4],[5] work counters of the two wave tiers, [6] reads left for the per-batch lane tier
+	for (Slot &sl : ix->slot) if ((rc = dev_alloc(ix, &sl.ctr, 16, true, true))) return rc;       // sixteen words a batch; the layout: vg_wave.h, CTR_WORK_MAIN
 	if ((rc = dev_alloc(ix, &ix->d_clamped, 2 * ix->n_sites + 2, false, true))) return rc;
 	if ((rc = dev_alloc(ix, &ix->d_fq, 1, true, true))) return rc;
 	if ((rc = dev_alloc(ix, &ix->bz.d_key, 1, true, true))) return rc;
@@ -3148,6 +3153,7 @@ extern "C" int vg_index_open(const char *prefix, int device, vg_index **out)
 }
 extern "C" uint64_t vg_index_device_bytes(const vg_index *ix) { return ix ? ix->dev_bytes : 0; }
 extern "C" uint64_t vg_num_sites(const vg_index *ix) { return ix ? ix->n_sites : 0; }
+extern "C" uint64_t vg_held_passes(const vg_index *ix) { return ix ? ix->held_passes : 0; }
 extern "C" uint32_t vg_index_views(const vg_index *ix)
 {
 	if (!ix) return 0;
@@ -3190,6 +3196,7 @@ static int harvest(vg_index *ix, Slot &sl)
 		HIP_TRY(hipStreamSynchronize(ix->tail2));
 	}
 	for (int i = 0; i < 4; i++) ix->cum[i] += sl.h_ctr.p[i];
+	ix->held_passes += sl.h_ctr.p[CTR_HELD];
 	ix->planes[sl.plane].invalid += sl.h_ctr.p[3];
 	// the deep tier's grid follows the lists it has been getting (enqueue_batch): the larger of this batch's and half the hint before
 	ix->spill_hint = std::max<uint32_t>(sl.h_ctr.p[0], ix->spill_hint / 2);
@@ -3294,9 +3301,16 @@ static int begin_batch(Slot &sl, hipStream_t on, hipStream_t produced_on)
 
 // One tier of the wave machine (<W1_*>: the main tier, <W3_*, 1>: the deep tier): the kernel built for an index without the merged
 // view (big), the instantiation that compares (F, lo32) (sdx), or the general one, as the counting build (stats) or the plain one.
+// hold (it matters to the main tier's two timed instantiations only): gate-open pairs may wait (vg_wave.h, "held pairs"); without it
+// those two run as vg_wave_kernel_plain.
 template <int ECAP, int NCAP, int WPB, class... A>
-static void launch_wave(bool big, bool sdx, bool stats, unsigned grid, hipStream_t st, const A &...a)
+static void launch_wave(bool big, bool sdx, bool stats, bool hold, unsigned grid, hipStream_t st, const A &...a)
 {
+	if constexpr (WPB > 1) if (!hold && !big && !stats) {
+		if (sdx) vg_wave_kernel_plain<ECAP, NCAP, WPB, true><<<grid, 64 * WPB, 0, st>>>(a...);
+		else vg_wave_kernel_plain<ECAP, NCAP, WPB, false><<<grid, 64 * WPB, 0, st>>>(a...);
+		return;
+	}
 	if (big) vg_wave_kernel_big<ECAP, NCAP, WPB><<<grid, 64 * WPB, 0, st>>>(a...);
 	else if (sdx) vg_wave_kernel<false, ECAP, NCAP, WPB, true><<<grid, 64 * WPB, 0, st>>>(a...);
 	else if (stats) vg_wave_kernel<true, ECAP, NCAP, WPB><<<grid, 64 * WPB, 0, st>>>(a...);
@@ -3332,8 +3346,15 @@ static int enqueue_batch(vg_index *ix, Slot &sl, const bool stats, const uint8_t
 		// dynamically, which costs less than holding the wave kernel back for them (0.71 -> 0.66 ms per 1 M-read step).
 		HIP_TRY(hipEventRecord(sl.wave_begin, ix->stream));       // the wave kernel's own start
 		ix->planes[sl.plane].dirty = true;
-		const unsigned wgrid = (unsigned)std::min<uint64_t>((n_reads + 64 * W1_WPB - 1) / (64 * W1_WPB), (uint64_t)ix->wave_grid / W1_WPB);
-		launch_wave<W1_ECAP, W1_NCAP, W1_WPB>(big, sdx, stats, wgrid, ix->stream, dv, sl.pk_kmer.p, sl.pk_meta.p, d_offsets, n_reads, nullptr, d_n_reads, sl.listA.p, &ctr[0], &ctr[4], ix->work_chunk, ix->d_stats, fin);
+		unsigned wgrid = (unsigned)std::min<uint64_t>((n_reads + 64 * W1_WPB - 1) / (64 * W1_WPB), (uint64_t)ix->wave_grid / W1_WPB);
+		if (ix->wave_wgs) wgrid = std::min<unsigned>(wgrid, ix->wave_wgs);
+		// Held pairs pay where the prune has left a wave few pairs per iteration: reads of at most four chunks.  Longer reads are not
+		// pruned and meet the threshold in nearly every iteration, so a batch whose reads average five chunks or more runs the plain
+		// kernel, as does every batch under a threshold of 0.  A batch whose length is not known here (total_bases 0: packed on the host,
+		// or framed on the device) has a mean of 0 and is held.  The mean decides for the whole batch: a mixed batch below 160 is held
+		// with its long reads in it, which is exact like every schedule and has not been measured.
+		const bool hold = ix->hold_pairs > 0 && mean_len < 5 * 32;
+		launch_wave<W1_ECAP, W1_NCAP, W1_WPB>(big, sdx, stats, hold, wgrid, ix->stream, dv, sl.pk_kmer.p, sl.pk_meta.p, d_offsets, n_reads, nullptr, d_n_reads, sl.listA.p, &ctr[0], &ctr[CTR_WORK_MAIN], ix->work_chunk, ix->hold_pairs, ix->d_stats, fin);
 		HIP_TRY(hipEventRecord(sl.wave_end, ix->stream));
 		ix->last_wave_end = sl.wave_end;
 		// tail stream, the deep tier: the same kernel with deeper tables over the spill list (single-wave workgroups of 42 KB of LDS).
@@ -3351,7 +3372,7 @@ static int enqueue_batch(vg_index *ix, Slot &sl, const bool stats, const uint8_t
 		// the waves pull their work from a counter and their pulls grow with the list -- just by fewer waves.
 		unsigned w2grid = (unsigned)std::min<uint64_t>((n_reads + 63) / 64, (uint64_t)ix->cus * ix->w2_wpc);
 		if (ix->spill_known && !ix->w2_full_grid) w2grid = std::min<unsigned>(w2grid, std::max<unsigned>(32u, (2u * ix->spill_hint + ix->w2_chunk - 1) / ix->w2_chunk + 16u));
-		launch_wave<W3_ECAP, W3_NCAP, 1>(big, sdx, stats, w2grid, ix->tail, dv, sl.pk_kmer.p, sl.pk_meta.p, d_offsets, 0, sl.listA.p, &ctr[0], sl.listB.p, &ctr[1], &ctr[5], ix->w2_chunk, ix->d_stats, nofuse);
+		launch_wave<W3_ECAP, W3_NCAP, 1>(big, sdx, stats, false, w2grid, ix->tail, dv, sl.pk_kmer.p, sl.pk_meta.p, d_offsets, 0, sl.listA.p, &ctr[0], sl.listB.p, &ctr[1], &ctr[5], ix->w2_chunk, 0u, ix->d_stats, nofuse);
 		// what the deep tier leaves behind goes to the handle's late store (the lane machine runs over it once, at the next
 		// synchronisation); the slot only keeps what the store cannot take (listA is free again: the deep tier has consumed it)
 		sl.lt_late = ix->late.state != nullptr;
@@ -5208,6 +5229,7 @@ extern "C" int vg_counts_reset(vg_index *ix)
 	for (Plane &pl : ix->planes) pl.invalid = 0;
 	HIP_TRY(hipMemsetAsync(ix->d_stats, 0, S_COUNT * sizeof(unsigned long long), ix->stream));
 	for (auto &c : ix->cum) c = 0;
+	ix->held_passes = 0;
 	ix->host_invalid = 0;
 	HIP_TRY(hipStreamSynchronize(ix->stream));
 	return VG_OK;

@@ -80,6 +80,13 @@ constexpr int SEC_W = VG_SEC_W;   // entries of an LO32-view bucket fetched in o
 #endif
 constexpr uint32_t SEC_LONG = VG_SEC_LONG;   // a longer bucket, up to this many entries, is dealt to the lanes record by record in stage B1
 constexpr int PCAP = 32;         // rows of the stage-B pair table (a wave with more gate-open chunks takes several windows)
+#ifndef VG_HOLD_PAIRS_DEFAULT
+#define VG_HOLD_PAIRS_DEFAULT 12  // held pairs: gate-open pairs a main-tier wave lets wait before it runs stage B (0: stage B every iteration; see vg_wave_body)
+#endif
+// A batch's counter block (sixteen words, zeroed per batch; Slot::ctr in vargeno_hip.hip): [0..2] spill counts of the three lists,
+// [3] invalid reads, [4] and [5] the work counters of the main and the deep wave tier, [6] reads left for the per-batch lane tier,
+// [7] passes the main tier held.  The two words the main tier's kernel finds from its work counter's address:
+constexpr int CTR_WORK_MAIN = 4, CTR_HELD = 7;
 constexpr int HCAP = 4;          // high-half reference hits per pair kept from the LO32-ordered view (more: the 48 queries are issued)
 
 // packed reads: chunk k-mers at [offsets[r] >> 5 ...), one flag word per read
@@ -130,11 +137,11 @@ __device__ inline uint32_t wave_sum(uint32_t v)
 // SDX: the instantiation for a direct table of fewer than 2^32 buckets (DevIndex::dx_bits < 32: small indexes, and hg38-scale ones
 // under a budget): the look-up compares (F, lo32) -- the key's bits below the bucket -- where the 2^32-bucket form compares lo32.
 // A kernel of its own for the same reason as NOMX: the headline instantiation keeps its registers and its instruction stream.
-template <bool STATS, int W_ECAP, int W_NCAP, int WPB, bool NOMX, bool SDX = false>
+template <bool STATS, int W_ECAP, int W_NCAP, int WPB, bool NOMX, bool SDX = false, bool HOLDK = false>
 __device__ __forceinline__ void vg_wave_body(const DevIndex &d, const uint64_t *__restrict__ pk_kmer, const uint64_t *__restrict__ pk_meta,
                                              const uint64_t *__restrict__ offsets, uint64_t n_reads_arg,
                                              const uint32_t *__restrict__ read_ids, const uint32_t *__restrict__ n_ids,
-                                             uint32_t *overflow_list, uint32_t *overflow_count, uint32_t *work_next, const uint32_t WORK_CHUNK_ARG, unsigned long long *stats,
+                                             uint32_t *overflow_list, uint32_t *overflow_count, uint32_t *work_next, const uint32_t WORK_CHUNK_ARG, const uint32_t HOLD_PAIRS_ARG, unsigned long long *stats,
                                              const FuseIn fuse)
 {
 	// Exact contexts are kept BY VOTE KEY, not one by one (r04).  A vote key (qv.cc:132-178) is the IMPLIED READ POSITION of a
@@ -239,9 +246,38 @@ __device__ __forceinline__ void vg_wave_body(const DevIndex &d, const uint64_t *
 	bool drained = false;
 
 	bool active = false;
+	// HELD PAIRS.  HOLD is true in the timed main tier of vg_wave_kernel only: its headline and its SDX instantiation.
+	// Who launches what (enqueue_batch): a batch of reads of at most four chunks, under a threshold above 0, goes to vg_wave_kernel;
+	// a batch of longer reads, and every batch under a threshold of 0, goes to vg_wave_kernel_plain, the same tier without the hold.
+	// The deep tier, the counting build and the kernel for an index without the merged view never hold.
+	// Why two kernels: in one kernel, behind a run-time threshold of 0, the deciding, parking and restoring cost 0.9 % of a step
+	// with nobody held.  With HOLD false none of it is compiled in.
+	// What is held and why: stage B costs a wave a chain of dependent waits per ITERATION, whatever the number of pairs.  After the prune a wave has 4.6 pairs per iteration for rows of 32 and rounds of 64.  So a lane whose pass still has
+	// gate-open pairs may WAIT, its stage-A result intact, while the other lanes vote, walk and take new reads, and stage B runs once
+	// for the pairs of several iterations.  A held lane is `active` (the refill gives it no read), runs neither stage A nor stage C and
+	// queues no auxiliary row; what stages B and C need of it is where it was: its K_* column (nothing writes a held lane's column),
+	// rid, n, gates, pass, slot0 -- and kcnt, parked in H_kcnt.  heldm: bit l = lane l is held (wave-uniform).
+	// The rule, once per iteration, wave-uniform: with W = the pairs of the held lanes and of the lanes that ran stage A,
+	//     flush = W >= hold_pairs  ||  the refill left a lane free (the launch has run out for this wave)
+	// No flush: lanes with pairs park kcnt and become held; everybody else runs stage C without neighbour contexts, as a lane without
+	// a pair always has.  Flush: held lanes take kcnt back and form `pend` again -- from the same mask column, pass, gates and n: the
+	// same value -- and join the new lanes in the prefix sum, the windows and the rounds; nobody is held afterwards.
+	// Termination: while nothing flushes every lane that is not held finishes a pass per iteration, so either the waiting pairs reach
+	// the threshold (64 held lanes are at least 64 pairs, and hold_pairs is at most PCAP), or the launch runs out of reads: then the
+	// refill leaves a lane free and every later iteration flushes.  A wave never ends an iteration with a held lane and nothing left to
+	// do, and the exit test needs no change: held lanes are active.
+	// Exactness: a job's stages read and write its own column, its own registers and the index; across jobs there are only integer
+	// atomicAdds on counters and appends to the spill list, whose sums do not depend on the order.  Every tier is exact, so the
+	// counters are bit-identical for every hold_pairs.
+	constexpr bool HOLD = HOLDK && !STATS && !NOMX && WPB > 1;
+	__shared__ uint8_t H_kcnt[HOLD ? 64 * WPB : 1];
+	const uint32_t hold_pairs = HOLD ? (HOLD_PAIRS_ARG < (uint32_t)PCAP ? HOLD_PAIRS_ARG : (uint32_t)PCAP) : 0u;
+	uint64_t heldm = 0ull;
+	uint32_t held_passes = 0;                            // wave-uniform: passes this wave has held
+	const auto held_lane = [&heldm]() -> bool { return HOLD && __builtin_amdgcn_inverse_ballot_w64(heldm); };      // (the mask itself is the condition: no instruction)
 #ifdef VG_STAGE_CLOCKS
 	long long clk[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tlast = clock64();
-	uint32_t iters = 0, dbg_pairs = 0, dbg_items = 0, dbg_rounds = 0, dbg_dq = 0, dbg_rows = 0, dbg_large = 0, dbg_secbad = 0;
+	uint32_t iters = 0, dbg_pairs = 0, dbg_items = 0, dbg_rounds = 0, dbg_dq = 0, dbg_rows = 0, dbg_large = 0, dbg_secbad = 0, dbg_holds = 0, dbg_flushes = 0;
 #endif
 	uint32_t rid = 0, n = 0, gates = 0, pass = 0;
 	uint32_t slot0 = 0;                                  // first k-mer slot of the read (a batch holds < 2^37 bases: checked on the host)
@@ -382,7 +418,7 @@ __device__ __forceinline__ void vg_wave_body(const DevIndex &d, const uint64_t *
 		uint32_t kcnt = 0, ncnt = 0;                             // vote keys of this pass (slots [0, kcnt)), neighbour contexts
 		uint32_t npend = 0;                                      // auxiliary rows this lane has queued for the wave to expand together (below)
 		bool ovf = false;
-		if (active) {
+		if (active && !held_lane()) {
 			// an exact context of chunk c at k-mer position p (qv.cc:850-937): find its vote key among slots [lo, hi) of the lane's
 			// table, four candidates per LDS round trip starting at `hint` -- the auxiliary rows of consecutive chunks of a read inside
 			// a repeat list the same copies in the same order, so the slot after the last match is usually the one.  Returns the slot,
@@ -814,6 +850,7 @@ __device__ __forceinline__ void vg_wave_body(const DevIndex &d, const uint64_t *
 			// A pass without a single exact hit has no vote key, and neighbour contexts cannot open one (qv.cc:134-139): nothing its
 			// gate-open chunks could find would vote or be walked.  That is the whole forward pass of every reverse-strand read -- a
 			// third of all passes -- so the timed build skips stage B for it (the counting build runs it: its events are priced).
+			if constexpr (HOLD) if (held_lane()) kcnt = H_kcnt[col];      // a held lane's keys as its stage A left them
 #ifdef VG_NO_HOPELESS_SKIP
 			const bool hopeless = false;
 #else
@@ -844,7 +881,23 @@ __device__ __forceinline__ void vg_wave_body(const DevIndex &d, const uint64_t *
 			const uint32_t my_np = (uint32_t)__popc(pend);
 			uint32_t pincl = my_np;
 			for (int o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(pincl, o); if ((int)lane >= o) pincl += y; }
-			const uint32_t my_base = pincl - my_np, P = (uint32_t)__builtin_amdgcn_readlane((int)pincl, 63);    // wave-uniform: scalar
+			const uint32_t my_base = pincl - my_np, P_all = (uint32_t)__builtin_amdgcn_readlane((int)pincl, 63);    // wave-uniform: scalar
+			// held pairs: flush, or hold the lanes that have pairs (P_all counts the held lanes' pairs and the new ones)
+			uint32_t P = P_all;
+			if constexpr (HOLD) {
+				if (P_all >= hold_pairs || __ballot(!active) != 0ull) heldm = 0ull;      // (a lane the refill left free: `active` has not changed since)
+				else {
+					const bool newly = pend != 0u && !held_lane();
+					if (newly) H_kcnt[col] = (uint8_t)kcnt;
+					const uint64_t nm = __ballot(newly);
+					held_passes += (uint32_t)__popcll(nm);
+					heldm |= nm;
+					P = 0u;                                              // no window, no round: this iteration's stage B is the two stores below
+				}
+#ifdef VG_STAGE_CLOCKS
+				dbg_holds += (uint32_t)__popcll(heldm); dbg_flushes += P ? 1u : 0u;
+#endif
+			}
 			N_cnt[col] = 0; N_ovf[col] = 0;
 			if constexpr (STATS) for (int i = 0; i < NSH; i++) S_own[i][col] = 0;
 			for (uint32_t w0 = 0; w0 < P; w0 += PCAP) {
@@ -1366,7 +1419,7 @@ __device__ __forceinline__ void vg_wave_body(const DevIndex &d, const uint64_t *
 		VG_WAVE_SYNC();
 
 		// ------------------------------------------------------------------ stage C: replay the vote, walk the pile-up
-		if (active) {
+		if (active && !held_lane()) {
 			bool processed = false;
 			if (!ovf) {
 				// improved_index_table_add, qv.cc:132-178, from per-key totals (see the key table's description): a key's frequency is the
@@ -1555,25 +1608,38 @@ __device__ __forceinline__ void vg_wave_body(const DevIndex &d, const uint64_t *
 		VG_CLK(5);
 	}
 #ifdef VG_STAGE_CLOCKS
-	{ const uint32_t dq = wave_sum<false>(dbg_dq); if (!STATS && lane == 0 && (blockIdx.x % 97u) == 0 && wv == 0) printf("DBG blk %u iters %u pairs %u items %u rounds %u dualq %u large %u secbad %u\n", blockIdx.x, iters, dbg_pairs, dbg_items, dbg_rounds, dq, dbg_large, dbg_secbad); }
+	{ const uint32_t dq = wave_sum<false>(dbg_dq); if (!STATS && lane == 0 && (blockIdx.x % 97u) == 0 && wv == 0) printf("DBG blk %u iters %u pairs %u items %u rounds %u dualq %u large %u secbad %u holds %u flushes %u\n", blockIdx.x, iters, dbg_pairs, dbg_items, dbg_rounds, dq, dbg_large, dbg_secbad, dbg_holds, dbg_flushes); }
 	if (!STATS && lane == 0 && (blockIdx.x % 97u) == 0 && wv == 0)
 		printf("CLK blk %u iters %u refill %lld A %lld B0 %lld B1 %lld vote %lld walk %lld wload %lld wloop %lld watom %lld Akmer %lld Adx %lld Ascan %lld ecap %d\n", blockIdx.x, iters, clk[0], clk[1], clk[2], clk[3], clk[4], clk[5], clk[6], clk[7], clk[8], clk[9], clk[10], clk[11], W_ECAP);
 #endif
 	if constexpr (STATS) {
 		for (int i = 0; i < S_COUNT; i++) if (tot.v[i]) atomicAdd(&stats[i], (unsigned long long)tot.v[i]);
 	}
+	if constexpr (HOLD) if (held_passes && lane == 0) atomicAdd(work_next + (CTR_HELD - CTR_WORK_MAIN), held_passes);      // work_next is the block's word CTR_WORK_MAIN
 }
 
 #undef lane
 #undef col
 
+// (its timed main-tier instantiations hold pairs; the deep tier and the counting build have nothing to hold: vg_wave_body, HOLD)
 template <bool STATS, int W_ECAP, int W_NCAP, int WPB, bool SDX = false>
 __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(WPB > 1 ? VG_WPE : 1))) void vg_wave_kernel(DevIndex d, const uint64_t *__restrict__ pk_kmer, const uint64_t *__restrict__ pk_meta,
                                                      const uint64_t *__restrict__ offsets, uint64_t n_reads_arg,
                                                      const uint32_t *__restrict__ read_ids, const uint32_t *__restrict__ n_ids,
-                                                     uint32_t *overflow_list, uint32_t *overflow_count, uint32_t *work_next, const uint32_t WORK_CHUNK_ARG, unsigned long long *stats, const FuseIn fuse)
+                                                     uint32_t *overflow_list, uint32_t *overflow_count, uint32_t *work_next, const uint32_t WORK_CHUNK_ARG, const uint32_t HOLD_PAIRS_ARG, unsigned long long *stats, const FuseIn fuse)
 {
-	vg_wave_body<STATS, W_ECAP, W_NCAP, WPB, false, SDX>(d, pk_kmer, pk_meta, offsets, n_reads_arg, read_ids, n_ids, overflow_list, overflow_count, work_next, WORK_CHUNK_ARG, stats, fuse);
+	vg_wave_body<STATS, W_ECAP, W_NCAP, WPB, false, SDX, true>(d, pk_kmer, pk_meta, offsets, n_reads_arg, read_ids, n_ids, overflow_list, overflow_count, work_next, WORK_CHUNK_ARG, HOLD_PAIRS_ARG, stats, fuse);
+}
+
+// the timed main tier without held pairs: a threshold of 0, and batches of reads of more than four chunks (enqueue_batch).
+// It takes HOLD_PAIRS_ARG and ignores it, so that launch_wave hands every kernel of the tier one argument pack.
+template <int W_ECAP, int W_NCAP, int WPB, bool SDX>
+__global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(WPB > 1 ? VG_WPE : 1))) void vg_wave_kernel_plain(DevIndex d, const uint64_t *__restrict__ pk_kmer, const uint64_t *__restrict__ pk_meta,
+                                                     const uint64_t *__restrict__ offsets, uint64_t n_reads_arg,
+                                                     const uint32_t *__restrict__ read_ids, const uint32_t *__restrict__ n_ids,
+                                                     uint32_t *overflow_list, uint32_t *overflow_count, uint32_t *work_next, const uint32_t WORK_CHUNK_ARG, const uint32_t HOLD_PAIRS_ARG, unsigned long long *stats, const FuseIn fuse)
+{
+	vg_wave_body<false, W_ECAP, W_NCAP, WPB, false, SDX, false>(d, pk_kmer, pk_meta, offsets, n_reads_arg, read_ids, n_ids, overflow_list, overflow_count, work_next, WORK_CHUNK_ARG, HOLD_PAIRS_ARG, stats, fuse);
 }
 
 // the timed build for an index without the merged view (see vg_wave_body)
@@ -1581,9 +1647,9 @@ template <int W_ECAP, int W_NCAP, int WPB>
 __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(WPB > 1 ? VG_WPE : 1))) void vg_wave_kernel_big(DevIndex d, const uint64_t *__restrict__ pk_kmer, const uint64_t *__restrict__ pk_meta,
                                                      const uint64_t *__restrict__ offsets, uint64_t n_reads_arg,
                                                      const uint32_t *__restrict__ read_ids, const uint32_t *__restrict__ n_ids,
-                                                     uint32_t *overflow_list, uint32_t *overflow_count, uint32_t *work_next, const uint32_t WORK_CHUNK_ARG, unsigned long long *stats, const FuseIn fuse)
+                                                     uint32_t *overflow_list, uint32_t *overflow_count, uint32_t *work_next, const uint32_t WORK_CHUNK_ARG, const uint32_t HOLD_PAIRS_ARG, unsigned long long *stats, const FuseIn fuse)
 {
-	vg_wave_body<false, W_ECAP, W_NCAP, WPB, true>(d, pk_kmer, pk_meta, offsets, n_reads_arg, read_ids, n_ids, overflow_list, overflow_count, work_next, WORK_CHUNK_ARG, stats, fuse);
+	vg_wave_body<false, W_ECAP, W_NCAP, WPB, true>(d, pk_kmer, pk_meta, offsets, n_reads_arg, read_ids, n_ids, overflow_list, overflow_count, work_next, WORK_CHUNK_ARG, HOLD_PAIRS_ARG, stats, fuse);
 }
 
 }  // namespace vg
