@@ -24,6 +24,7 @@
 // kernel with deeper lists, then the generic lane machine of vg_device.h (exactness is never traded).
 #pragma once
 #include "vg_device.h"
+#include "vg_acand.h"
 
 #ifndef VG_WPE
 #define VG_WPE 4          // waves per SIMD the main tier is compiled for (128 VGPRs)
@@ -626,6 +627,8 @@ __device__ __forceinline__ void vg_wave_body(const DevIndex &d, const uint64_t *
 						// anything deeper is rare and goes one by one); then each chunk's exact contexts are appended (qv.cc:850-937),
 						// reference hit first, then SNP hit.  An ambiguous k-mer with exactly two positions carries both in its entry
 						// (flag PAIR, set by vg_inline_pairs), so only k-mers with 3-10 copies still read their auxiliary row.
+#ifdef VG_A_PER_SITE
+						// (A/B builds only: every site of the look-up searches the key table itself, as before the drain below)
 						#pragma unroll
 						for (uint32_t z0 = 0; z0 < 4; z0 += 2) {
 							constexpr uint32_t SW = VG_SCAN_W;
@@ -709,6 +712,119 @@ __device__ __forceinline__ void vg_wave_body(const DevIndex &d, const uint64_t *
 								}
 							}
 						}
+#else
+						// DRAINED CANDIDATES.  The look-up of a chunk only COMPARES: every entry with the chunk's key goes to vg_acand_note
+						// (vg_acand.h), which keeps the chunk's at most six candidates -- reverse-strand pushes, reference hit, SNP hit, rows --
+						// in named registers and touches no key table.  After a PAIR of chunks one loop drains both lists: in trip k a lane
+						// handles its k-th candidate, whichever kind it is -- ONE key-table search whose range ([0, kcnt) or the reverse block
+						// [rc_top, W_ECAP)) and insert (grow up / grow down) are per-lane selects, one copy of the row code.  Through the
+						// per-site form every site searched the table itself: up to eight searches per chunk, each executed whenever ANY of the
+						// wave's 64 lanes needed it, which with half the lanes of the other strand, a SNP hit in one slot in twenty and a few
+						// PAIRs is nearly always -- the wave paid the sum over the sites where it needs the maximum over its lanes.
+						// A lane's order is the per-site form's: chunk by chunk, a chunk's reverse-strand pushes before its forward pushes, so
+						// the key table, kcnt, rc_top, ovf come out the same for every read.  The loop over the quad's two pairs is a real loop, so that
+						// the drain exists once: a trip looks at records 0 and 1, and the first trip ends by moving records 2 and 3 there (a
+						// branch per pair instead would keep all four records alive through both drains).
+						#pragma nounroll
+						for (uint32_t z0 = 0; z0 < 4u; z0 += 2u) {
+							VgAChunk ac[2];                                            // (indexed by constants only)
+							bool rc_ok = rc_top != RC_BAD;                             // the reverse block may take candidates (see vg_acand_note)
+							constexpr uint32_t SW = VG_SCAN_W;
+							uint4 sv[2][SW];
+							#pragma unroll
+							for (uint32_t y = 0; y < 2; y++) {
+								const uint32_t cnt = ecnt(bq[y]), lo = bq[y].w;
+								#pragma unroll
+								for (uint32_t x = 0; x < SW; x++) { sv[y][x] = make_uint4(0xFFFFFFFFu, 0, 0xFFFF0000u, 0); if (more[y] && x + 1u < cnt) sv[y][x] = gather<uint4>(d.mx + (lo + 1u + x)); }
+							}
+							#pragma unroll
+							for (uint32_t y = 0; y < 2; y++) {
+								const uint32_t z = z0 + y;
+								vg_acand_begin(ac[y], pass, rc_ok);
+								if (z >= m) continue;
+								cur.add(S_CHUNKS, 1);
+								const uint4 b = bq[y];
+								const xkey_t key = kx[y];                               // (lo32, or (F, lo32) under SDX)
+								const uint32_t ks = (sbits >> z) & 1u;
+								const bool pal = (sbits >> (4u + z)) & 1u;
+								if ((b.z & 1u) && ekey(b) == key)                      // the inline first entry (dx flags: 2 SNP, 4 ambiguous, 8 PAIR, 32 strand, 64 / 128 quiet)
+									vg_acand_note(ac[y], ks, pal, (b.z & 2u) != 0u, (b.z >> 5) & 1u, b.y, b.w, 1u | (((b.z >> 2) & 1u) << 1) | (((b.z >> 3) & 1u) << 2) | (b.z & VG_QUIET_MASK));
+								if (more[y]) {
+									const uint32_t cnt = ecnt(b), lo = b.w, hi = lo + cnt;
+									auto take = [&](const uint4 v) {                     // mx flags: 1 SNP, 2 ambiguous, 4 PAIR, 8 strand, 64 / 128 quiet
+										vg_acand_note(ac[y], ks, pal, (v.z & 1u) != 0u, (v.z >> 3) & 1u, v.y, v.w, 1u | (v.z & 2u) | (v.z & 4u) | (v.z & VG_QUIET_MASK));
+									};
+									#pragma unroll
+									for (uint32_t x = 0; x < SW; x++) if (x + 1u < cnt && ekey(sv[y][x]) == key) take(sv[y][x]);
+									if (cnt > SW + 1u && ekey(sv[y][SW - 1]) <= key) {  // the bucket goes on and may still hold the key
+										uint32_t e = lo + SW + 1u;
+										if (cnt > 8u) { uint32_t eb = hi; while (e < eb) { const uint32_t mm = e + ((eb - e) >> 1); if (ekey(d.mx[mm]) < key) e = mm + 1; else eb = mm; } }
+										for (; e < hi; e++) {
+											const uint4 v = d.mx[e];
+											if (ekey(v) < key) continue;
+											if (ekey(v) > key) break;
+											take(v);
+										}
+									}
+								}
+								rc_ok = ac[y].usable;
+							}
+							const uint32_t m0 = vg_acand_meta(ac[0]), m1 = vg_acand_meta(ac[1]);
+							if ((m0 & 4u) && (ac[0].rf & 2u)) cur.add(S_AUX_REF, 1);
+							if ((m0 & 16u) && (ac[0].sf & 2u)) cur.add(S_AUX_SNP, 1);
+							if ((m1 & 4u) && (ac[1].rf & 2u)) cur.add(S_AUX_REF, 1);
+							if ((m1 & 16u) && (ac[1].sf & 2u)) cur.add(S_AUX_SNP, 1);
+							// the twelve slots as plain values (a select over the closure's variables would be a select of addresses)
+							const uint32_t a0 = ac[0].v[0], a1 = ac[0].v[1], a2 = ac[0].v[2], a3 = ac[0].v[3], a4 = ac[0].v[4], a5 = ac[0].v[5];
+							const uint32_t b0 = ac[1].v[0], b1 = ac[1].v[1], b2 = ac[1].v[2], b3 = ac[1].v[3], b4 = ac[1].v[4], b5 = ac[1].v[5];
+							uint32_t vm = (m0 & 63u) | ((m1 & 63u) << VG_AC_SLOTS);      // slots still to drain: chunk z0's, then chunk z0 + 1's
+							#pragma nounroll
+							while (vm) {
+								const uint32_t j = (uint32_t)__ffs((int)vm) - 1u;
+								vm &= vm - 1u;
+								const bool second = j >= VG_AC_SLOTS;
+								const uint32_t s = second ? j - VG_AC_SLOTS : j, mm = second ? m1 : m0;
+								const bool odd = (s & 1u) != 0u;
+								const uint32_t x01 = odd ? (second ? b1 : a1) : (second ? b0 : a0), x23 = odd ? (second ? b3 : a3) : (second ? b2 : a2), x45 = odd ? (second ? b5 : a5) : (second ? b4 : a4);
+								const uint32_t val = s >= 4u ? x45 : s >= 2u ? x23 : x01;
+								const uint32_t cf = c + z0 + (second ? 1u : 0u);          // the candidate's chunk of this pass
+								if (vg_acand_is_row(mm, s)) {
+									// An auxiliary row (a k-mer with 3-10 copies) is not expanded here but QUEUED -- the neighbour lists' LDS slots are idle
+									// during stage A: row index and chunk per entry -- and the wave expands everybody's rows together after the look-ups
+									// (below).  A pass with a row has exact hits of its own: the reverse-strand block will not be used.  An index whose
+									// rows repeat positions (DevIndex::aux_dups), and a lane whose queue is full, expand the row now, the careful way.
+									const uint32_t is_snp = s == 4u ? 1u : 0u;
+									if (d.aux_dups || npend == (uint32_t)W_NCAP) push_row((is_snp ? d.snp_aux_pos : d.ref_aux) + (uint64_t)val * AUX_COLS, cf);
+									else {
+										N_kpos[npend][col] = val; N_meta[npend][col] = (uint16_t)(cf | (is_snp << 5));
+										npend++;
+										rc_top = RC_BAD;
+									}
+								} else {
+									// a push: an exact context of chunk cf of this pass at position val -- or, of the other strand, of pass 1's chunk
+									// n - 1 - cf, into the block that grows down from the top of the list (given up when it meets the forward list or
+									// when a chunk votes twice for a key; the forward list then sends the read to the next tier)
+									const bool rev = vg_acand_is_reverse(s);
+									if (!rev) cur.add(S_CTX, 1);
+									if (rev ? rc_top != RC_BAD : !ovf) {
+										const uint32_t cc = rev ? n - 1u - cf : cf, q = val - 32u * cc;
+										const uint32_t hq = vg_acand_quiet_of(mm, s), qb = hq ? vg_quiet_chunks(hq, cc, n) << KFREE : 0u;
+										bool dup = false;
+										if (key_find(q, cc, rev ? rc_top : 0u, rev ? (uint32_t)W_ECAP : kcnt, dup, qb) == (uint32_t)W_ECAP) {
+											if (rev ? rc_top > kcnt : kcnt < (uint32_t)W_ECAP) {
+												const uint32_t at = rev ? rc_top - 1u : kcnt;
+												K_idx[at][col] = q; K_mask[at][col] = (kmask_t)((1u << cc) | qb);
+												if (rev) rc_top = at; else { kcnt++; hint = kcnt; }
+											} else if (rev) rc_top = RC_BAD;
+											else { VG_OVF(0); ovf = true; }
+										} else if (dup) { if (rev) rc_top = RC_BAD; else { VG_OVF(2); ovf = true; } }
+									}
+								}
+							}
+							if (!rc_ok) rc_top = RC_BAD;                              // an entry of the other strand with several positions was met
+							if (z0 == 0u) { bq[0] = bq[2]; bq[1] = bq[3]; kx[0] = kx[2]; kx[1] = kx[3]; more[0] = more[2]; more[1] = more[3]; }
+						}
+#endif
 					}
 					// A forward pass without a single exact hit can neither vote nor be walked (the stage-B skip below): the lane goes on as
 					// pass 1 with the keys collected above -- none at all means that pass 1 has nothing either, and the read is done
