@@ -466,6 +466,54 @@ uint64_t vg_gmatrix_device_bytes(const vg_gmatrix *gm);
 void vg_gmatrix_destroy(vg_gmatrix *gm);
 int  vg_pairs_host(const uint8_t *gt, const int32_t *gq, uint64_t n_sites, uint32_t n_samples, int32_t min_gq, int threads, uint64_t *counts);
 
+/* The cohort prior: the samples of a cohort called again, with the alt allele frequency q of every site estimated from the cohort
+ * itself in place of the dictionary's two frequencies.  No reference counterpart (the reference calls one sample per process).  The
+ * rule lives in csrc/vg_cprior.h, one statement for the host loop and the kernel: a sample is informative at a site iff
+ * vg_call_site would call it; q starts at the dictionary's alt_freq / (ref_freq + alt_freq) (0.5 where both are 0), and `iters` EM
+ * passes (1 .. 64; 8 is the default of the command line) replace it by (expected alt alleles of the informative samples under
+ * Hardy-Weinberg at q + pseudo * the dictionary's) / (2 * informative samples + pseudo), clamped to [1e-6, 1 - 1e-6]; `pseudo`
+ * (finite, >= 0; 2.0 by default) is the dictionary's weight in alleles.  An informative sample's call is the caller's own choice
+ * among hom-ref / het / hom-alt under Hardy-Weinberg at the final q, its confidence the posterior x the Poisson(7.1) mass of its
+ * depth, gq = (int)(-10 ln(confidence)); any other sample has gt 0, gq 0.  gt / gq are the numbering and the columns of
+ * vg_sample_calls_fetch.  The arithmetic up to the confidence is bit for bit the host loop's; the logarithm is not shared, as in the
+ * caller: the kernel leaves an entry whose -10 ln(confidence) lies within `guard` of an integer with an escape code, and the host
+ * recomputes such an entry with libm before it is handed out.  The values handed out are final.
+ * A vg_cprior lives on one device and is tied to no vg_index; a handle is thread-compatible.
+ *   vg_cprior_create        ALL device memory the handle will ever use: the samples' counters and their calls, sample-major, 2 bytes
+ *                           per site and sample each; q, 8 bytes per site; the two frequency columns, 1 byte per site each; one
+ *                           sample's two counter columns of staging, 2 bytes per site; the caller's factor tables (5 104 bytes) and
+ *                           the escape count (8): 4 * n_samples * n_sites + 12 * n_sites + 5 112 bytes, an empty buffer counting 8.
+ *                           The handle also keeps 8 bytes per site of host memory.  n_samples 1 .. 16 384 (0: VG_EINVAL, more:
+ *                           VG_ETOOBIG), n_sites below 2^32 (else VG_EINVAL; 0 is allowed).  VG_ENOMEM leaves nothing behind
+ *   vg_cprior_set           one sample's counter columns as vg_counts_fetch hands them out (host arrays of n_sites entries, free again
+ *                           on return; clamped again at 63).  A sample never set is uninformative everywhere; setting a sample again
+ *                           replaces it.  VG_EINVAL: a null pointer, a sample out of range -- the handle stays as it was
+ *   vg_cprior_run           the kernel over the counters as they are, with the sites' frequency bytes (host arrays of n_sites
+ *                           entries).  Synchronous.  q_out (may be NULL): n_sites doubles, the final q.  *n_escaped (may be NULL): the
+ *                           entries the kernel left to the host; they are recomputed as vg_cprior_calls hands their column out.
+ *                           guard <= 0: the default, 1e-6; a guard must be below 0.5.  VG_EINVAL: iters or pseudo outside their
+ *                           ranges.  With VG_VERBOSE set the call prints the kernel's own time
+ *   vg_cprior_calls         the final gt / gq columns of one sample (n_sites entries each) after a run; VG_EINVAL without one, or
+ *                           when a sample was set since
+ *   vg_cprior_device_bytes  device memory the handle holds (0 for a null handle)
+ *   vg_cprior_host          the same q, gt and gq by the header's host loop on `threads` host threads (< 1: one), from counters laid
+ *                           out [n_samples][n_sites], sample-major, into gt / gq of that layout and q_out (may be NULL).  Touches no
+ *                           device */
+#ifndef VG_CPRIOR_ITERS
+#define VG_CPRIOR_ITERS     8      /* the defaults of the command line and the Python binding */
+#define VG_CPRIOR_PSEUDO    2.0
+#define VG_CPRIOR_ITERS_MAX 64
+#endif
+typedef struct vg_cprior vg_cprior;
+int  vg_cprior_create(int device, uint64_t n_sites, uint32_t n_samples, vg_cprior **out);
+int  vg_cprior_set(vg_cprior *cp, uint32_t sample, const uint8_t *ref_cnt, const uint8_t *alt_cnt);
+int  vg_cprior_run(vg_cprior *cp, const uint8_t *ref_freq, const uint8_t *alt_freq, int iters, double pseudo, double guard, double *q_out, uint64_t *n_escaped);
+int  vg_cprior_calls(vg_cprior *cp, uint32_t sample, uint8_t *gt, int32_t *gq);
+uint64_t vg_cprior_device_bytes(const vg_cprior *cp);
+void vg_cprior_destroy(vg_cprior *cp);
+int  vg_cprior_host(const uint8_t *ref_cnt, const uint8_t *alt_cnt, uint64_t n_sites, uint32_t n_samples, const uint8_t *ref_freq, const uint8_t *alt_freq, int iters, double pseudo, int threads,
+                    uint8_t *gt, int32_t *gq, double *q_out);
+
 /* The data lines of the joint (multi-sample) VCF rendered on the device.  No reference counterpart.  The rules live in csrc/vg_jtext.h,
  * one statement for the host loop and the kernels.  A sample's CELL for a call (gt, gq) of vg_sample_calls_fetch is "\t" + "0/0" (gt 1),
  * "1/1" (gt 2) or "0/1" (gt 3) + ":" + gq as "%d" prints an int32 (any value: 6 to 16 bytes); a sample without a call shows "\t./.:.".

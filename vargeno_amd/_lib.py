@@ -31,6 +31,7 @@ SYMBOLS = ["vg_last_error", "vg_build_id", "vg_device_count", "vg_device_memory"
            "vg_gunzip_host", "vg_gunzip_device", "vg_gunzip_chunked_host", "vg_gunzip_pushed_host",
            "vg_fastq_stream_begin_gzip", "vg_gzip_stream_stats", "vg_fastq_stream_gzip_checkpoint",
            "vg_gmatrix_create", "vg_gmatrix_set", "vg_gmatrix_pairs", "vg_gmatrix_device_bytes", "vg_gmatrix_destroy", "vg_pairs_host",
+           "vg_cprior_create", "vg_cprior_set", "vg_cprior_run", "vg_cprior_calls", "vg_cprior_device_bytes", "vg_cprior_destroy", "vg_cprior_host",
            "vg_jtext_create", "vg_jtext_destroy", "vg_jtext_device_bytes", "vg_jtext_set", "vg_jtext_text_bound", "vg_jtext_bgzf_bound", "vg_jtext_render", "vg_jtext_render_host",
            "vg_jtext_bgzf_begin", "vg_jtext_bgzf_text", "vg_jtext_bgzf_lines", "vg_jtext_bgzf_end",
            "vg_vcfidx_create", "vg_vcfidx_destroy", "vg_vcfidx_text_host", "vg_vcfidx_text_device", "vg_vcfidx_bgzf", "vg_vcfidx_bound", "vg_vcfidx_finish", "vg_vcfidx_error", "vg_vcfidx_stats",
@@ -216,6 +217,15 @@ def lib():
         L.vg_gmatrix_destroy.argtypes = [vp]
         L.vg_gmatrix_destroy.restype = None
         L.vg_pairs_host.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_int32, C.c_int, vp]
+        L.vg_cprior_create.argtypes = [C.c_int, C.c_uint64, C.c_uint32, C.POINTER(vp)]
+        L.vg_cprior_set.argtypes = [vp, C.c_uint32, vp, vp]
+        L.vg_cprior_run.argtypes = [vp, vp, vp, C.c_int, C.c_double, C.c_double, vp, C.POINTER(C.c_uint64)]
+        L.vg_cprior_calls.argtypes = [vp, C.c_uint32, vp, vp]
+        L.vg_cprior_device_bytes.argtypes = [vp]
+        L.vg_cprior_device_bytes.restype = C.c_uint64
+        L.vg_cprior_destroy.argtypes = [vp]
+        L.vg_cprior_destroy.restype = None
+        L.vg_cprior_host.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_int, C.c_double, C.c_int, vp, vp, vp]
         L.vg_jtext_create.argtypes = [C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(vp)]
         L.vg_jtext_destroy.argtypes = [vp]
         L.vg_jtext_destroy.restype = None

@@ -763,6 +763,95 @@ def pairs_host(gt, gq, min_gq=0, threads=1):
     return out
 
 
+# the cohort prior's defaults and limits (csrc/vg_cprior.h), its kernel's launch, and the device bytes of a handle beside its
+# 4 * n_samples * n_sites + 12 * n_sites: the caller's factor tables and the escape count
+CPRIOR_ITERS, CPRIOR_PSEUDO, CPRIOR_MAX_ITERS, CPRIOR_MAX_SAMPLES = 8, 2.0, 64, 16384
+CPRIOR_BLOCK, CPRIOR_MAX_GRID, CPRIOR_FIXED_BYTES = 256, 8192, 5104 + 8
+
+
+class CohortPrior:
+    """The counters of a cohort on a device (vg_cprior_*): every sample called again with the allele frequency the cohort itself
+    shows at each site, in place of the dictionary's."""
+
+    def __init__(self, n_sites, n_samples, device=0):
+        self._h = None
+        self.n_sites, self.n_samples = int(n_sites), int(n_samples)
+        if self.n_sites < 0 or self.n_samples < 0:
+            raise ValueError("CohortPrior: negative size")
+        h = C.c_void_p()
+        check(lib().vg_cprior_create(int(device), self.n_sites, min(self.n_samples, 2 ** 32 - 1), C.byref(h)))
+        self._h = h
+        self.n_escaped = 0
+
+    def close(self):
+        if self._h:
+            lib().vg_cprior_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def device_bytes(self):
+        return int(lib().vg_cprior_device_bytes(self._h))
+
+    def set(self, sample, ref_cnt, alt_cnt):
+        """One sample's counters (as GenoIndex.counts() returns them; clamped again at 63)."""
+        ref_cnt = np.ascontiguousarray(ref_cnt, dtype=np.uint8)
+        alt_cnt = np.ascontiguousarray(alt_cnt, dtype=np.uint8)
+        if ref_cnt.shape != (self.n_sites,) or alt_cnt.shape != (self.n_sites,):
+            raise ValueError("CohortPrior.set: ref_cnt and alt_cnt hold one entry per site")
+        if not 0 <= int(sample) < 2 ** 32:
+            raise ValueError("CohortPrior.set: sample out of range")
+        check(lib().vg_cprior_set(self._h, int(sample), _ptr(ref_cnt), _ptr(alt_cnt)))
+
+    def run(self, ref_freq, alt_freq, iters=CPRIOR_ITERS, pseudo=CPRIOR_PSEUDO, guard=0):
+        """The kernel over the samples set so far: float64[n_sites], the sites' final q.  ref_freq, alt_freq: the dictionary's n/255
+        bytes.  n_escaped then holds the entries the kernel left to the host (guard as call_device's)."""
+        ref_freq = np.ascontiguousarray(ref_freq, dtype=np.uint8)
+        alt_freq = np.ascontiguousarray(alt_freq, dtype=np.uint8)
+        if ref_freq.shape != (self.n_sites,) or alt_freq.shape != (self.n_sites,):
+            raise ValueError("CohortPrior.run: ref_freq and alt_freq hold one entry per site")
+        q, esc = np.empty(self.n_sites, np.float64), C.c_uint64()
+        check(lib().vg_cprior_run(self._h, _ptr(ref_freq), _ptr(alt_freq), int(iters), float(pseudo), float(guard), _ptr(q), C.byref(esc)))
+        self.n_escaped = int(esc.value)
+        return q
+
+    def calls(self, sample):
+        """(gt, gq) of one sample after run(): final, as GenoIndex.calls() returns them."""
+        if not 0 <= int(sample) < 2 ** 32:
+            raise ValueError("CohortPrior.calls: sample out of range")
+        gt, gq = np.empty(self.n_sites, np.uint8), np.empty(self.n_sites, np.int32)
+        check(lib().vg_cprior_calls(self._h, int(sample), _ptr(gt), _ptr(gq)))
+        return gt, gq
+
+
+def cohort_prior_host(ref_cnt, alt_cnt, ref_freq, alt_freq, iters=CPRIOR_ITERS, pseudo=CPRIOR_PSEUDO, threads=1):
+    """The same by the host loop (vg_cprior_host; no device): ref_cnt, alt_cnt are [n_samples, n_sites]; returns (gt, gq, q) with gt,
+    gq of that shape and q float64[n_sites]."""
+    ref_cnt = np.ascontiguousarray(ref_cnt, dtype=np.uint8)
+    alt_cnt = np.ascontiguousarray(alt_cnt, dtype=np.uint8)
+    ref_freq = np.ascontiguousarray(ref_freq, dtype=np.uint8)
+    alt_freq = np.ascontiguousarray(alt_freq, dtype=np.uint8)
+    if ref_cnt.ndim != 2 or ref_cnt.shape != alt_cnt.shape:
+        raise ValueError("cohort_prior_host: ref_cnt and alt_cnt are [n_samples, n_sites]")
+    n_samples, n_sites = ref_cnt.shape
+    if ref_freq.shape != (n_sites,) or alt_freq.shape != (n_sites,):
+        raise ValueError("cohort_prior_host: ref_freq and alt_freq hold one entry per site")
+    gt, gq, q = np.empty((n_samples, n_sites), np.uint8), np.empty((n_samples, n_sites), np.int32), np.empty(n_sites, np.float64)
+    check(lib().vg_cprior_host(_ptr(ref_cnt), _ptr(alt_cnt), n_sites, n_samples, _ptr(ref_freq), _ptr(alt_freq), int(iters), float(pseudo), int(threads), _ptr(gt), _ptr(gq), _ptr(q)))
+    return gt, gq, q
+
+
 # vg_jtext_record: a data line of the joint VCF -- its first eight fields in `heads` and its run of site indices in `sites`
 JTEXT_RECORD = np.dtype([("head_off", "<u8"), ("site_at", "<u8"), ("head_len", "<u4"), ("n_sites", "<u4")])
 

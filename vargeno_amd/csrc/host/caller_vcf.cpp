@@ -736,6 +736,7 @@ bool write_joint_vcf_planned(const std::vector<uint32_t> &pos, const std::vector
 				if (!declares_gt) dst += kGtDecl;
 				if (!declares_gq) dst += kGqDecl;
 				if (tr.info_counts) dst += kJointInfoDecl;
+				dst += tr.prior_line;
 				const Span cols = joint_first_eight(ln);
 				dst.append(cols.b, cols.e) += "\tFORMAT";
 				for (const JointSample &js : samples) { dst.push_back('\t'); dst += js.name; }
@@ -934,6 +935,7 @@ void write_joint_vcf(const std::vector<uint32_t> &pos, const std::vector<ChrLen>
 				if (!declares_gt) dst += kGtDecl;
 				if (!declares_gq) dst += kGqDecl;
 				if (text_route.info_counts) dst += kJointInfoDecl;
+				dst += text_route.prior_line;
 				const Span cols = first_eight(ln);
 				dst.append(cols.b, cols.e) += "\tFORMAT";
 				for (const JointSample &js : samples) { dst.push_back('\t'); dst += js.name; }

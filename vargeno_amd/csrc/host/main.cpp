@@ -75,6 +75,17 @@
 //                         A SNP list whose header already declares one of the four keys is refused before a device is touched or a
 //                         file created (a list that carries such keys undeclared is not noticed: its lines get them twice).  Unset or
 //                         empty: the file as ever.  Any other value is refused before an index or a device is looked at
+//   VARGENO_JOINT_PRIOR=cohort  joint (and the hidden jointvcf): after the last sample every column is called again with the alt allele
+//                         frequency the cohort itself shows at each site in place of the dictionary's two frequencies (csrc/vg_cprior.h has
+//                         the rule: 8 EM passes, the dictionary's frequency counting as 2 alleles).  joint keeps every finished sample's
+//                         counters for it, 2 more bytes of host memory per site and sample.  The re-called columns are what the joint
+//                         file, its INFO counts and the pair table see; the header gets "##vargenoPrior=cohort,iters=8,pseudo=2" in front of
+//                         #CHROM.  Unset or empty: the file as ever.  Any other value is refused before an index or a device is looked at.
+//                         geno and cohort do not read it
+//   VARGENO_JOINT_PRIOR_ROUTE=device|host  who re-calls: `device`, also unset or empty, the prior kernel on replica 0's device (vg_cprior_*),
+//                         the host loop where the device has no memory for the matrix (one line under VARGENO_VERBOSE); `host`: the
+//                         header's host loop on VARGENO_THREADS threads.  jointvcf has no device and always takes `host`.  The columns
+//                         are the same on both.  VARGENO_VERBOSE prints "cohort prior: <route>, sites, samples, entries recomputed on the host"
 //   VARGENO_JOINT_TEXT_LINES=n  records per rendered span (default: what keeps a span's text near 128 MiB, at most 2^20)
 //   VARGENO_PAIRS_MIN_GQ=n  the table counts a call iff it is called and its GQ is at least n (default 0)
 //   VARGENO_VERBOSE=1     stderr: the index plan and start-up report, one "ingest, replica g:" line per route taken, the "reads:" line with
@@ -207,6 +218,32 @@ static bool joint_info_switch(bool *counts)
 	fprintf(stderr, "vargeno: VARGENO_JOINT_INFO=%s is not understood: `counts` adds NS, AN, AC and AF to the INFO of the joint VCF's lines, unset adds nothing\n", v.c_str());
 	return false;
 }
+// VARGENO_JOINT_PRIOR and VARGENO_JOINT_PRIOR_ROUTE, read once.  false: a value that is none of their words -- said on stderr, in one line
+struct JointPrior {
+	bool cohort = false;                                             // VARGENO_JOINT_PRIOR=cohort
+	bool device = true;                                              // VARGENO_JOINT_PRIOR_ROUTE (`device` unless `host`)
+	int iters = VG_CPRIOR_ITERS;                                     // (the rule's defaults: no variable changes them)
+	double pseudo = VG_CPRIOR_PSEUDO;
+	std::string header_line() const
+	{
+		char b[96];
+		snprintf(b, sizeof b, "##vargenoPrior=cohort,iters=%d,pseudo=%g\n", iters, pseudo);
+		return cohort ? std::string(b) : std::string();
+	}
+};
+static bool joint_prior_switch(JointPrior *jp)
+{
+	const std::string v = env_str("VARGENO_JOINT_PRIOR"), r = env_str("VARGENO_JOINT_PRIOR_ROUTE");
+	jp->cohort = v == "cohort";
+	jp->device = r != "host";
+	if (!v.empty() && !jp->cohort) {
+		fprintf(stderr, "vargeno: VARGENO_JOINT_PRIOR=%s is not understood: `cohort` calls the joint VCF's samples again with allele frequencies estimated from the cohort, unset leaves the calls as they are\n", v.c_str());
+		return false;
+	}
+	if (r.empty() || r == "device" || r == "host") return true;
+	fprintf(stderr, "vargeno: VARGENO_JOINT_PRIOR_ROUTE=%s is not understood: `device` or `host` names who computes the cohort prior, unset is `device`\n", r.c_str());
+	return false;
+}
 // CPUs this process may use: the hardware threads, capped by a cgroup CPU quota (cpu.max: "<quota> <period>"; this pool's GPU boxes
 // give a container 16 CPUs' worth of time on a 256-thread host)
 static int usable_cpus()
@@ -263,7 +300,9 @@ struct GenoOptions {
 	// device, which is device 0, or on the BGZF threads
 	// joint: who makes the data lines (VARGENO_JOINT_TEXT; main() has refused a value that is none of its three words)
 	// ... and whether their INFO carries the counts (VARGENO_JOINT_INFO; refused by main() likewise)
-	const vgh::JointTextRoute joint_text = [] { vgh::JointTextRoute r; (void)joint_text_route(&r); (void)joint_info_switch(&r.info_counts); return r; }();
+	// ... and whether the columns are called again with the cohort's own allele frequencies (VARGENO_JOINT_PRIOR; refused by main() likewise)
+	const JointPrior joint_prior = [] { JointPrior jp; (void)joint_prior_switch(&jp); return jp; }();
+	const vgh::JointTextRoute joint_text = [] { vgh::JointTextRoute r; JointPrior jp; (void)joint_text_route(&r); (void)joint_info_switch(&r.info_counts); (void)joint_prior_switch(&jp); r.prior_line = jp.header_line(); return r; }();
 	const vgh::VcfOutput vcf_out = [this] { vgh::VcfOutput w; (void)vcf_bgzf_route(&w.bgzf); (void)vcf_bgzf_codes(&w.codes); (void)vcf_index_switch(&w.index, w.bgzf); w.device = 0; w.threads = bgzf_threads; w.verbose = verbose; return w; }();
 	explicit GenoOptions(int devices) : have(devices)
 	{
@@ -1368,6 +1407,40 @@ static void joint_pairs_table(const GenoOptions &o, int device, const std::vecto
 	write_pairs_table(o.joint_pairs, names, n_sites, o.pairs_min_gq, counts);
 }
 
+// VARGENO_JOINT_PRIOR=cohort: the samples' columns called again from their counters (kept[s]: ref_cnt and alt_cnt of sample s) with
+// the cohort's own allele frequencies -- through a vg_cprior on `device`, or by the header's host loop: where `on_device` is false
+// (VARGENO_JOINT_PRIOR_ROUTE=host, jointvcf) and where the device has no memory for the matrix (VG_ENOMEM).  The columns are the same.
+static void joint_prior_recall(const JointPrior &jp, bool on_device, int device, int threads, bool verbose, const std::vector<uint8_t> &ref_freq, const std::vector<uint8_t> &alt_freq,
+                               const std::vector<vgh::SiteCounts> &kept, std::vector<vgh::JointSample> &columns)
+{
+	const size_t N = columns.size(), n = ref_freq.size();
+	for (size_t i = 0; i < N; i++) {
+		if (kept[i].ref_cnt.size() != n || kept[i].alt_cnt.size() != n) throw vgh::Error{"sample " + columns[i].name + " has counters for another number of sites than the index has"};
+		columns[i].calls.gt.resize(n); columns[i].calls.gq.resize(n);
+	}
+	int rc = VG_ENOMEM;
+	if (on_device) {
+		vg_cprior *cp = nullptr;
+		uint64_t escaped = 0;
+		rc = vg_cprior_create(device, n, (uint32_t)std::min<size_t>(N, UINT32_MAX), &cp);
+		for (size_t i = 0; rc == VG_OK && i < N; i++) rc = vg_cprior_set(cp, (uint32_t)i, kept[i].ref_cnt.data(), kept[i].alt_cnt.data());
+		if (rc == VG_OK) rc = vg_cprior_run(cp, ref_freq.data(), alt_freq.data(), jp.iters, jp.pseudo, 0, nullptr, &escaped);
+		for (size_t i = 0; rc == VG_OK && i < N; i++) rc = vg_cprior_calls(cp, (uint32_t)i, columns[i].calls.gt.data(), columns[i].calls.gq.data());
+		vg_cprior_destroy(cp);
+		if (rc == VG_OK && verbose) fprintf(stderr, "cohort prior: device, %lu sites, %lu samples, %lu entries recomputed on the host\n", (unsigned long)n, (unsigned long)N, (unsigned long)escaped);
+		if (rc == VG_ENOMEM && verbose) fprintf(stderr, "cohort prior: no device memory for the cohort's counters (%s): the host loop\n", vg_last_error());
+	}
+	if (rc == VG_ENOMEM) {
+		std::vector<uint8_t> r(N * n), a(N * n), gt(N * n);
+		std::vector<int32_t> gq(N * n);
+		for (size_t i = 0; i < N; i++) { std::copy(kept[i].ref_cnt.begin(), kept[i].ref_cnt.end(), r.begin() + i * n); std::copy(kept[i].alt_cnt.begin(), kept[i].alt_cnt.end(), a.begin() + i * n); }
+		rc = vg_cprior_host(r.data(), a.data(), n, (uint32_t)std::min<size_t>(N, UINT32_MAX), ref_freq.data(), alt_freq.data(), jp.iters, jp.pseudo, threads, gt.data(), gq.data(), nullptr);
+		for (size_t i = 0; rc == VG_OK && i < N; i++) { std::copy(gt.begin() + i * n, gt.begin() + (i + 1) * n, columns[i].calls.gt.begin()); std::copy(gq.begin() + i * n, gq.begin() + (i + 1) * n, columns[i].calls.gq.begin()); }
+		if (rc == VG_OK && verbose) fprintf(stderr, "cohort prior: host (%d threads), %lu sites, %lu samples, 0 entries recomputed on the host\n", threads, (unsigned long)n, (unsigned long)N);
+	}
+	if (rc != VG_OK) throw vgh::Error{std::string("the cohort prior failed: ") + vg_last_error()};
+}
+
 // joint_out: `vargeno joint` -- the same workers, but a finished sample's calls are kept as a column (from the caller kernel; the
 // host loop when the device has no memory for it) and ONE file is written after the last sample, if every sample succeeded.
 static int run_cohort(const std::string &prefix, const std::string &manifest, const std::string &vcf_in, const std::string *joint_out = nullptr)
@@ -1403,6 +1476,8 @@ static int run_cohort(const std::string &prefix, const std::string &manifest, co
 	std::atomic<size_t> next{0};
 	std::atomic<int> failed{0};
 	std::vector<vgh::JointSample> columns(joint ? samples.size() : 0);      // joint: the samples' calls, in manifest order
+	const bool prior = joint && o.joint_prior.cohort;                 // VARGENO_JOINT_PRIOR=cohort: ... and their counters, for the re-call after the last one
+	std::vector<vgh::SiteCounts> kept(prior ? samples.size() : 0);
 	const char *const nothing = joint ? "no joint file written" : "no VCF written";
 	// what happens to a finished sample: its own VCF, or its column of the joint file.  false: said on stderr
 	auto deliver = [&](size_t at, vgh::SiteCounts &sc, vgh::SiteCalls &calls, bool have_calls) -> bool {
@@ -1411,6 +1486,7 @@ static int run_cohort(const std::string &prefix, const std::string &manifest, co
 			if (!have_calls) { sc.pos = sites.pos; sc.ref_freq = sites.ref_freq; sc.alt_freq = sites.alt_freq; vgh::call_sites(sc, calls); }
 			columns[at].name = s.out;
 			columns[at].calls = std::move(calls);
+			if (prior) { kept[at].ref_cnt = std::move(sc.ref_cnt); kept[at].alt_cnt = std::move(sc.alt_cnt); }
 			return true;
 		}
 		sc.pos = sites.pos; sc.ref_freq = sites.ref_freq; sc.alt_freq = sites.alt_freq;
@@ -1474,7 +1550,7 @@ static int run_cohort(const std::string &prefix, const std::string &manifest, co
 				if (!invalid && bz_ok) {
 					reduce_selected_counts(o, ix);
 					have_calls = (joint || o.caller_device) && fetch_reduced_calls(o, ix[0], calls);
-					if (!have_calls) fetch_reduced_counts(ix[0], sc);
+					if (!have_calls || prior) fetch_reduced_counts(ix[0], sc);
 				}
 				for (auto *h : ix) VG_CHECK(vg_sample_reset(h, plane));
 				for (auto &m : mu) m.unlock();
@@ -1495,6 +1571,7 @@ static int run_cohort(const std::string &prefix, const std::string &manifest, co
 	for (auto &t : th) t.join();
 	if (joint && !failed.load()) {
 		try {
+			if (prior) joint_prior_recall(o.joint_prior, o.joint_prior.device, 0, o.pairs_threads, o.verbose, sites.ref_freq, sites.alt_freq, kept, columns);      // (replica 0 sits on device 0)
 			vgh::write_joint_vcf(sites.pos, chrlens, columns, vcf_in, *joint_out, &vcf_text, o.vcf_out, o.joint_text);
 			if (!o.joint_pairs.empty()) joint_pairs_table(o, 0, columns, sites.pos.size());      // (replica 0 sits on device 0)
 		}
@@ -1534,6 +1611,9 @@ int main(int argc, const char *argv[])
 		auto with_index = [](int rc) { return rc == EXIT_SUCCESS && vgh::vcf_index_refusals() ? EXIT_FAILURE : rc; };
 		vgh::JointTextRoute joint_text;
 		if ((opt == "joint" || opt == "jointvcf") && (!joint_text_route(&joint_text) || !joint_info_switch(&joint_text.info_counts))) return EXIT_FAILURE;
+		JointPrior joint_prior;
+		if ((opt == "joint" || opt == "jointvcf") && !joint_prior_switch(&joint_prior)) return EXIT_FAILURE;
+		joint_text.prior_line = joint_prior.header_line();
 		// a SNP list that declares a key VARGENO_JOINT_INFO adds: refused here, before an index, a device or the output is looked at
 		if (joint_text.info_counts && ((opt == "joint" && argc == 6) || (opt == "jointvcf" && argc >= 6))) {
 			const std::string tag = vgh::joint_info_declared(argv[opt == "joint" ? 4 : 3]);
@@ -1741,6 +1821,8 @@ int main(int argc, const char *argv[])
 			// sites): <chrlens> <snps.vcf> <out.vcf> <name>=<counts.txt> ...  (no device needed; tests/test_joint_vcf_cpu.py)
 			if (argc < 6) { print_help(); return EXIT_FAILURE; }
 			std::vector<vgh::JointSample> columns;
+			std::vector<vgh::SiteCounts> kept;                            // VARGENO_JOINT_PRIOR=cohort: the samples' counters, and the sites' frequencies as the first table has them
+			std::vector<uint8_t> ref_freq, alt_freq;
 			std::vector<uint32_t> pos;
 			for (int a = 5; a < argc; a++) {
 				const std::string arg = argv[a];
@@ -1748,12 +1830,13 @@ int main(int argc, const char *argv[])
 				if (eq == std::string::npos || eq == 0 || eq + 1 >= arg.size()) { print_help(); return EXIT_FAILURE; }
 				vgh::SiteCounts sc;
 				read_counts_table(arg.substr(eq + 1), sc);
-				if (a == 5) pos = sc.pos;
+				if (a == 5) { pos = sc.pos; ref_freq = sc.ref_freq; alt_freq = sc.alt_freq; }
 				else if (sc.pos != pos) throw vgh::Error{arg.substr(eq + 1) + " lists other sites than " + std::string(argv[5]).substr(std::string(argv[5]).find('=') + 1)};
 				vgh::JointSample js;
 				js.name = arg.substr(0, eq);
 				vgh::call_sites(sc, js.calls);
 				columns.push_back(std::move(js));
+				if (joint_prior.cohort) { kept.emplace_back(); kept.back().ref_cnt = std::move(sc.ref_cnt); kept.back().alt_cnt = std::move(sc.alt_cnt); }
 			}
 			// the output options of `joint`: VARGENO_VCF_BGZF / VARGENO_VCF_CODES (unset: plain text, as ever) and VARGENO_JOINT_TEXT
 			vgh::VcfOutput how;
@@ -1763,6 +1846,7 @@ int main(int argc, const char *argv[])
 			how.threads = std::max(1, std::min(env_int("VARGENO_BGZF_THREADS", vgh::bgzf_threads_default(usable_cpus())), 256));
 			how.verbose = env_int("VARGENO_VERBOSE", 0) != 0;
 			if (how.bgzf == vgh::VcfBgzf::Device && vg_device_count() <= 0) { fprintf(stderr, "vargeno: no HIP device found (VARGENO_VCF_BGZF=host compresses on the host)\n"); return EXIT_FAILURE; }
+			if (joint_prior.cohort) joint_prior_recall(joint_prior, false, 0, std::max(1, env_int("VARGENO_THREADS", usable_cpus())), how.verbose, ref_freq, alt_freq, kept, columns);
 			vgh::write_joint_vcf(pos, vgh::read_chrlens(argv[2]), columns, argv[3], argv[4], nullptr, how, joint_text);
 			return with_index(EXIT_SUCCESS);
 		} else if (opt == "pairstsv") {

@@ -217,12 +217,15 @@ struct JointSample { std::string name; SiteCalls calls; };
 // info_counts (VARGENO_JOINT_INFO=counts): every data line's INFO carries NS / AN / AC / AF over the calls the line shows -- the rule,
 // the tag's text and where it is spliced into the eighth field are ../vg_jtext.h's, compiled by all three routes -- and the header
 // declares the four keys in front of the #CHROM line.  A line with fewer than eight fields is written as without it.
+// prior_line (VARGENO_JOINT_PRIOR=cohort): the samples' columns were called again with the cohort's own allele frequencies
+// (../vg_cprior.h) before they came here; the writer only says so, in this one header line in front of the #CHROM line.  Empty: none.
 enum class JointText { Host, Planned, Device };
 struct JointTextRoute {
 	JointText route = JointText::Host;
 	uint64_t lines = 0;                            // VARGENO_JOINT_TEXT_LINES
 	int device = 0;
 	bool info_counts = false;                      // VARGENO_JOINT_INFO=counts
+	std::string prior_line;                        // "##vargenoPrior=cohort,iters=8,pseudo=2\n" or empty
 };
 // The first of NS, AN, AC, AF that the SNP list's leading header lines declare as an INFO key ("##INFO=<ID=AF,"), or "" -- also when
 // the list cannot be read, which the writer says in its own words.  Such a list would get the key declared twice under info_counts.

@@ -18,6 +18,7 @@
 #include "vg_gunzip.h"
 #include "vg_caller.h"
 #include "vg_pairs.h"
+#include "vg_cprior.h"
 #include "vg_jtext.h"
 #include "vg_vcfidx.h"
 
@@ -5631,6 +5632,233 @@ extern "C" int vg_pairs_host(const uint8_t *gt, const int32_t *gq, uint64_t n_si
 	if (n_sites >= (1ull << 32)) return fail(VG_EINVAL, "vg_pairs_host: 2^32 sites or more");
 	return guarded([&]() -> int {
 		vg_pairs_host_run(gt, gq, n_sites, n_samples, min_gq, threads, counts);
+		return VG_OK;
+	});
+}
+
+// ---- the cohort prior: every sample re-called with the cohort's own allele frequency (vg_cprior.h; no reference counterpart) ------
+// A vg_cprior holds, on one device, the counter words of n_samples samples and their call words, both SAMPLE-MAJOR
+// (word[sample * n_sites + site], 2 bytes each), the sites' final q, the two frequency columns of a run and one sample's columns of
+// staging.  It is no part of a vg_index.
+//
+// vg_cprior_kernel: one lane per site (grid-stride).  The block stages the per-sample factors of the HOST's table -- keep, flip,
+// half, depth, 3 056 bytes -- in LDS; the site's two freq[] entries come from the table in global memory, once.  The EM passes and
+// the last pass walk the samples in index order inside the lane: the 64 lanes of a wave read 64 consecutive 2-byte words of one
+// sample, one 128-byte line per wave and sample, and the passes after the first find the lines in L2 as far as it holds them.  The
+// sum e is the lane's own, in sample order: no cross-lane sum, no atomic but the escape count's (a wave reduction, then one 64-bit
+// add per wave).  Per sample and pass: five LDS reads (their banks are the counters' accident), about a dozen f64 multiplies and
+// adds, one f64 division.  The last pass writes the call words sample-major, again a line per wave and sample.  A call whose
+// -10 ln(confidence) the device's log cannot settle (vg_gq_settled) leaves with VG_CALL_ESCAPE, as in vg_call_kernel.
+// 256 lanes per block: the kernel holds 3 KB of LDS per block and no barrier but the staging's, so the block size only decides how
+// many lanes share one staging; nothing about its speed has been measured.
+constexpr unsigned VG_CPRIOR_BLOCK = 256, VG_CPRIOR_MAX_GRID = 8192;
+constexpr uint32_t VG_CPRIOR_MAX_SAMPLES = 16384;
+__global__ __launch_bounds__(VG_CPRIOR_BLOCK) void vg_cprior_kernel(const uint16_t *__restrict__ cnt, const uint8_t *__restrict__ ref_freq, const uint8_t *__restrict__ alt_freq,
+                                                                    const vg_caller_tables *__restrict__ tab, uint64_t n_sites, uint32_t n_samples, int iters, double pseudo, double guard,
+                                                                    double *__restrict__ q_out, uint16_t *__restrict__ calls, unsigned long long *__restrict__ n_escaped)
+{
+	__shared__ vg_cprior_factors f;
+	{
+		constexpr unsigned words = sizeof(vg_cprior_factors) / sizeof(double);      // (the head of vg_caller_tables: vg_cprior.h)
+		const double *src = (const double *)tab;
+		double *dst = (double *)&f;
+		for (unsigned k = threadIdx.x; k < words; k += VG_CPRIOR_BLOCK) dst[k] = src[k];
+	}
+	__syncthreads();
+	uint32_t escaped = 0;
+	for (uint64_t site = (uint64_t)blockIdx.x * VG_CPRIOR_BLOCK + threadIdx.x; site < n_sites; site += (uint64_t)gridDim.x * VG_CPRIOR_BLOCK) {
+		const uint16_t *col = cnt + site;
+		auto word = [&](uint32_t s) -> unsigned { return col[(uint64_t)s * n_sites]; };
+		const double q = vg_cprior_site_q(f, word, n_samples, vg_cprior_qd(tab->freq[ref_freq[site]], tab->freq[alt_freq[site]]), iters, pseudo);
+		q_out[site] = q;
+		const vg_cprior_hw g = vg_cprior_hw_at(q);
+		for (uint32_t s = 0; s < n_samples; s++) {
+			const vg_site_call c = vg_cprior_call(f, g, word(s));
+			uint32_t gq = 0;
+			if (c.gt != VGC_NONE) {
+				const double y = -10 * log(c.confidence);
+				if (vg_gq_settled(c.confidence, y, guard)) gq = (uint32_t)(int)y;
+				else { gq = VG_CALL_ESCAPE; escaped++; }
+			}
+			calls[(uint64_t)s * n_sites + site] = (uint16_t)((uint32_t)c.gt << 14 | gq);
+		}
+	}
+	for (int o = 32; o > 0; o >>= 1) escaped += __shfl_xor(escaped, o);
+	if ((threadIdx.x & 63) == 0 && escaped) atomicAdd(n_escaped, (unsigned long long)escaped);
+}
+
+// one sample's two counter columns (staging) -> its counter words, clamped
+__global__ __launch_bounds__(256) void vg_cprior_pack_kernel(const uint8_t *__restrict__ ref_cnt, const uint8_t *__restrict__ alt_cnt, uint64_t n_sites, uint16_t *__restrict__ words)
+{
+	for (uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x; s < n_sites; s += (uint64_t)gridDim.x * 256) words[s] = vg_cprior_word(ref_cnt[s], alt_cnt[s]);
+}
+
+struct vg_cprior {
+	int device = 0;
+	uint64_t n_sites = 0, dev_bytes = 0;
+	uint32_t n_samples = 0;
+	uint16_t *d_cnt = nullptr, *d_calls = nullptr;   // [n_samples][n_sites]: r | a << 8 (zero: never set), gt << 14 | gq
+	double *d_q = nullptr;                           // [n_sites]
+	uint8_t *d_rf = nullptr, *d_af = nullptr;        // the frequency columns of a run
+	uint8_t *d_stage = nullptr;                      // one sample's ref and alt columns on their way to the pack kernel
+	vg_caller_tables *d_tab = nullptr;
+	unsigned long long *d_esc = nullptr;
+	hipStream_t stream = nullptr;
+	hipEvent_t ev0 = nullptr, ev1 = nullptr;         // around the kernel (VG_VERBOSE prints the time)
+	bool ran = false;                                // the call words are those of the counters as they are now
+	std::vector<double> q;                           // the last run's q, for the entries that left it with the escape code
+};
+
+static void cprior_free(vg_cprior *cp)
+{
+	if (!cp) return;
+	(void)hipSetDevice(cp->device);
+	if (cp->ev0) (void)hipEventDestroy(cp->ev0);
+	if (cp->ev1) (void)hipEventDestroy(cp->ev1);
+	if (cp->stream) (void)hipStreamDestroy(cp->stream);
+	for (void *p : {(void *)cp->d_cnt, (void *)cp->d_calls, (void *)cp->d_q, (void *)cp->d_rf, (void *)cp->d_af, (void *)cp->d_stage, (void *)cp->d_tab, (void *)cp->d_esc}) if (p) (void)hipFree(p);
+	(void)hipGetLastError();
+	delete cp;
+}
+
+static int cprior_check_rule(const char *who, int iters, double pseudo)
+{
+	if (iters < 1 || iters > VG_CPRIOR_ITERS_MAX) return fail(VG_EINVAL, "%s: iters is 1 .. 64", who);
+	if (!(pseudo >= 0.0 && pseudo <= 1.7976931348623157e308)) return fail(VG_EINVAL, "%s: pseudo is finite and not negative", who);
+	return VG_OK;
+}
+
+extern "C" int vg_cprior_create(int device, uint64_t n_sites, uint32_t n_samples, vg_cprior **out)
+{
+	if (!out) return fail(VG_EINVAL, "null argument");
+	*out = nullptr;
+	if (n_samples == 0) return fail(VG_EINVAL, "vg_cprior_create: no samples");
+	if (n_sites >= (1ull << 32)) return fail(VG_EINVAL, "vg_cprior_create: 2^32 sites or more");
+	if (n_samples > VG_CPRIOR_MAX_SAMPLES) return fail(VG_ETOOBIG, "vg_cprior_create: more than %s samples", std::to_string(VG_CPRIOR_MAX_SAMPLES).c_str());
+	return guarded([&]() -> int {
+		HIP_TRY(hipSetDevice(device));
+		vg_cprior *cp = new vg_cprior;
+		cp->device = device; cp->n_sites = n_sites; cp->n_samples = n_samples;
+		try { cp->q.resize((size_t)n_sites); } catch (...) { delete cp; throw; }
+		const size_t matrix_bytes = (size_t)n_samples * n_sites * 2;
+		struct { void **p; size_t bytes; const char *what; } want[] = {
+			{(void **)&cp->d_cnt, matrix_bytes, "the samples' counters"}, {(void **)&cp->d_calls, matrix_bytes, "the samples' calls"}, {(void **)&cp->d_q, (size_t)n_sites * 8, "the sites' q"},
+			{(void **)&cp->d_rf, (size_t)n_sites, "a frequency column"}, {(void **)&cp->d_af, (size_t)n_sites, "a frequency column"}, {(void **)&cp->d_stage, (size_t)n_sites * 2, "a sample's counter columns"},
+			{(void **)&cp->d_tab, sizeof(vg_caller_tables), "the caller tables"}, {(void **)&cp->d_esc, 8, "the escape count"}};
+		for (auto &w : want) {
+			if (vg_malloc_patient(w.p, w.bytes ? w.bytes : 8) != hipSuccess) {
+				(void)hipGetLastError();
+				*w.p = nullptr;
+				cprior_free(cp);
+				return fail(VG_ENOMEM, "vg_cprior_create: no device memory for %s (%s bytes)", w.what, std::to_string(w.bytes).c_str());
+			}
+			cp->dev_bytes += w.bytes ? w.bytes : 8;
+		}
+		hipError_t e = hipStreamCreateWithFlags(&cp->stream, hipStreamNonBlocking);
+		if (e == hipSuccess) e = hipEventCreate(&cp->ev0);
+		if (e == hipSuccess) e = hipEventCreate(&cp->ev1);
+		if (e == hipSuccess && matrix_bytes) e = hipMemsetAsync(cp->d_cnt, 0, matrix_bytes, cp->stream);
+		if (e == hipSuccess) e = hipMemcpyAsync(cp->d_tab, &host_call_tables(), sizeof(vg_caller_tables), hipMemcpyHostToDevice, cp->stream);
+		if (e == hipSuccess) e = hipStreamSynchronize(cp->stream);
+		if (e != hipSuccess) { cprior_free(cp); return fail(VG_ENODEV, "vg_cprior_create: %s", hipGetErrorString(e)); }
+		*out = cp;
+		return VG_OK;
+	});
+}
+
+extern "C" void vg_cprior_destroy(vg_cprior *cp) { cprior_free(cp); }
+extern "C" uint64_t vg_cprior_device_bytes(const vg_cprior *cp) { return cp ? cp->dev_bytes : 0; }
+
+extern "C" int vg_cprior_set(vg_cprior *cp, uint32_t sample, const uint8_t *ref_cnt, const uint8_t *alt_cnt)
+{
+	if (!cp || !ref_cnt || !alt_cnt) return fail(VG_EINVAL, "null argument");
+	if (sample >= cp->n_samples) return fail(VG_EINVAL, "vg_cprior_set: sample %s is out of range", std::to_string(sample).c_str());
+	cp->ran = false;
+	const uint64_t n = cp->n_sites;
+	if (n == 0) return VG_OK;
+	HIP_TRY(hipSetDevice(cp->device));
+	HIP_TRY(hipMemcpyAsync(cp->d_stage, ref_cnt, n, hipMemcpyHostToDevice, cp->stream));
+	HIP_TRY(hipMemcpyAsync(cp->d_stage + n, alt_cnt, n, hipMemcpyHostToDevice, cp->stream));
+	vg_cprior_pack_kernel<<<(unsigned)std::min<uint64_t>((n + 255) / 256, 4096), 256, 0, cp->stream>>>(cp->d_stage, cp->d_stage + n, n, cp->d_cnt + (uint64_t)sample * n);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipStreamSynchronize(cp->stream));                    // (the host arrays are the caller's again)
+	return VG_OK;
+}
+
+extern "C" int vg_cprior_run(vg_cprior *cp, const uint8_t *ref_freq, const uint8_t *alt_freq, int iters, double pseudo, double guard, double *q_out, uint64_t *n_escaped)
+{
+	if (n_escaped) *n_escaped = 0;
+	if (!cp || ((!ref_freq || !alt_freq) && cp->n_sites)) return fail(VG_EINVAL, "null argument");
+	if (int rc = cprior_check_rule("vg_cprior_run", iters, pseudo)) return rc;
+	if (!(guard > 0)) guard = VG_CALL_GUARD_DEFAULT;
+	if (!(guard < 0.5)) return fail(VG_EINVAL, "vg_cprior_run: a guard of 0.5 or more settles nothing");
+	const uint64_t n = cp->n_sites;
+	if (n == 0) { cp->ran = true; return VG_OK; }
+	HIP_TRY(hipSetDevice(cp->device));
+	cp->ran = false;
+	HIP_TRY(hipMemcpyAsync(cp->d_rf, ref_freq, n, hipMemcpyHostToDevice, cp->stream));
+	HIP_TRY(hipMemcpyAsync(cp->d_af, alt_freq, n, hipMemcpyHostToDevice, cp->stream));
+	HIP_TRY(hipMemsetAsync(cp->d_esc, 0, sizeof(unsigned long long), cp->stream));
+	const unsigned grid = (unsigned)std::min<uint64_t>((n + VG_CPRIOR_BLOCK - 1) / VG_CPRIOR_BLOCK, VG_CPRIOR_MAX_GRID);
+	HIP_TRY(hipEventRecord(cp->ev0, cp->stream));
+	vg_cprior_kernel<<<grid, VG_CPRIOR_BLOCK, 0, cp->stream>>>(cp->d_cnt, cp->d_rf, cp->d_af, cp->d_tab, n, cp->n_samples, iters, pseudo, guard, cp->d_q, cp->d_calls, cp->d_esc);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipEventRecord(cp->ev1, cp->stream));
+	unsigned long long esc = 0;
+	HIP_TRY(hipMemcpyAsync(cp->q.data(), cp->d_q, n * sizeof(double), hipMemcpyDeviceToHost, cp->stream));
+	HIP_TRY(hipMemcpyAsync(&esc, cp->d_esc, sizeof esc, hipMemcpyDeviceToHost, cp->stream));
+	HIP_TRY(hipStreamSynchronize(cp->stream));
+	cp->ran = true;
+	if (q_out) memcpy(q_out, cp->q.data(), n * sizeof(double));
+	if (n_escaped) *n_escaped = esc;
+	if (getenv("VG_VERBOSE")) {
+		float ms = 0;
+		HIP_TRY(hipEventElapsedTime(&ms, cp->ev0, cp->ev1));
+		fprintf(stderr, "[vargeno_hip] vg_cprior_run: %u samples, %lu sites, %d iterations in %u blocks: kernel %.3f ms, %lu entries left to the host\n", cp->n_samples, (unsigned long)n, iters, grid, ms, (unsigned long)esc);
+	}
+	return VG_OK;
+}
+
+extern "C" int vg_cprior_calls(vg_cprior *cp, uint32_t sample, uint8_t *gt, int32_t *gq)
+{
+	if (!cp || ((!gt || !gq) && cp->n_sites)) return fail(VG_EINVAL, "null argument");
+	if (sample >= cp->n_samples) return fail(VG_EINVAL, "vg_cprior_calls: sample %s is out of range", std::to_string(sample).c_str());
+	if (!cp->ran) return fail(VG_EINVAL, "vg_cprior_calls: no vg_cprior_run since the handle was made or a sample was set");
+	const uint64_t n = cp->n_sites;
+	if (n == 0) return VG_OK;
+	return guarded([&]() -> int {
+		HIP_TRY(hipSetDevice(cp->device));
+		std::vector<uint16_t> code((size_t)n), cnt;
+		HIP_TRY(hipMemcpyAsync(code.data(), cp->d_calls + (uint64_t)sample * n, n * sizeof(uint16_t), hipMemcpyDeviceToHost, cp->stream));
+		HIP_TRY(hipStreamSynchronize(cp->stream));
+		const vg_caller_tables &t = host_call_tables();
+		for (uint64_t s = 0; s < n; s++) {
+			gt[s] = (uint8_t)(code[s] >> 14);
+			gq[s] = code[s] & VG_CALL_ESCAPE;
+			if (gq[s] != VG_CALL_ESCAPE) continue;
+			if (cnt.empty()) {                                        // the first escaped entry of the column: its counter words, once
+				cnt.resize((size_t)n);
+				HIP_TRY(hipMemcpyAsync(cnt.data(), cp->d_cnt + (uint64_t)sample * n, n * sizeof(uint16_t), hipMemcpyDeviceToHost, cp->stream));
+				HIP_TRY(hipStreamSynchronize(cp->stream));
+			}
+			const vg_site_call c = vg_cprior_call(t, vg_cprior_hw_at(cp->q[s]), cnt[s]);      // the same function over the same q: the same bits up to the logarithm
+			gt[s] = c.gt;
+			gq[s] = c.gt == VGC_NONE ? 0 : vg_genotype_quality(c.confidence);
+		}
+		return VG_OK;
+	});
+}
+
+extern "C" int vg_cprior_host(const uint8_t *ref_cnt, const uint8_t *alt_cnt, uint64_t n_sites, uint32_t n_samples, const uint8_t *ref_freq, const uint8_t *alt_freq, int iters, double pseudo, int threads,
+                              uint8_t *gt, int32_t *gq, double *q_out)
+{
+	if ((!ref_cnt || !alt_cnt || !ref_freq || !alt_freq || !gt || !gq) && n_sites) return fail(VG_EINVAL, "null argument");
+	if (n_samples == 0) return fail(VG_EINVAL, "vg_cprior_host: no samples");
+	if (n_sites >= (1ull << 32)) return fail(VG_EINVAL, "vg_cprior_host: 2^32 sites or more");
+	if (n_samples > VG_CPRIOR_MAX_SAMPLES) return fail(VG_ETOOBIG, "vg_cprior_host: more than %s samples", std::to_string(VG_CPRIOR_MAX_SAMPLES).c_str());
+	if (int rc = cprior_check_rule("vg_cprior_host", iters, pseudo)) return rc;
+	return guarded([&]() -> int {
+		vg_cprior_host_run(ref_cnt, alt_cnt, n_sites, n_samples, ref_freq, alt_freq, iters, pseudo, threads, gt, gq, q_out);
 		return VG_OK;
 	});
 }
